@@ -12,13 +12,13 @@ are independent (batch mode, code/PLADE/main.cpp:97-158), so every rank register
 data-path collective and the per-pair 4x4 results are gathered to rank 0 over the ranks' loopback rendezvous at the end
 (weak scaling: work per GPU is fixed).  Several GROUPS of pairs are in flight per GPU (one plade_ctx + host thread per
 group, --group consecutive pairs of the batch per plade_registration_pairs call: the plane extraction of a group's clouds
-is one launch sequence); `value` = timed steps / the window between the completion of the last lead-in group and the
-completion of the last timed group, i.e. exactly `steps` registrations complete inside the window with the pipeline full
-on both sides.  A pipeline of M x S registrations in flight is not sampled fairly by a handful of steps (the driver's 20
-are less than one round of 32), so max(K, 32 x registrations in flight) steps are timed, in whole groups: `steps`
-on the line is the number really timed, `requested_steps` echoes K; the occupancy estimator of round 3 is reported
-beside it (`pipeline.occupancy_value`).
+is one launch sequence).  Exactly K steps are timed: the groups after the lead-in hold them, the last one the K mod S
+that are left when K is not a multiple of S.  With the pipeline full on both sides (lead-in before, M untimed groups
+after), each timed group cost the pipeline the time it occupied its worker / M (Little's law); `ms_per_step` is the
+sum of that over the timed groups / K, `value` = 1000 / `ms_per_step` x ranks.
 Rank 0 prints ONE JSON line.  `resident_rank0` is the same pipeline on clouds already resident in HBM.
+--dump-outputs DIR writes what the timed path returned for its last step (timed step K - 1, pair (K - 1) mod pairs of
+rank 0): DIR/T.npy (4 x 4 float32) and DIR/ok.npy (1.0 or 0.0, float32).
 
 Extra objects on the line:
   roofline     -- the dominant kernel of the step, timed live after the timed region under the same load, in two legs:
@@ -33,6 +33,7 @@ Extra objects on the line:
 """
 import argparse
 import json
+import math
 import os
 import sys
 import time
@@ -494,7 +495,7 @@ def _cgroup_throttle():
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=512)
+    ap.add_argument("--steps", type=int, default=512, help="registrations timed (exactly this many)")
     ap.add_argument("--warmup", type=int, default=16)
     ap.add_argument("--points", type=int, default=1000000)
     ap.add_argument("--pairs", type=int, default=0,
@@ -520,7 +521,11 @@ def main():
     ap.add_argument("--profiled-steps", type=int, default=16, help="registrations of the roofline leg (HIP events per launch)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-cli", action="store_true", help="skip the CLI end-to-end leg (64-pair file_pairs.txt through plade_amd/PLADE)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned for its last step to DIR/T.npy and DIR/ok.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -618,9 +623,12 @@ def main():
         executed[M] += 1
         return ctxs[w].registration_dev(ct, cs)
 
-    # Step number i registers pair i % NP; group number j holds the steps j*S .. j*S + S - 1 (consecutive pairs of the batch).
+    # Step number i registers pair i % NP; group number j holds the steps j*S .. j*S + S - 1 (consecutive pairs of the batch),
+    # or fewer where group_size says so (the last timed group when --steps is not a multiple of S).
+    group_size = {}
+
     def members(j):
-        return [j * S + q for q in range(S)]
+        return [j * S + q for q in range(group_size.get(j, S))]
 
     # the timed path: registration(T, target, source) of code/PLADE/plade.h:58 on clouds in (page-locked) HOST memory, in
     # batch mode (main.cpp:97-158 loops over pairs): plade_registration_pairs = S x plade_registration with the plane
@@ -636,16 +644,17 @@ def main():
         return ctxs[w].registration_pairs(cur, nx)
 
     def rgroup(j, w, nxt):
-        executed[w] += S
-        return ctxs[w].registration_pairs_dev([clouds[w][i % NR] for i in members(j)])
+        ids = members(j)
+        executed[w] += len(ids)
+        return ctxs[w].registration_pairs_dev([clouds[w][i % NR] for i in ids])
 
     def run_pipeline(fn, lead_groups, count_groups):
         """Steady-state throughput of the pipeline of M groups in flight: worker w takes groups w, w + M, ... of lead + count + M
         groups (the first `lead` fill the pipeline and are untimed, the last M keep it full until the last timed group
-        completes); the timed window runs from the completion of group number `lead` to the completion of group number
-        lead + count, i.e. EXACTLY count x S registrations complete inside it with the pipeline full on both sides.
-        Returns (seconds of the window, [(step, ok, T)] of the timed steps, occupancy estimate of the same steps in seconds,
-        seconds from start to the last completion)."""
+        completes).  The timed steps are those of groups lead .. lead + count - 1.  A group occupied its worker from the
+        completion of the worker's previous group to its own; with M groups always in flight it cost the pipeline that
+        occupancy / M of wall time (Little's law), and the timed steps took the sum of it over the timed groups.
+        Returns (seconds the timed steps took, [(step, ok, T)] of the timed steps, seconds from start to the last completion)."""
         total = lead_groups + count_groups + M
         stamps, out = [0.0] * total, [None] * total
 
@@ -659,20 +668,14 @@ def main():
             t.start()
         for t in ths:
             t.join()
-        done = sorted(stamps)
-        window = done[lead_groups + count_groups - 1] - done[lead_groups - 1]
-        order = sorted(range(total), key=lambda j: stamps[j])[lead_groups:lead_groups + count_groups]
-        # secondary estimator (Little's law): a group occupied its worker from stamps[j - M] to stamps[j]; with M groups
-        # always in flight the rate is M * S / (mean occupancy of the timed groups)
-        occ = {j: stamps[j] - (stamps[j - M] if j >= M else ts) for j in order}
-        occupancy = sum(occ.values()) / count_groups
+        timed_js = range(lead_groups, lead_groups + count_groups)
+        occ = {j: stamps[j] - (stamps[j - M] if j >= M else ts) for j in timed_js}
         steps = []
-        for j in sorted(order):
+        for j in timed_js:
             for q, i in enumerate(members(j)):
                 steps.append((i, bool(out[j][q][0]), out[j][q][1]))
         run_pipeline.group_occupancy = occ      # seconds a timed group occupied its worker, by group number
-        run_pipeline.completions = done         # completion stamps of all groups, ascending
-        return window, steps, count_groups * occupancy / M, done[-1] - ts
+        return sum(occ.values()) / M, steps, max(stamps) - ts
 
     # warm-up: every worker (context) registers every group composition once through BOTH entry points, so that no
     # first-use allocation or graph capture falls into the timed region; the W warm-up steps the driver asks for are part
@@ -691,25 +694,32 @@ def main():
     for t in wths:
         t.join()
     # lead-in: the W warm-up steps the driver asks for, and at least 8 rounds of the M workers -- they start in lock step
-    # (all in the same stage at once, competing for the same units) and need a few rounds to spread out over the stages
-    lead_groups = max((args.warmup + S - 1) // S, int(os.environ.get("BENCH_LEAD_ROUNDS", "8")) * M)
+    # (all in the same stage at once, competing for the same units) and need a few rounds to spread out over the stages.
+    # A multiple of the NP / gcd(NP, S) groups after which group j registers the same pairs again, so that timed step k
+    # registers pair k % NP whatever M is.
+    cycle = NP // math.gcd(NP, S)
+    lead_groups = max((args.warmup + S - 1) // S, int(os.environ.get("BENCH_LEAD_ROUNDS", "8")) * M, 1)
+    lead_groups = (lead_groups + cycle - 1) // cycle * cycle
+    # K = --steps registrations are timed: ceil(K / S) groups, the last of them holding what is left of K
+    n_timed = args.steps
+    timed_groups = (n_timed + S - 1) // S
+    last_group = lead_groups + timed_groups - 1
+    if n_timed % S:
+        group_size[last_group] = n_timed % S
+        hgroup(last_group, last_group % M, None)      # its composition is warmed on the worker that registers it
     device_sync()
     barrier()
     device_sync()
     cpu0, thr0 = time.process_time(), _cgroup_throttle()
     t_begin = time.perf_counter()
-    # K = --steps; a pipeline of M x S registrations in flight is not sampled fairly by fewer than ~32 rounds of it (the driver's
-    # 20 steps are little more than ONE round of 16), so at least 32 * M * S steps are timed, in whole groups; `steps` on the
-    # line is the number of steps really timed, `requested_steps` echoes K
-    timed_groups = (max(args.steps, int(os.environ.get("BENCH_MIN_ROUNDS", "32")) * RIF) + S - 1) // S   # (BENCH_MIN_ROUNDS: profiling runs)
-    n_timed = timed_groups * S
-    window, timed, occ_elapsed, span = run_pipeline(hgroup, lead_groups, timed_groups)
+    elapsed, timed, span = run_pipeline(hgroup, lead_groups, timed_groups)
     host_occ = dict(run_pipeline.group_occupancy)
-    # the figure for exactly the K steps the driver asked for (in whole groups): the first ceil(K / S) completions of the window
-    req_groups = max(1, min(timed_groups, (args.steps + S - 1) // S))
-    req_window = run_pipeline.completions[lead_groups + req_groups - 1] - run_pipeline.completions[lead_groups - 1]
-    elapsed = window
     cpu1, thr1 = time.process_time(), _cgroup_throttle()
+    if args.dump_outputs and rank == 0:
+        _, ok_last, T_last = timed[-1]
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "T.npy"), np.asarray(T_last, np.float32))
+        np.save(os.path.join(args.dump_outputs, "ok.npy"), np.array([1.0 if ok_last else 0.0], np.float32))
     timed_ids = [t[0] for t in timed]
     oks = [t[1] for t in timed]
     results = [t[2] for t in timed]
@@ -725,14 +735,14 @@ def main():
     bracketed = time.perf_counter() - t_begin
     total_ok = n_ok
     if comm is not None:
-        elapsed, bracketed, occ_elapsed, req_window = comm.all_reduce_max([elapsed, bracketed, occ_elapsed, req_window])
+        elapsed, bracketed = comm.all_reduce_max([elapsed, bracketed])
         total_ok = int(comm.all_reduce_sum([n_ok])[0])
     elif world > 1:
-        tmax = torch.tensor([elapsed, bracketed, occ_elapsed, req_window], dtype=torch.float64, device=dev)
+        tmax = torch.tensor([elapsed, bracketed], dtype=torch.float64, device=dev)
         okt = torch.tensor([n_ok], dtype=torch.int64, device=dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dist.all_reduce(okt, op=dist.ReduceOp.SUM)
-        elapsed, bracketed, occ_elapsed, req_window = (float(tmax[k].item()) for k in range(4))
+        elapsed, bracketed = (float(tmax[k].item()) for k in range(2))
         total_ok = int(okt.item())
 
     # every registration of the same pair, whichever context ran it and whatever its partners in the group were, must
@@ -746,11 +756,14 @@ def main():
         work_by_seed.append({q: st_k.get(q) for q in ("ransac_iterations", "n_planes_tgt", "n_planes_src", "n_matches", "n_clusters",
                                                         "n_candidates_verified")})
     # service time by group composition: a group of S consecutive pairs occupied one of the M workers for occ seconds, i.e. it
-    # cost the pipeline occ / M of wall time = occ / (M * S) per registration (Little's law, as `occupancy_value`)
+    # cost the pipeline occ / M of wall time = occ / (M * S) per registration (Little's law, as `value`); a shorter last
+    # group is a composition of its own and left out
     by_comp = {}
     for j, o in host_occ.items():
-        by_comp.setdefault(j % max(n_comp, 1), []).append(o / (M * S) * 1e3)
+        if j not in group_size:
+            by_comp.setdefault(j % max(n_comp, 1), []).append(o / (M * S) * 1e3)
     comp_ms = sorted(float(np.mean(v)) for v in by_comp.values())
+    group_size.clear()      # the legs below run whole groups
 
     def mmm(v):
         v = sorted(float(x) for x in v if x is not None)
@@ -779,7 +792,7 @@ def main():
     resident_leg = None
     if args.resident_steps > 0:
         r_groups = (args.resident_steps + S - 1) // S
-        r_win, r_res, _, _ = run_pipeline(rgroup, 2 * M, r_groups)
+        r_win, r_res, _ = run_pipeline(rgroup, 2 * M, r_groups)
         device_sync()
         same = all(np.array_equal(T, ref_result[i % NR]) for (i, ok, T) in r_res)
         resident_leg = {"value": r_groups * S / r_win, "unit": "registrations/s (this rank)", "steps": r_groups * S,
@@ -793,7 +806,7 @@ def main():
         for c_ in ctxs:
             c_.set_params(closest_point_mode=0)
         s_groups = (args.closed_form_steps + S - 1) // S
-        s_win, s_res, _, _ = run_pipeline(hgroup, 2 * M, s_groups)
+        s_win, s_res, _ = run_pipeline(hgroup, 2 * M, s_groups)
         device_sync()
         for c_ in ctxs:
             c_.set_params(closest_point_mode=1)
@@ -813,7 +826,7 @@ def main():
             parity = {"note": f"unavailable: {e}"}
     mb = sum(tg.nbytes + sr.nbytes for tg, sr, _ in pairs) / NP / 1e6
     host_leg = {"h2d_MB_per_step": mb, "pcie_GB_per_s": mb * 1e-3 * n_timed / elapsed,
-                "bracketed_value": (lead_groups + timed_groups + M) * S / bracketed if bracketed > 0 else None,
+                "bracketed_value": ((lead_groups + M) * S + n_timed) / bracketed if bracketed > 0 else None,
                 "bracketed_note": "all lead-in + timed + tail steps of this rank over the barrier-to-barrier time (fill and drain of "
                                   "the pipeline and the result gather inside)"}
 
@@ -1053,9 +1066,6 @@ def main():
             "steps": n_timed,
             "warmup": args.warmup,
             "requested_steps": args.steps,
-            "value_at_requested_steps": {"value": world * req_groups * S / req_window if req_window > 0 else None, "steps": req_groups * S,
-                                         "note": "the first ceil(requested_steps / pairs_per_group) group completions of the same timed window: "
-                                                 "with fewer steps than registrations in flight this samples less than one round of the pipeline"},
             "ms_per_step": elapsed / n_timed * 1e3,
             "higher_is_better": True,
             "scaling": "weak",
@@ -1070,7 +1080,7 @@ def main():
                                    "page-locked HOST memory, batch mode (plade_registration_pairs: consecutive pairs of the batch in groups whose plane "
                                    "extraction is one launch sequence; H2D + SoA conversion + bounding boxes of every step inside the timed "
                                    "region, the next group's upload queued under the current group's kernels); "
-                                   "timed window = EXACTLY `steps` completions of the full pipeline (steady state, SURVEY 8d); "
+                                   "exactly `steps` registrations timed with the pipeline full (steady state, SURVEY 8d); "
                                    "plade_params.orient_normals=1 (planes oriented like their inliers' normals: the generator's "
                                    "Manhattan scenes need it, DESIGN.md section 2); CPU baseline applies the same rule",
                        "points_per_cloud": args.points, "pairs_per_rank": args.pairs, "distinct_pairs_total": args.pairs * world,
@@ -1089,7 +1099,7 @@ def main():
             "closed_form_mode_rank0": closed_leg,
             "pair_generation_seconds": t_gen,
             "max_frobenius_vs_ground_truth_rank0": max(errs) if errs else None,
-            "host_rank0": {"cpu_seconds_per_step": (cpu1 - cpu0) / ((lead_groups + timed_groups + M) * S),
+            "host_rank0": {"cpu_seconds_per_step": (cpu1 - cpu0) / ((lead_groups + M) * S + n_timed),
                            "busy_host_threads_avg": (cpu1 - cpu0) / max(span, 1e-9),
                            "cpu_budget": _cpu_budget(),
                            "cgroup_throttled_periods": (thr1[0] - thr0[0]) if thr0 and thr1 else None,
@@ -1099,13 +1109,11 @@ def main():
             "default_mode_rank0": default_mode,
             "pipeline": {"lead_in_steps": lead_groups * S, "timed_steps": n_timed, "requested_steps": args.steps, "tail_steps": M * S,
                          "groups_in_flight": M, "pairs_per_group": S,
-                         "timing": "value = timed_steps / (completion of group #(lead_in + timed) - completion of group #lead_in), per rank, MAX of "
-                                   "the window over ranks: exactly `steps` registrations complete inside the window with the pipeline full on both "
-                                   "sides; barrier + device_sync() before the first and after the last step of the run.  steps = max(requested, "
-                                   "32 x registrations in flight) in whole groups",
-                         "occupancy_value": world * n_timed / occ_elapsed if occ_elapsed > 0 else None,
-                         "occupancy_note": "secondary estimator (round 3's `value`): groups in flight x pairs per group / mean time a timed "
-                                           "group occupied its worker (Little's law)"},
+                         "timing": "ms_per_step = sum over the timed groups of (time the group occupied its worker / groups in flight) / "
+                                   "timed_steps (Little's law), per rank, MAX over ranks; the timed groups hold exactly `steps` registrations "
+                                   "(the last one what is left of steps mod pairs_per_group), lead-in groups before them and one untimed group "
+                                   "per worker after them keep the pipeline full; barrier + device_sync() before the first and after the last "
+                                   "step of the run"},
             "roofline": roofline,
             "roofline_sort": roofline_sort,
             "dominant_by_gpu_time": dominant,

@@ -3,7 +3,8 @@ list properties, CRLF, comments, odd version strings, awkward numbers (nan, inf,
 columns), truncations and trailing garbage -- read by plade_ply_read and by the REFERENCE's reader compiled from its own sources
 (oracle/_ref; in a child process, tests/ply_ref_helper.py, because rply has fixed buffers and may die on a hostile file: such files
 are skipped, the reference has no behaviour there).  Same verdict on every file, same floats bit for bit (NaNs matching NaNs).
-Runs where the reference tree's build exists (this container); tests/test_ply_reader.py holds the committed goldens for everywhere."""
+Where oracle/_ref has not been built, the reference's verdicts on the files of the default seed come from
+tests/golden/ply_fuzz.npz (tools/make_golden_ply_fuzz.py)."""
 import hashlib
 import os
 import struct
@@ -17,7 +18,9 @@ import plade_amd
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF_SO = os.path.join(ROOT, "oracle", "_ref", "libplade_ref.so")
-pytestmark = pytest.mark.skipif(not os.path.exists(REF_SO), reason="oracle/_ref not built (needs the reference tree)")
+GOLDEN = os.path.join(ROOT, "tests", "golden", "ply_fuzz.npz")
+DEFAULT_SEED = 20260929
+N_FILES = 800
 
 TYPES = ["char", "uchar", "short", "ushort", "int", "uint", "float", "double", "int8", "uint8", "int16", "uint16", "int32", "uint32", "float32", "float64"]
 FMT = {"char": "b", "uchar": "B", "short": "h", "ushort": "H", "int": "i", "uint": "I", "float": "f", "double": "d"}
@@ -138,14 +141,34 @@ def reference_verdicts(paths):
     return out
 
 
+def random_files(seed, n=N_FILES):
+    rng = np.random.default_rng(seed)
+    return [random_file(rng) for _ in range(n)]
+
+
+def golden_verdicts(files):
+    """The reference's verdicts on the files of DEFAULT_SEED, as stored: "died", or (ok, n, sha256 of the floats)."""
+    g = np.load(GOLDEN)
+    assert hashlib.sha256(b"".join(files)).hexdigest() == str(g["files_sha256"]), "random_file() no longer makes the files of the golden"
+    return ["died" if st < 0 else (bool(st), int(n), str(d)) for st, n, d in zip(g["status"], g["n"], g["sha256"])]
+
+
 def test_random_ply_files_read_like_the_reference(tmp_path):
-    rng = np.random.default_rng(int(os.environ.get("PLADE_FUZZ_SEED", "20260929")))
+    seed = int(os.environ.get("PLADE_FUZZ_SEED", str(DEFAULT_SEED)))
+    files = random_files(seed)
     paths = []
-    for k in range(800):
+    for k, data in enumerate(files):
         p = tmp_path / f"f{k}.ply"
-        p.write_bytes(random_file(rng))
+        p.write_bytes(data)
         paths.append(str(p))
-    ref = reference_verdicts(paths)
+    if os.path.exists(REF_SO):
+        ref = reference_verdicts(paths)
+        if seed == DEFAULT_SEED:
+            assert ref == golden_verdicts(files)          # the stored verdicts are the reference's
+    elif seed == DEFAULT_SEED:
+        ref = golden_verdicts(files)
+    else:
+        pytest.skip("verdicts of another seed need the reference's reader (oracle/_ref)")
     accepted = refused = died = 0
     for p, want in zip(paths, ref):
         if want == "died":

@@ -1,10 +1,11 @@
 #!/bin/bash
 # quick look: rocprofv3 kernel statistics of a short bench run, per registration (gpurun_out/prof_quick*)
+set -eu     # stop at the first failing step
 R=${GRAFT_REPO_ROOT:-/root/repo}; O=$R/gpurun_out; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-export BENCH_LEAD_ROUNDS=${BENCH_LEAD_ROUNDS:-1} BENCH_MIN_ROUNDS=${BENCH_MIN_ROUNDS:-6}
+export BENCH_LEAD_ROUNDS=${BENCH_LEAD_ROUNDS:-1}
 rm -rf $O/prof_quick
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_quick -o q -- python $R/bench.py --pairs 16 --steps 96 --warmup 8 --resident-steps 0 --closed-form-steps 0 --no-cpu-baseline --no-cli --no-default-mode --no-parity --profiled-steps 0 ${BENCH_EXTRA:-} > $O/prof_quick.log 2>&1
+timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_quick -o q -- python $R/bench.py --pairs 16 --steps 192 --warmup 8 --resident-steps 0 --closed-form-steps 0 --no-cpu-baseline --no-cli --no-default-mode --no-parity --profiled-steps 0 ${BENCH_EXTRA:-} > $O/prof_quick.log 2>&1
 grep "registrations executed" $O/prof_quick.log
 find $O/prof_quick -name "*kernel_trace.csv" -delete
 python3 - <<PY

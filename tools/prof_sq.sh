@@ -3,12 +3,13 @@
 # (MI355X_MICROARCH.md "rocprofv3 PMC slots": WAIT_ANY + WAIT_INST_ANY + ACTIVE_INST_ANY ~ WAVE_CYCLES, in quad-cycles) over the
 # same command as tools/profile_bench.sh.  Output: gpurun_out/prof_sq_summary.csv (per kernel: launches, waves, wave cycles and
 # the three shares), copied to profiles/ by hand.
+set -eu     # stop at the first failing step
 R=${GRAFT_REPO_ROOT:-/root/repo}; O=$R/gpurun_out; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-export BENCH_LEAD_ROUNDS=1 BENCH_MIN_ROUNDS=${BENCH_MIN_ROUNDS:-6}
-CMD="python $R/bench.py --pairs 16 --steps 96 --warmup 8 --resident-steps 0 --closed-form-steps 0 --no-cpu-baseline --no-cli --no-default-mode --no-parity --profiled-steps 0"
+export BENCH_LEAD_ROUNDS=1
+CMD="python $R/bench.py --pairs 16 --steps 192 --warmup 8 --resident-steps 0 --closed-form-steps 0 --no-cpu-baseline --no-cli --no-default-mode --no-parity --profiled-steps 0"
 rm -rf $O/prof_sq
-timeout 900 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU GRBM_GUI_ACTIVE --output-format csv -d $O/prof_sq -o sq -- $CMD > $O/prof_sq.log 2>&1
+timeout -k 10 900 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU GRBM_GUI_ACTIVE --output-format csv -d $O/prof_sq -o sq -- $CMD > $O/prof_sq.log 2>&1
 grep "registrations executed" $O/prof_sq.log
 python3 - <<PY
 import csv, glob, collections, re, subprocess

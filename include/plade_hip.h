@@ -307,6 +307,34 @@ int plade_registration_dev(plade_ctx *ctx, plade_cloud *tgt, plade_cloud *src, f
 int plade_registration_pairs_dev(plade_ctx *ctx, uint32_t count, plade_cloud *const *tgt, plade_cloud *const *src, float *T16,
                                  int32_t *status);
 
+/* ---- normal estimation: clouds without normals (no reference counterpart: the reference requires oriented normals in its
+ * input, README "should provide oriented point normals", and rejects a PLY without them, code/PLADE/util.cpp:1533-1536) -----
+ * Semantics, exact where a CPU restatement can check them bit for bit (plade_amd/csrc/normals.h):
+ *   neighbours   the k_eff = min(k, n) points j -- i itself included -- with the smallest d(i, j) = fp32 FLANN L2 of (p_i, p_j)
+ *                ((dx*dx + dy*dy) + dz*dz), ties broken by the smaller original index j; listed in ascending (d, j) order
+ *   PCA          fp64 on the neighbours' coordinates relative to p_i, accumulated in the listed order (centroid, then the
+ *                covariance about it); normal = unit eigenvector of the smallest eigenvalue l0, written as fp32; curvature =
+ *                l0 / (l0 + l1 + l2).  Independent of launch shape, grid cell size and what else is in flight.
+ *   orientation  n is flipped when (v - p_i) . n < 0 (PCL's flipNormalTowardsViewpoint); viewpoint NULL = (0, 0, 0), the
+ *                sensor origin of a scan in its own frame
+ *   degenerate   k_eff < 3 or a covariance that is exactly zero (all neighbours coincide): normal and curvature NaN -- such points
+ *                never pass the plane tests of the registration (a NaN comparison is false)
+ * Errors: PLADE_EINVAL for n = 0, k outside [3, 64], stride < 3, a non-finite coordinate or viewpoint; the context stays usable.
+ * plade_estimate_normals   xyz: n points of `stride` floats (host).  pos_nrm_out: n x 6 (x y z copied, nx ny nz); curvature_out
+ *                          (n floats) and nbr_out (n x k int32: the neighbour list, -1 behind the k_eff entries when n < k) may be
+ *                          NULL.  plade_stats_get then reports normals_grid_s / normals_search_s (HIP events on the context's
+ *                          stream: grid build including its host waits below, search + PCA), normals_grid_builds and
+ *                          normals_ring_queries (points the 27-cell search could not finish).
+ * plade_cloud_upload_xyz   the same estimate straight into a resident cloud (plade_cloud_upload's layout): the coordinates are
+ *                          uploaded once and the normals never leave the device.  The call still waits on the host several times
+ *                          for small results: the bounding box, the occupied-cell count of each grid build (up to four builds
+ *                          while the cell is adapted), the end of the estimate and the cloud's own bounding box.  Register the
+ *                          cloud with plade_registration_dev / plade_registration_pairs_dev, free it with plade_cloud_free. */
+int plade_estimate_normals(plade_ctx *ctx, const float *xyz, uint32_t n, uint32_t stride, int32_t k, const float *viewpoint,
+                           float *pos_nrm_out, float *curvature_out, int32_t *nbr_out);
+int plade_cloud_upload_xyz(plade_ctx *ctx, const float *xyz, uint32_t n, uint32_t stride, int32_t k, const float *viewpoint,
+                           plade_cloud **out);
+
 /* ---- instrumentation ---------------------------------------------------------------------- */
 /* Named intermediates of the last registration (when params.dump != 0). Returns 0 if found;
  * the pointer stays valid until the next call on this ctx. */
@@ -344,6 +372,10 @@ int plade_diag_launches(plade_ctx *ctx, uint32_t count, uint32_t blocks, uint32_
  * false: unreadable / malformed file, no vertex points, "the number of points does not equal to the number of normals in the
  * file" (util.cpp:1533-1536), an empty cloud.  Host code only: no context, no GPU. */
 int plade_ply_read(const char *path, float **pos_nrm, uint64_t *n, char *err, size_t err_cap);
+/* plade_ply_read that also accepts a vertex element without nx ny nz: *has_normals = 0 and NaN in the normal columns (estimate
+ * them with plade_estimate_normals / plade_cloud_upload_xyz, stride 6).  A file with normals reads as with plade_ply_read
+ * (*has_normals = 1); every other failure keeps plade_ply_read's message.  Free with plade_ply_free.  Host code only. */
+int plade_ply_read_points(const char *path, float **pos_nrm, uint64_t *n, int32_t *has_normals, char *err, size_t err_cap);
 void plade_ply_free(float *pos_nrm);
 /* Seam of the one host-side stage whose tie-breaking shapes the result: the order in which
  * std::sort(sortVec.begin(), sortVec.end(), myCompareGreater) (code/PLADE/util.cpp:335-345, util.h:347-365) leaves clusters

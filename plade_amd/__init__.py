@@ -26,6 +26,7 @@ ABI_SYMBOLS = [
     "plade_closest_points", "plade_lines_meet", "plade_ply_read", "plade_ply_free",
     "plade_device_count", "plade_comm_unique_id", "plade_comm_create", "plade_comm_all_gather", "plade_comm_destroy", "plade_comm_last_error",
     "plade_set_candidate_shard_comm",
+    "plade_estimate_normals", "plade_cloud_upload_xyz", "plade_ply_read_points",
 ]
 
 
@@ -97,6 +98,10 @@ def load_library(path=LIB_PATH):
     sig("plade_diag_line_solver_host", argtypes=[i32, p, p, p, p, u32, p, p, p])
     sig("plade_ply_read", argtypes=[C.c_char_p, C.POINTER(C.POINTER(C.c_float)), C.POINTER(u64), C.c_char_p, C.c_size_t])
     sig("plade_ply_free", argtypes=[C.POINTER(C.c_float)], restype=None)
+    sig("plade_ply_read_points", argtypes=[C.c_char_p, C.POINTER(C.POINTER(C.c_float)), C.POINTER(u64), C.POINTER(i32), C.c_char_p,
+                                           C.c_size_t])
+    sig("plade_estimate_normals", argtypes=[p, p, u32, u32, i32, p, p, p, p])
+    sig("plade_cloud_upload_xyz", argtypes=[p, p, u32, u32, i32, p, C.POINTER(p)])
     sig("plade_sort_segments", argtypes=[p, p, p, p, u32, C.c_int, p, p])
     sig("plade_set_candidate_shard", argtypes=[p, u32, u32, u32, EXCHANGE_FN, p])
     sig("plade_registration_minsupport", argtypes=[p, p, u32, p, u32, i32, i32, p])
@@ -177,6 +182,38 @@ def read_ply(path):
         L.plade_ply_free(ptr)
 
 
+def read_ply_points(path):
+    """plade_ply_read_points (no GPU): read_ply that also accepts a vertex element without nx ny nz.  Returns (array, has_normals):
+    the (N, 6) float32 array x y z nx ny nz -- NaN normal columns when has_normals is False (estimate them with
+    Context.estimate_normals(array[:, :3]) or Context.upload_xyz) -- and whether the file had normals.  Every other failure
+    raises PladeError with read_ply's message."""
+    L = load_library()
+    ptr, n, has = C.POINTER(C.c_float)(), C.c_uint64(0), C.c_int32(0)
+    err = C.create_string_buffer(512)
+    rc = L.plade_ply_read_points(os.fsencode(path), C.byref(ptr), C.byref(n), C.byref(has), err, len(err))
+    if rc != 0:
+        raise PladeError(rc, err.value.decode(errors="replace"))
+    try:
+        return np.ctypeslib.as_array(ptr, shape=(n.value, 6)).copy(), bool(has.value)
+    finally:
+        L.plade_ply_free(ptr)
+
+
+def _xyz_view(xyz):
+    """(N, >= 3) float32 array -> (C-contiguous array, n, stride in floats) for the xyz entry points (no copy of an N x 6 cloud)."""
+    a = _f32(xyz)
+    if a.ndim != 2 or a.shape[1] < 3:
+        raise ValueError(f"an (N, 3) array x y z (or wider rows whose first three columns are x y z) is required, got shape {a.shape}")
+    return a, len(a), a.shape[1]
+
+
+def _viewpoint(viewpoint):
+    v = _f32(viewpoint).reshape(-1)
+    if v.shape != (3,):
+        raise ValueError("viewpoint: three coordinates")
+    return v
+
+
 def line_solver_host(kind, a, b, c, d):
     """Host seam (no GPU): the register form of the reference's SVD solver as the kernels inline it -- kind 0: closest points of
     n line pairs -> (q1, q2, ok), kind 1: meeting points -> (point, ok); ok 1 solved / 0 rank-deficient / -1 guard fired."""
@@ -204,8 +241,11 @@ def cluster_order(sizes, mode=0, depth_limit=-1):
 class Cloud:
     """Device-resident oriented point cloud (plade_cloud)."""
 
-    def __init__(self, ctx, pos_nrm):
+    def __init__(self, ctx, pos_nrm, handle=None):
         self.ctx = ctx
+        if handle is not None:          # a cloud the library made (Context.upload_xyz)
+            self.n, self.h = handle
+            return
         a = _f32(pos_nrm)
         if a.ndim != 2 or a.shape[1] != 6:
             raise ValueError(f"Cloud: an (N, 6) array x y z nx ny nz is required, got shape {a.shape}")
@@ -542,6 +582,31 @@ class Context:
 
     def upload(self, pos_nrm):
         return Cloud(self, pos_nrm)
+
+    # ---- clouds without normals -------------------------------------------------------------
+    def estimate_normals(self, xyz, k=16, viewpoint=(0.0, 0.0, 0.0), curvature=False, neighbours=False):
+        """plade_estimate_normals: k-nearest-neighbour PCA normals of an (N, 3) cloud (or the x y z columns of wider rows),
+        oriented toward `viewpoint`.  Returns the (N, 6) float32 array x y z nx ny nz; with curvature / neighbours also the
+        (N,) float32 curvature and the (N, k) int32 neighbour lists (ascending (distance, index), the point itself included;
+        -1 behind the min(k, N) entries).  NaN normal and curvature where fewer than 3 points or only coincident points are
+        the neighbourhood."""
+        a, n, stride = _xyz_view(xyz)
+        v = _viewpoint(viewpoint)
+        out = np.empty((n, 6), np.float32)
+        curv = np.empty(n, np.float32) if curvature else None
+        nbr = np.empty((n, max(int(k), 0)), np.int32) if neighbours else None
+        self._check(self.L.plade_estimate_normals(self.h, _ptr(a), n, stride, int(k), _ptr(v), _ptr(out), _ptr(curv), _ptr(nbr)))
+        res = (out,) + ((curv,) if curvature else ()) + ((nbr,) if neighbours else ())
+        return res[0] if len(res) == 1 else res
+
+    def upload_xyz(self, xyz, k=16, viewpoint=(0.0, 0.0, 0.0)):
+        """plade_cloud_upload_xyz: upload an (N, 3) cloud and estimate its normals into a resident Cloud (the point data makes no host round
+        trip) for registration_dev / registration_pairs_dev."""
+        a, n, stride = _xyz_view(xyz)
+        v = _viewpoint(viewpoint)
+        h = C.c_void_p()
+        self._check(self.L.plade_cloud_upload_xyz(self.h, _ptr(a), n, stride, int(k), _ptr(v), C.byref(h)))
+        return Cloud(self, None, handle=(n, h))
 
     def pin(self, arr):
         """Page-lock a C-contiguous float32 array the caller keeps alive (plade_host_pin); registration() calls that are

@@ -93,6 +93,13 @@ void cloud_upload(plade_ctx *ctx, const float *pos_nrm, uint32_t n, CloudDev &ou
     finish_uploads(ctx, cl, 1);
 }
 
+void cloud_shape(CloudDev &out, uint32_t n) { shape_cloud(out, n); }
+
+void cloud_finish_device(plade_ctx *ctx, CloudDev &out) {
+    CloudDev *cl[1] = {&out};
+    finish_uploads(ctx, cl, 1);
+}
+
 void cloud_upload_many(plade_ctx *ctx, int count, const float *const ptr[], const uint32_t n[], CloudDev *const out[]) {
     PLADE_REQUIRE(count >= 1 && count <= 2 * PLADE_GROUP_MAX, PLADE_EINVAL, "cloud_upload_many: too many clouds");
     for (int i = 0; i < count; ++i) {

@@ -83,13 +83,14 @@ struct plade_cloud {
     std::vector<float> host_copy;  // pos_nrm kept for the small host-side gathers
 };
 
-namespace plade { struct RegistrationWork; struct RansacWork; }
+namespace plade { struct RegistrationWork; struct RansacWork; struct NormalsWork; }
 namespace plade { void comm_all_gather_dev(plade_comm *c, const void *d_send, void *d_recv, size_t bytes, hipStream_t stream); }
 
 struct plade_ctx {
     int device = 0;
     plade::RegistrationWork *reg_work = nullptr;
     plade::RansacWork *ransac_work = nullptr;
+    plade::NormalsWork *normals_work = nullptr;   // grid and lists of plade_estimate_normals / plade_cloud_upload_xyz
     plade_ctx *peers[PLADE_GROUP_MAX - 1] = {};   // the contexts of pairs 1.. of a group (plade_registration_pairs): stream, aux, work areas
     hipEvent_t ev_group = nullptr;   // end of a group's joint plane extraction on `stream` (the peers' streams wait for it)
     bool in_group = false;      // this context carries one pair of a group of several (register_group)
@@ -529,6 +530,9 @@ struct StageTimer {
 // ---- kernels / stages implemented across the .hip files ----------------------------------
 // cloud upload: AoS N x 6 (host) -> SoA on device
 void cloud_upload(plade_ctx *ctx, const float *pos_nrm, uint32_t n, CloudDev &out);
+// a cloud shaped for n points whose AoS copy the device has just written (estimated normals): SoA planes + bounding box
+void cloud_shape(CloudDev &out, uint32_t n);
+void cloud_finish_device(plade_ctx *ctx, CloudDev &out);
 void cloud_upload_pair(plade_ctx *ctx, const float *tgt, uint32_t n_t, CloudDev &out_t, const float *src, uint32_t n_s, CloudDev &out_s);
 // `count` (<= 2 * PLADE_GROUP_MAX) clouds in one go: all copies first, one wait, then conversion + bounding boxes of all of them, one wait
 void cloud_upload_many(plade_ctx *ctx, int count, const float *const ptr[], const uint32_t n[], CloudDev *const out[]);

@@ -110,6 +110,26 @@ struct Watch {
     }
 };
 
+// PLADE_ESTIMATE_NORMALS=<k> (opt-in, 0 / unset = off): a PLY without nx ny nz is accepted and its normals are estimated on the
+// GPU (plade_estimate_normals: k nearest neighbours, viewpoint (0, 0, 0) of the file's own frame); files with normals keep them.
+// Unset, such a file fails with the reference's message (util.cpp:1533-1536).
+int estimate_normals_k() {
+    static const int k = [] { const char *w = getenv("PLADE_ESTIMATE_NORMALS"); return w ? atoi(w) : 0; }();
+    return k;
+}
+// read_ply_pos_nrm, or under PLADE_ESTIMATE_NORMALS read_ply_points (*estimate: the file had no normals)
+bool read_ply_cloud(const std::string &file_name, std::vector<float> &buf, std::string &err, std::vector<std::string> *warnings,
+                    const std::function<void()> *before_grow, bool *estimate) {
+    *estimate = false;
+    if (!estimate_normals_k()) return plade::read_ply_pos_nrm(file_name, buf, err, warnings, before_grow);
+    bool has_normals = true;
+    if (!plade::read_ply_points(file_name, buf, has_normals, err, warnings, before_grow)) return false;
+    *estimate = !has_normals;
+    return true;
+}
+// the normal columns of an x y z nx ny nz array, estimated in place on the calling thread's context
+bool estimate_in_place(const std::string &file_name, std::vector<float> &buf);
+
 std::string extension(const std::string &file_name) {  // util.cpp:525-531
     std::string::size_type dot = file_name.find_last_of('.');
     std::string::size_type slash = file_name.find_last_of("/\\");
@@ -117,6 +137,24 @@ std::string extension(const std::string &file_name) {  // util.cpp:525-531
     return std::string(file_name.begin() + dot + 1, file_name.end());
 }
 
+}  // namespace
+
+namespace {
+bool estimate_in_place(const std::string &file_name, std::vector<float> &buf) {
+    plade_ctx *ctx = context();
+    if (!ctx) return false;
+    const int k = estimate_normals_k();
+    const float view[3] = {0.f, 0.f, 0.f};
+    const size_t n = buf.size() / 6;
+    trace("normals: estimating");
+    // (in place: the upload of the coordinates precedes the read-back of the result on the context's stream)
+    if (plade_estimate_normals(ctx, buf.data(), (uint32_t)n, 6, k, view, buf.data(), nullptr, nullptr) != PLADE_OK) {
+        con_err() << "estimating normals failed: " << plade_last_error(ctx) << std::endl;
+        return false;
+    }
+    con_out() << "no normals in " << file_name << ": estimated from " << k << " nearest neighbours" << std::endl;
+    return true;
+}
 }  // namespace
 
 void plade_cli_trace(const char *what) { trace(what); }
@@ -230,11 +268,13 @@ bool register_packed(Eigen::Matrix<float, 4, 4> &transformation, const float *tg
 bool load_packed(const std::string &file_name, std::vector<float> &buf) {
     std::string err;
     std::vector<std::string> warnings;
-    if (!plade::read_ply_pos_nrm(file_name, buf, err, &warnings)) {
+    bool estimate = false;
+    if (!read_ply_cloud(file_name, buf, err, &warnings, nullptr, &estimate)) {
         if (!err.empty()) con_err() << err << std::endl;
         return false;
     }
     for (auto &w : warnings) con_out() << w << std::endl;
+    if (estimate && !estimate_in_place(file_name, buf)) return false;
     return !buf.empty();
 }
 
@@ -300,7 +340,7 @@ void registration_group(size_t count, Eigen::Matrix<float, 4, 4> *transformation
     // The files of the group are read side by side (a 1M-point binary PLY is ~10 ms of parsing and copying; sixteen of them one
     // after the other would take longer than the group's registration); what the loads have to say is kept and printed below,
     // pair by pair, where the sequential run prints it.
-    struct Loaded { bool tried = false, ok = false; std::string err; std::vector<std::string> warnings; };
+    struct Loaded { bool tried = false, ok = false, estimate = false; std::string err; std::vector<std::string> warnings; };
     Loaded loaded[2 * GMAX];
     {
         std::vector<float> *const b = bufs;
@@ -317,7 +357,7 @@ void registration_group(size_t count, Eigen::Matrix<float, 4, 4> *transformation
                 PinnedVec *pin = &g_pins[2 * i + side];
                 readers.emplace_back([file, l, buf, pin]() {
                     const std::function<void()> before_grow = [pin]() { pin->release(); };
-                    l->ok = plade::read_ply_pos_nrm(*file, *buf, l->err, &l->warnings, &before_grow) && !buf->empty();
+                    l->ok = read_ply_cloud(*file, *buf, l->err, &l->warnings, &before_grow, &l->estimate) && !buf->empty();
                 });
             }
         }
@@ -327,9 +367,10 @@ void registration_group(size_t count, Eigen::Matrix<float, 4, 4> *transformation
         for (auto &t : readers) t.join();
         trace("group: files read");
     }
-    auto report = [&](const Loaded &l) {   // load_packed's messages
+    auto report = [&](const Loaded &l, const std::string &file, std::vector<float> &buf) {   // load_packed's messages
         if (!l.ok && !l.err.empty()) con_err() << l.err << std::endl;
         if (l.ok || l.err.empty()) for (auto &w : l.warnings) con_out() << w << std::endl;
+        if (l.ok && l.estimate) return estimate_in_place(file, buf);
         return l.ok;
     };
     for (size_t i = 0; i < count; ++i) {
@@ -342,8 +383,8 @@ void registration_group(size_t count, Eigen::Matrix<float, 4, 4> *transformation
             con_err() << "only PLY format is accepted" << std::endl;
             continue;
         }
-        if (!report(loaded[2 * i])) { con_err() << "loading target point cloud failed" << std::endl; continue; }
-        if (!report(loaded[2 * i + 1])) { con_err() << "loading source point cloud failed" << std::endl; continue; }
+        if (!report(loaded[2 * i], target_cloud_files[i], bufs[2 * i])) { con_err() << "loading target point cloud failed" << std::endl; continue; }
+        if (!report(loaded[2 * i + 1], source_cloud_files[i], bufs[2 * i + 1])) { con_err() << "loading source point cloud failed" << std::endl; continue; }
         Item it{i, bufs[2 * i].data(), bufs[2 * i + 1].data(), bufs[2 * i].size() / 6, bufs[2 * i + 1].size() / 6, false};
         if (it.n_s >= it.n_t * 1.2f) {
             std::swap(it.tg, it.sr);
@@ -389,11 +430,13 @@ bool load_ply_cloud(const std::string &file_name, pcl::PointCloud<pcl::PointNorm
     std::vector<float> pos_nrm;
     std::string err;
     std::vector<std::string> warnings;
-    if (!plade::read_ply_pos_nrm(file_name, pos_nrm, err, &warnings)) {
+    bool estimate = false;
+    if (!read_ply_cloud(file_name, pos_nrm, err, &warnings, nullptr, &estimate)) {
         if (!err.empty()) con_err() << err << std::endl;
         return false;
     }
     for (auto &w : warnings) con_out() << w << std::endl;
+    if (estimate && !estimate_in_place(file_name, pos_nrm)) return false;
     const size_t n = pos_nrm.size() / 6;
     cloud.resize(n);
     for (size_t i = 0; i < n; ++i) {

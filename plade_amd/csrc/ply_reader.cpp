@@ -192,8 +192,10 @@ bool read_value(Cursor &c, int type, int mode, bool swap, std::string &w, double
 
 struct FileCloser { FILE *f; ~FileCloser() { if (f) fclose(f); } };
 
+// has_normals == nullptr: a vertex element without nx ny nz fails (the reference's load_ply_cloud); else it is read with NaN
+// normals and *has_normals tells which kind the file was
 bool read_body(const std::string &path, std::vector<float> &out, std::string &err, std::vector<std::string> *warnings,
-               const std::function<void()> *before_grow) {
+               const std::function<void()> *before_grow, bool *has_normals) {
     auto size_to = [&](size_t floats) {
         if (out.size() == floats) return;
         if (floats > out.capacity() && before_grow) (*before_grow)();     // the allocation is about to move
@@ -257,6 +259,7 @@ bool read_body(const std::string &path, std::vector<float> &out, std::string &er
         if (a != -1 && b != -1 && c != -1) { col[3] = a; col[4] = b; col[5] = c; }
     }
     const bool has_pos = col[0] != -1, has_nrm = col[3] != -1;
+    const bool xyz_only = has_normals && has_pos && !has_nrm;   // accepted by read_ply_points only
     // an element cannot hold more instances than the rest of the file has bytes for (the count is untrusted input); counts
     // beyond the C ABI's 32-bit point count are refused
     {
@@ -290,12 +293,15 @@ bool read_body(const std::string &path, std::vector<float> &out, std::string &er
             data.resize((size_t)file_size);
             if (fread(data.data() + have, 1, data.size() - have, f) != data.size() - have) return fail("error occurred while parsing ply file: " + path);
         }
-        if (vertex >= 0 && has_pos && has_nrm) size_to(6 * (size_t)h.elems[vertex].count);
+        if (vertex >= 0 && has_pos && (has_nrm || xyz_only)) size_to(6 * (size_t)h.elems[vertex].count);
+        if (vertex >= 0 && xyz_only)
+            for (long long i = 0; i < h.elems[vertex].count; ++i)
+                for (int q = 3; q < 6; ++q) out[6 * (size_t)i + q] = NAN;
         Cursor c{data.data() + h.data_offset, data.data() + data.size()};
         std::string w;
         for (size_t ei = 0; ei < h.elems.size(); ++ei) {
             const Elem &e = h.elems[ei];
-            const bool keep = (int)ei == vertex && has_pos && has_nrm;
+            const bool keep = (int)ei == vertex && has_pos && (has_nrm || xyz_only);
             const size_t np = e.props.size();
             std::vector<int> slots(np, -1);
             // (two coordinates fed by one column cannot happen: the names differ)
@@ -330,7 +336,8 @@ bool read_body(const std::string &path, std::vector<float> &out, std::string &er
     // util.cpp:1519-1545
     if (vertex < 0 || (!has_pos && !has_nrm)) return fail(vertex < 0 && h.elems.empty() ? "failed to read ply file (no elements): " + path
                                                                                           : "no points in the vertex element of " + path);
-    if (has_pos != has_nrm) return fail("the number of points does not equal to the number of normals in the file");
+    if (has_pos != has_nrm && !xyz_only) return fail("the number of points does not equal to the number of normals in the file");
+    if (has_normals) *has_normals = has_nrm;
     if (warnings) {
         const Elem &e = h.elems[vertex];
         auto has = [&](const char *a, const char *b, const char *c3, bool fl) {
@@ -344,7 +351,7 @@ bool read_body(const std::string &path, std::vector<float> &out, std::string &er
         for (size_t i = 0; i < h.elems.size(); ++i)
             if (h.elems[i].name != "vertex" && h.elems[i].count > 0 && !h.elems[i].props.empty())
                 warnings->push_back("Warning: unknown element '" + h.elems[i].name);       // util.cpp:1542 (the quote is not closed there either)
-        if (!out.empty()) {                                                                // ply_reader.cpp:351-355
+        if (!out.empty() && has_nrm) {                                                     // ply_reader.cpp:351-355
             const float len = std::sqrt(out[3] * out[3] + out[4] * out[4] + out[5] * out[5]);
             if (std::abs(1.0 - len) > 1e-4)
                 warnings->push_back("normals (defined on element 'vertex') not normalized (length of the first normal vector is " + std::to_string(len) + ")");
@@ -355,11 +362,12 @@ bool read_body(const std::string &path, std::vector<float> &out, std::string &er
 
 }  // namespace
 
-bool read_ply_pos_nrm(const std::string &path, std::vector<float> &out, std::string &err, std::vector<std::string> *warnings,
-                      const std::function<void()> *before_grow) {
+namespace {
+bool read_ply(const std::string &path, std::vector<float> &out, std::string &err, std::vector<std::string> *warnings,
+              const std::function<void()> *before_grow, bool *has_normals) {
     // never throws: a header that asks for more memory than there is ends in `false` like any other malformed file
     try {
-        if (read_body(path, out, err, warnings, before_grow)) return true;
+        if (read_body(path, out, err, warnings, before_grow, has_normals)) return true;
         if (err.empty()) err = "empty point cloud in " + path;
         out.clear();
         return false;
@@ -368,6 +376,18 @@ bool read_ply_pos_nrm(const std::string &path, std::vector<float> &out, std::str
         err = std::string("cannot read PLY file ") + path + ": " + e.what();
         return false;
     }
+}
+}  // namespace
+
+bool read_ply_pos_nrm(const std::string &path, std::vector<float> &out, std::string &err, std::vector<std::string> *warnings,
+                      const std::function<void()> *before_grow) {
+    return read_ply(path, out, err, warnings, before_grow, nullptr);
+}
+
+bool read_ply_points(const std::string &path, std::vector<float> &out, bool &has_normals, std::string &err,
+                     std::vector<std::string> *warnings, const std::function<void()> *before_grow) {
+    has_normals = false;
+    return read_ply(path, out, err, warnings, before_grow, &has_normals);
 }
 
 bool write_ply_pos_nrm(const std::string &path, const float *pos_nrm, size_t n) {
@@ -383,13 +403,18 @@ bool write_ply_pos_nrm(const std::string &path, const float *pos_nrm, size_t n) 
 }  // namespace plade
 
 // ---- C ABI (include/plade_hip.h) ---------------------------------------------------------------------------------------------
-extern "C" int plade_ply_read(const char *path, float **pos_nrm, uint64_t *n, char *err, size_t err_cap) {
+namespace {
+int ply_read_c(const char *path, float **pos_nrm, uint64_t *n, int32_t *has_normals, char *err, size_t err_cap) {
     if (err && err_cap) err[0] = 0;
     if (!path || !pos_nrm || !n) return PLADE_EINVAL;
     *pos_nrm = nullptr; *n = 0;
     std::vector<float> buf;
     std::string msg;
-    if (!plade::read_ply_pos_nrm(path, buf, msg, nullptr, nullptr)) {
+    bool nrm = true;
+    const bool ok = has_normals ? plade::read_ply_points(path, buf, nrm, msg, nullptr, nullptr)
+                                : plade::read_ply_pos_nrm(path, buf, msg, nullptr, nullptr);
+    if (has_normals) *has_normals = ok && nrm ? 1 : 0;
+    if (!ok) {
         if (err && err_cap) { strncpy(err, msg.c_str(), err_cap - 1); err[err_cap - 1] = 0; }
         return PLADE_EINVAL;
     }
@@ -398,5 +423,14 @@ extern "C" int plade_ply_read(const char *path, float **pos_nrm, uint64_t *n, ch
     memcpy(o, buf.data(), buf.size() * sizeof(float));
     *pos_nrm = o; *n = buf.size() / 6;
     return PLADE_OK;
+}
+}  // namespace
+
+extern "C" int plade_ply_read(const char *path, float **pos_nrm, uint64_t *n, char *err, size_t err_cap) {
+    return ply_read_c(path, pos_nrm, n, nullptr, err, err_cap);
+}
+extern "C" int plade_ply_read_points(const char *path, float **pos_nrm, uint64_t *n, int32_t *has_normals, char *err, size_t err_cap) {
+    if (!has_normals) return PLADE_EINVAL;
+    return ply_read_c(path, pos_nrm, n, has_normals, err, err_cap);
 }
 extern "C" void plade_ply_free(float *pos_nrm) { free(pos_nrm); }

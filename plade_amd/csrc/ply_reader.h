@@ -19,6 +19,12 @@ namespace plade {
 bool read_ply_pos_nrm(const std::string &path, std::vector<float> &pos_nrm, std::string &err,
                       std::vector<std::string> *warnings = nullptr, const std::function<void()> *before_grow = nullptr);
 
+// read_ply_pos_nrm that also accepts a vertex element with x y z but without nx ny nz: has_normals = false and NaN in the
+// normal columns (the CLI estimates them under PLADE_ESTIMATE_NORMALS; C ABI: plade_ply_read_points).  Every other failure,
+// and its message, is read_ply_pos_nrm's.
+bool read_ply_points(const std::string &path, std::vector<float> &pos_nrm, bool &has_normals, std::string &err,
+                     std::vector<std::string> *warnings = nullptr, const std::function<void()> *before_grow = nullptr);
+
 bool write_ply_pos_nrm(const std::string &path, const float *pos_nrm, size_t n);
 
 }  // namespace plade

@@ -335,6 +335,65 @@ int plade_estimate_normals(plade_ctx *ctx, const float *xyz, uint32_t n, uint32_
 int plade_cloud_upload_xyz(plade_ctx *ctx, const float *xyz, uint32_t n, uint32_t stride, int32_t k, const float *viewpoint,
                            plade_cloud **out);
 
+/* ---- fine alignment: point-to-plane ICP after the coarse registration (no reference counterpart: the reference returns the
+ * Umeyama fit of its matched descriptors and refines nothing) -------------------------------------------------------------
+ * Semantics (plade_amd/csrc/icp.h).  Target: n_t points x y z nx ny nz; source: its x y z (normals ignored);
+ * T_in: source -> target, row-major 4 x 4 like plade_registration's T16.  D = the diagonal of the target's bounding box; a
+ * parameter that is 0 takes the automatic value in brackets.
+ *   sample       S = plade_voxel_downsample of the source's x y z with leaf source_leaf [0.005 D]
+ *   iterate      T_k in fp64, T_0 = T_in; the stage distance d starts at max_dist [0.025 D]
+ *   match        p' = fp32(R) s + fp32(t), each row ((r0 x + r1 y) + r2 z) + t in fp32; j = the argmin over ALL target points
+ *                of (fp32 FLANN L2 (p', q_j), j); s has a correspondence when that distance < (float)d * (float)d and n_j is
+ *                finite.  An exact set: independent of grid cell sizes and launch shapes.
+ *   linearise    fp64 over the correspondences, p = T_k double(s): r = n . (p - q), J = [p x n, n]; the 21 values of J^T J, the 6 of
+ *                J^T r, sum r^2 and the count, summed in a fixed order (bit-identical from run to run)
+ *   solve        J^T J x = -J^T r by fp64 Cholesky; a pivot <= 1e-12 max(diag) is a degenerate geometry
+ *   update       T_{k+1} = [Rodrigues(x0..2) | x3..5] T_k
+ *   schedule     a stage converges when |x0..2| < eps_rotation [1e-6 rad] and |x3..5| < eps_translation [1e-6 D]; then
+ *                d = max(min_dist, d / 2) while d > min_dist [0.0025 D], else stop with converged = 1; at most max_iterations
+ *                [60] updates in all (then converged = 0, still PLADE_OK, T_out = the last iterate)
+ *   failure      PLADE_EFAIL and T_out = T_in when an iteration has fewer than min_correspondences [100] correspondences
+ *                (failure = PLADE_ICP_TOO_FEW) or a degenerate system (PLADE_ICP_DEGENERATE, e.g. a single plane)
+ *   output       T_out: fp32 of the fp64 iterate; the result's correspondences, rmse = sqrt(sum r^2 / count) and fitness =
+ *                count / |S| are those of the last linearisation
+ * Errors: PLADE_EINVAL for NULL pointers, n = 0, non-finite coordinates or T_in, negative or non-finite parameters, min_dist >
+ * max_dist, more than 16 stages (max_dist / min_dist > 2^15); the context stays usable.  plade_stats_get then reports
+ * icp_sample_s, icp_grid_s (one target grid per stage), icp_loop_s and icp_iterations (HIP events on the context's stream).  The
+ * loop queues max_iterations pairs of kernels without a host wait between them and reads T and the result back once. */
+#define PLADE_ICP_TOO_FEW 1
+#define PLADE_ICP_DEGENERATE 2
+typedef struct plade_icp_params {
+    double source_leaf;          /* 0: 0.005 D */
+    double max_dist;             /* 0: 0.025 D */
+    double min_dist;             /* 0: 0.0025 D (capped at max_dist when max_dist is given and min_dist is not) */
+    double eps_rotation;         /* radians, 0: 1e-6 */
+    double eps_translation;      /* 0: 1e-6 D */
+    int32_t max_iterations;      /* 0: 60 */
+    int32_t min_correspondences; /* 0: 100 */
+} plade_icp_params;
+typedef struct plade_icp_result {
+    int32_t iterations;          /* updates applied */
+    int32_t stages;              /* stage distances used (1 + the index of the last) */
+    int32_t converged;           /* 1: the stage at min_dist converged */
+    int32_t failure;             /* 0, PLADE_ICP_TOO_FEW or PLADE_ICP_DEGENERATE */
+    uint32_t correspondences;    /* of the last linearisation */
+    uint32_t samples;            /* |S| */
+    double rmse, fitness;        /* of the last linearisation */
+    double final_dist;           /* the stage distance d of the last linearisation */
+} plade_icp_result;
+/* The defaults: 0 for the scale-dependent values (automatic), eps_rotation = 1e-6, max_iterations = 60, min_correspondences = 100. */
+void plade_icp_default_params(plade_icp_params *p);
+/* params NULL: the defaults.  T_out16 may be T_in16. */
+int plade_refine_icp(plade_ctx *ctx, const float *tgt_pos_nrm, uint32_t n_t, const float *src_pos_nrm, uint32_t n_s,
+                     const float *T_in16, const plade_icp_params *params, float *T_out16, plade_icp_result *result);
+/* The same on resident clouds (plade_cloud_upload, plade_cloud_upload_xyz): bit-identical results. */
+int plade_refine_icp_dev(plade_ctx *ctx, plade_cloud *tgt, plade_cloud *src, const float *T_in16, const plade_icp_params *params,
+                         float *T_out16, plade_icp_result *result);
+/* Test seam: one match + linearise pass at stage distance `dist` on the given points (no sample): corr_out[i] = j or -1 (n_s
+ * int32, may be NULL); moments_out = J^T J (21 values, row-major upper triangle), J^T r (6), sum r^2, count. */
+int plade_icp_linearize(plade_ctx *ctx, const float *tgt_pos_nrm, uint32_t n_t, const float *src_xyz, uint32_t n_s, uint32_t stride,
+                        const double *T16, float dist, int32_t *corr_out, double *moments_out);
+
 /* ---- instrumentation ---------------------------------------------------------------------- */
 /* Named intermediates of the last registration (when params.dump != 0). Returns 0 if found;
  * the pointer stays valid until the next call on this ctx. */

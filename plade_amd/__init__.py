@@ -27,6 +27,7 @@ ABI_SYMBOLS = [
     "plade_device_count", "plade_comm_unique_id", "plade_comm_create", "plade_comm_all_gather", "plade_comm_destroy", "plade_comm_last_error",
     "plade_set_candidate_shard_comm",
     "plade_estimate_normals", "plade_cloud_upload_xyz", "plade_ply_read_points",
+    "plade_icp_default_params", "plade_refine_icp", "plade_refine_icp_dev", "plade_icp_linearize",
 ]
 
 
@@ -43,6 +44,22 @@ class Params(C.Structure):
                 ("ransac_topup", C.c_int32), ("match_window", C.c_int32), ("match_cell_budget", C.c_uint32),
                 ("group_max_points", C.c_uint32), ("prepare_sides", C.c_int32), ("closest_point_mode", C.c_int32)]
 
+
+class IcpParams(C.Structure):
+    """plade_icp_params: 0 = the automatic value (source_leaf 0.005 D, max_dist 0.025 D, min_dist 0.0025 D, eps_translation 1e-6 D;
+    D = the diagonal of the target's bounding box)."""
+    _fields_ = [("source_leaf", C.c_double), ("max_dist", C.c_double), ("min_dist", C.c_double), ("eps_rotation", C.c_double),
+                ("eps_translation", C.c_double), ("max_iterations", C.c_int32), ("min_correspondences", C.c_int32)]
+
+
+class IcpResult(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("stages", C.c_int32), ("converged", C.c_int32), ("failure", C.c_int32),
+                ("correspondences", C.c_uint32), ("samples", C.c_uint32), ("rmse", C.c_double), ("fitness", C.c_double),
+                ("final_dist", C.c_double)]
+
+
+PLADE_ICP_TOO_FEW, PLADE_ICP_DEGENERATE = 1, 2
+ICP_FAILURES = {0: None, PLADE_ICP_TOO_FEW: "too few correspondences", PLADE_ICP_DEGENERATE: "degenerate"}
 
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_int32), C.c_uint32, C.c_uint32, C.c_uint32)
 
@@ -102,6 +119,10 @@ def load_library(path=LIB_PATH):
                                            C.c_size_t])
     sig("plade_estimate_normals", argtypes=[p, p, u32, u32, i32, p, p, p, p])
     sig("plade_cloud_upload_xyz", argtypes=[p, p, u32, u32, i32, p, C.POINTER(p)])
+    sig("plade_icp_default_params", argtypes=[C.POINTER(IcpParams)], restype=None)
+    sig("plade_refine_icp", argtypes=[p, p, u32, p, u32, p, C.POINTER(IcpParams), p, C.POINTER(IcpResult)])
+    sig("plade_refine_icp_dev", argtypes=[p, p, p, p, C.POINTER(IcpParams), p, C.POINTER(IcpResult)])
+    sig("plade_icp_linearize", argtypes=[p, p, u32, p, u32, u32, p, f, p, p])
     sig("plade_sort_segments", argtypes=[p, p, p, p, u32, C.c_int, p, p])
     sig("plade_set_candidate_shard", argtypes=[p, u32, u32, u32, EXCHANGE_FN, p])
     sig("plade_registration_minsupport", argtypes=[p, p, u32, p, u32, i32, i32, p])
@@ -165,6 +186,30 @@ def default_params():
     prm = Params()
     load_library().plade_default_params(C.byref(prm))
     return prm
+
+
+def icp_default_params():
+    """plade_icp_default_params (pure: needs no GPU) as a dict of the plade_icp_params fields."""
+    prm = IcpParams()
+    load_library().plade_icp_default_params(C.byref(prm))
+    return {k: getattr(prm, k) for k, _ in IcpParams._fields_}
+
+
+def _icp_params(kw):
+    prm = IcpParams()
+    load_library().plade_icp_default_params(C.byref(prm))
+    for k, v in kw.items():
+        if k not in dict(IcpParams._fields_):
+            raise TypeError(f"unknown ICP parameter {k!r}")
+        setattr(prm, k, v)
+    return prm
+
+
+def _icp_info(res):
+    info = {k: getattr(res, k) for k, _ in IcpResult._fields_}
+    info["converged"] = bool(info["converged"])
+    info["reason"] = ICP_FAILURES.get(info["failure"], "unknown")
+    return info
 
 
 def read_ply(path):
@@ -607,6 +652,48 @@ class Context:
         h = C.c_void_p()
         self._check(self.L.plade_cloud_upload_xyz(self.h, _ptr(a), n, stride, int(k), _ptr(v), C.byref(h)))
         return Cloud(self, None, handle=(n, h))
+
+    # ---- fine alignment ----------------------------------------------------------------------
+    def _refine(self, call, T, icp_params):
+        T_in = _f32(T).reshape(4, 4).copy()
+        prm = _icp_params(icp_params)
+        T_out = np.zeros((4, 4), np.float32)
+        res = IcpResult()
+        rc = call(T_in, prm, T_out, res)
+        info = _icp_info(res)
+        if rc != 0:
+            err = PladeError(rc, self.L.plade_last_error(self.h).decode(errors="replace"))
+            err.info, err.T = info, T_out
+            raise err
+        return T_out, info
+
+    def refine_icp(self, tgt, src, T, **icp_params):
+        """plade_refine_icp: point-to-plane ICP of the (N, 6) source onto the (M, 6) target from the 4 x 4 source -> target T.
+        Returns (T_out, info), info = the plade_icp_result fields as a dict plus `reason` (None, "too few correspondences",
+        "degenerate").  A failed refinement raises PladeError (code PLADE_EFAIL, with .info and .T = T_in)."""
+        tgt, src = _f32(tgt), _f32(src)
+        self._check_cloud(tgt, "refine_icp"); self._check_cloud(src, "refine_icp")
+        return self._refine(lambda T_in, prm, T_out, res: self.L.plade_refine_icp(
+            self.h, _ptr(tgt), len(tgt), _ptr(src), len(src), _ptr(T_in), C.byref(prm), _ptr(T_out), C.byref(res)), T, icp_params)
+
+    def refine_icp_dev(self, tgt_cloud, src_cloud, T, **icp_params):
+        """plade_refine_icp_dev: refine_icp on resident clouds (upload, upload_xyz); bit-identical to refine_icp."""
+        return self._refine(lambda T_in, prm, T_out, res: self.L.plade_refine_icp_dev(
+            self.h, tgt_cloud.h, src_cloud.h, _ptr(T_in), C.byref(prm), _ptr(T_out), C.byref(res)), T, icp_params)
+
+    def icp_linearize(self, tgt, src_xyz, T, dist):
+        """plade_icp_linearize (test seam): one match + linearise pass of the ICP at stage distance `dist` with the fp64 4 x 4 T on
+        every point of src_xyz (no sample).  Returns (corr, moments): corr (N,) int32 = the target index or -1, moments (29,)
+        float64 = J^T J (upper triangle, row-major), J^T r, sum r^2, count."""
+        tgt = _f32(tgt)
+        self._check_cloud(tgt, "icp_linearize")
+        a, n, stride = _xyz_view(src_xyz)
+        T64 = np.ascontiguousarray(T, dtype=np.float64).reshape(4, 4)
+        corr = np.empty(n, np.int32)
+        mom = np.zeros(29, np.float64)
+        self._check(self.L.plade_icp_linearize(self.h, _ptr(tgt), len(tgt), _ptr(a), n, stride, _ptr(T64), float(dist), _ptr(corr),
+                                               _ptr(mom)))
+        return corr, mom
 
     def pin(self, arr):
         """Page-lock a C-contiguous float32 array the caller keeps alive (plade_host_pin); registration() calls that are

@@ -1,6 +1,7 @@
 // plade_amd/csrc/api.hip -- context management and instrumentation entry points of the C ABI.
 #include "ctx.h"
 #include "exact_sort.h"
+#include "icp.h"
 #include "normals.h"
 #include "pipeline.h"
 #include "ransac.h"
@@ -133,6 +134,7 @@ extern "C" void plade_ctx_destroy(plade_ctx *ctx) {
     if (ctx->reg_work) plade::registration_work_destroy(ctx->reg_work);
     if (ctx->ransac_work) plade::ransac_work_destroy(ctx->ransac_work);
     if (ctx->normals_work) plade::normals_work_destroy(ctx->normals_work);
+    if (ctx->icp_work) plade::icp_work_destroy(ctx->icp_work);
     (void)hipStreamDestroy(ctx->stream);
     if (ctx->pf.stream) { (void)hipStreamSynchronize(ctx->pf.stream); (void)hipStreamDestroy(ctx->pf.stream); }
     delete ctx;

@@ -49,6 +49,15 @@ bool registration(Eigen::Matrix<float, 4, 4> &transformation,
                   int ransac_min_support_target,
                   int ransac_min_support_source);
 
+/** Fine alignment (no counterpart in the reference): refines `transformation` (source -> target, e.g. the result of one of the
+ *  registration() overloads above) by point-to-plane ICP on the GPU (plade_refine_icp, default parameters; the target needs
+ *  normals, the source's are ignored).  Prints one line on success.  false: the refinement failed (too few correspondences, a
+ *  degenerate geometry, no GPU) and `transformation` is unchanged; a warning is printed.  The CLI and the file / cloud overloads
+ *  of registration(T, target, source) call it for every registered pair when PLADE_REFINE_ICP=1. */
+bool refine_registration(Eigen::Matrix<float, 4, 4> &transformation,
+                         pcl::PointCloud<pcl::PointNormal>::Ptr target_cloud,
+                         pcl::PointCloud<pcl::PointNormal>::Ptr source_cloud);
+
 /** Batch extension (no counterpart in the reference, whose batch mode is a plain loop of the file overload above,
  *  code/PLADE/main.cpp:122-148): `count` (1..registration_group_max = PLADE_GROUP_MAX) consecutive pairs of the list as ONE group.  Every pair gets the result,
  *  the messages and the identity-on-failure of the file overload -- its transformation is bit for bit the one the file overload

@@ -7,6 +7,7 @@
 
 #include <chrono>
 #include <cstdio>
+#include <cstring>
 #include <cstdlib>
 #include <iostream>
 #include <mutex>
@@ -129,6 +130,33 @@ bool read_ply_cloud(const std::string &file_name, std::vector<float> &buf, std::
 }
 // the normal columns of an x y z nx ny nz array, estimated in place on the calling thread's context
 bool estimate_in_place(const std::string &file_name, std::vector<float> &buf);
+
+// PLADE_REFINE_ICP=1 (opt-in, 0 / unset = off): every pair that registered is refined by point-to-plane ICP on the GPU
+// (plade_refine_icp with the default parameters, on the calling thread's context) before its transformation is returned; one
+// console line per refined pair.  A refinement that fails keeps PLADE's transformation and prints a warning.  Unset, nothing
+// changes.
+bool refine_icp_on() {
+    static const bool on = [] { const char *w = getenv("PLADE_REFINE_ICP"); return w && atoi(w) != 0; }();
+    return on;
+}
+// T16 (source -> target of the packed arrays) refined in place; false (T16 unchanged, a warning printed) when the refinement fails
+bool refine_packed(plade_ctx *ctx, float *T16, const float *tg, size_t n_t, const float *sr, size_t n_s) {
+    plade_icp_result res;
+    float out[16];
+    trace("icp: refining");
+    const int rc = plade_refine_icp(ctx, tg, (uint32_t)n_t, sr, (uint32_t)n_s, T16, nullptr, out, &res);
+    trace("icp: done");
+    if (rc != PLADE_OK) {
+        con_err() << "warning: ICP refinement failed (" << plade_last_error(ctx) << "); PLADE's transformation is kept" << std::endl;
+        return false;
+    }
+    memcpy(T16, out, sizeof(out));
+    char b[200];
+    snprintf(b, sizeof(b), "ICP refinement: %d iterations, %s, rmse %.6g, fitness %.4f", res.iterations,
+             res.converged ? "converged" : "not converged", res.rmse, res.fitness);
+    con_out() << b << std::endl;
+    return true;
+}
 
 std::string extension(const std::string &file_name) {  // util.cpp:525-531
     std::string::size_type dot = file_name.find_last_of('.');
@@ -258,8 +286,9 @@ bool register_packed(Eigen::Matrix<float, 4, 4> &transformation, const float *tg
         con_err() << plade_last_error(ctx) << std::endl;
         return false;
     }
-    to_matrix(T16, transformation);
     con_out() << "done. time: " << w.str() << std::endl;
+    if (refine_icp_on()) refine_packed(ctx, T16, tg, n_t, sr, n_s);
+    to_matrix(T16, transformation);
     return true;
 }
 
@@ -418,12 +447,26 @@ void registration_group(size_t count, Eigen::Matrix<float, 4, 4> *transformation
             con_err() << "registration failed" << std::endl;
             continue;
         }
-        to_matrix(T16 + 16 * q, transformations[it.pair]);
         con_out() << "done. time: " << w.str() << std::endl;
+        if (refine_icp_on()) refine_packed(ctx, T16 + 16 * q, it.tg, it.n_t, it.sr, it.n_s);
+        to_matrix(T16 + 16 * q, transformations[it.pair]);
         if (it.switched) transformations[it.pair] = transformations[it.pair].inverse();
         ok[it.pair] = true;
     }
     plade_set_thread_console(nullptr, nullptr);
+}
+
+// fine alignment after registration(): see plade.h
+bool refine_registration(Eigen::Matrix<float, 4, 4> &transformation, pcl::PointCloud<pcl::PointNormal>::Ptr target_cloud,
+                         pcl::PointCloud<pcl::PointNormal>::Ptr source_cloud) {
+    plade_ctx *ctx = context();
+    if (!ctx) return false;
+    std::vector<float> tg = flatten(*target_cloud), sr = flatten(*source_cloud);
+    float T16[16];
+    for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) T16[4 * r + c] = transformation(r, c);
+    if (!refine_packed(ctx, T16, tg.data(), target_cloud->size(), sr.data(), source_cloud->size())) return false;
+    to_matrix(T16, transformation);
+    return true;
 }
 
 bool load_ply_cloud(const std::string &file_name, pcl::PointCloud<pcl::PointNormal> &cloud) {

@@ -394,6 +394,37 @@ int plade_refine_icp_dev(plade_ctx *ctx, plade_cloud *tgt, plade_cloud *src, con
 int plade_icp_linearize(plade_ctx *ctx, const float *tgt_pos_nrm, uint32_t n_t, const float *src_xyz, uint32_t n_s, uint32_t stride,
                         const double *T16, float dist, int32_t *corr_out, double *moments_out);
 
+/* ---- cloud-to-cloud distances and registration quality (no reference counterpart) ------------------------------------------
+ * Semantics (plade_amd/csrc/distances.h).  Target: n_t points x y z nx ny nz (the normals may be NaN, as
+ * plade_ply_read_points gives for xyz-only files); source: n_s points x y z, `stride` floats apart; T16: the row-major 4 x 4
+ * source -> target transform in fp32 (NULL: the identity); d = max_dist (fp32, finite, > 0).
+ *   transform    p'_i = fp32(R) s_i + fp32(t), each row ((r0 x + r1 y) + r2 z) + t in fp32 (the ICP's match rule)
+ *   nearest      j_i = the argmin over ALL target points of (fp32 FLANN L2 (p'_i, q_j), j): ties go to the smaller index
+ *   corresp.     i has one when that distance < (float)d * (float)d; an exact set, independent of cell sizes, source order and
+ *                launch shapes
+ *   per point    each array may be NULL.  idx_out[i] = j_i or -1; d2_out[i] = the fp32 distance or +inf without a
+ *                correspondence; plane_out[i] = fp32 of r_i = (n0 (p0 - q0) + n1 (p1 - q1)) + n2 (p2 - q2), p = double(T) double(s_i)
+ *                in fp64 with the same row order, NaN without a correspondence or when n_j is not finite
+ *   summary      n = n_s, count, fitness = count / n, rmse = sqrt(sum d2 / count), mean = sum sqrt(d2) / count, max = max sqrt(d2),
+ *                plane_count = the correspondences with a finite n_j, plane_rmse = sqrt(sum r^2 / plane_count).  The sums are fp64
+ *                over double(d2) and r, in a fixed order of the original index (no fp64 atomics): bit-identical from run to run,
+ *                with or without per-point outputs, for host or resident clouds.  count = 0 (still PLADE_OK): rmse, mean and max
+ *                are NaN and fitness is 0; plane_count = 0: plane_rmse is NaN.
+ * Errors: PLADE_EINVAL for NULL clouds or summary, n = 0, non-finite coordinates or T, d <= 0 or not finite, stride < 3; the
+ * context stays usable.  plade_stats_get then reports distances_grid_s, distances_sort_s, distances_search_s (lane and ring
+ * passes), distances_lane_s, distances_ring_s, distances_summary_s (HIP events on the context's stream) and distances_ring_queries
+ * (probes the first pass could not finish). */
+typedef struct plade_distance_summary {
+    uint64_t n, count, plane_count;
+    double fitness, rmse, mean, max, plane_rmse;
+} plade_distance_summary;
+int plade_cloud_distances(plade_ctx *ctx, const float *tgt_pos_nrm, uint32_t n_t, const float *src_xyz, uint32_t n_s,
+                          uint32_t stride, const float *T16, float max_dist, int32_t *idx_out, float *d2_out,
+                          float *plane_out, plade_distance_summary *summary);
+/* The same on resident clouds (plade_cloud_upload / plade_cloud_upload_xyz; the source's x y z): bit-identical results. */
+int plade_cloud_distances_dev(plade_ctx *ctx, plade_cloud *tgt, plade_cloud *src, const float *T16, float max_dist,
+                              int32_t *idx_out, float *d2_out, float *plane_out, plade_distance_summary *summary);
+
 /* ---- instrumentation ---------------------------------------------------------------------- */
 /* Named intermediates of the last registration (when params.dump != 0). Returns 0 if found;
  * the pointer stays valid until the next call on this ctx. */

@@ -28,6 +28,7 @@ ABI_SYMBOLS = [
     "plade_set_candidate_shard_comm",
     "plade_estimate_normals", "plade_cloud_upload_xyz", "plade_ply_read_points",
     "plade_icp_default_params", "plade_refine_icp", "plade_refine_icp_dev", "plade_icp_linearize",
+    "plade_cloud_distances", "plade_cloud_distances_dev",
 ]
 
 
@@ -56,6 +57,13 @@ class IcpResult(C.Structure):
     _fields_ = [("iterations", C.c_int32), ("stages", C.c_int32), ("converged", C.c_int32), ("failure", C.c_int32),
                 ("correspondences", C.c_uint32), ("samples", C.c_uint32), ("rmse", C.c_double), ("fitness", C.c_double),
                 ("final_dist", C.c_double)]
+
+
+class DistanceSummary(C.Structure):
+    """plade_distance_summary: count, fitness = count / n, rmse, mean and max of the distances of the correspondences, and the
+    point-to-plane rmse over those with a finite target normal (NaN ratios when a count is 0)."""
+    _fields_ = [("n", C.c_uint64), ("count", C.c_uint64), ("plane_count", C.c_uint64), ("fitness", C.c_double), ("rmse", C.c_double),
+                ("mean", C.c_double), ("max", C.c_double), ("plane_rmse", C.c_double)]
 
 
 PLADE_ICP_TOO_FEW, PLADE_ICP_DEGENERATE = 1, 2
@@ -123,6 +131,8 @@ def load_library(path=LIB_PATH):
     sig("plade_refine_icp", argtypes=[p, p, u32, p, u32, p, C.POINTER(IcpParams), p, C.POINTER(IcpResult)])
     sig("plade_refine_icp_dev", argtypes=[p, p, p, p, C.POINTER(IcpParams), p, C.POINTER(IcpResult)])
     sig("plade_icp_linearize", argtypes=[p, p, u32, p, u32, u32, p, f, p, p])
+    sig("plade_cloud_distances", argtypes=[p, p, u32, p, u32, u32, p, f, p, p, p, C.POINTER(DistanceSummary)])
+    sig("plade_cloud_distances_dev", argtypes=[p, p, p, p, f, p, p, p, C.POINTER(DistanceSummary)])
     sig("plade_sort_segments", argtypes=[p, p, p, p, u32, C.c_int, p, p])
     sig("plade_set_candidate_shard", argtypes=[p, u32, u32, u32, EXCHANGE_FN, p])
     sig("plade_registration_minsupport", argtypes=[p, p, u32, p, u32, i32, i32, p])
@@ -694,6 +704,37 @@ class Context:
         self._check(self.L.plade_icp_linearize(self.h, _ptr(tgt), len(tgt), _ptr(a), n, stride, _ptr(T64), float(dist), _ptr(corr),
                                                _ptr(mom)))
         return corr, mom
+
+    # ---- cloud-to-cloud distances ------------------------------------------------------------
+    def _distances(self, call, n, max_dist, T, per_point):
+        T_in = None if T is None else _f32(T).reshape(4, 4).copy()
+        idx = np.empty(n, np.int32) if per_point else None
+        d2 = np.empty(n, np.float32) if per_point else None
+        plane = np.empty(n, np.float32) if per_point else None
+        summ = DistanceSummary()
+        self._check(call(_ptr(T_in), float(max_dist), _ptr(idx), _ptr(d2), _ptr(plane), C.byref(summ)))
+        return idx, d2, plane, {k: getattr(summ, k) for k, _ in DistanceSummary._fields_}
+
+    def cloud_distances(self, tgt, src, max_dist, T=None, per_point=True):
+        """plade_cloud_distances: the exact nearest (M, 6) target point of every point of src (N x 3, or the x y z columns of
+        wider rows) after the 4 x 4 source -> target T (None: the identity), bounded by max_dist.  Returns (idx, d2, plane,
+        summary): idx (N,) int32 (-1: nothing closer than max_dist), d2 (N,) float32 squared distances (+inf), plane (N,) float32
+        signed point-to-plane distances (NaN), all None when per_point is False, and the plade_distance_summary fields as a dict."""
+        tgt = _f32(tgt)
+        self._check_cloud(tgt, "cloud_distances")
+        a, n, stride = _xyz_view(src)
+        return self._distances(lambda T_in, d, i, d2, pl, summ: self.L.plade_cloud_distances(
+            self.h, _ptr(tgt), len(tgt), _ptr(a), n, stride, T_in, d, i, d2, pl, summ), n, max_dist, T, per_point)
+
+    def cloud_distances_dev(self, tgt_cloud, src_cloud, max_dist, T=None, per_point=True):
+        """plade_cloud_distances_dev: cloud_distances on resident clouds (upload, upload_xyz); bit-identical results."""
+        return self._distances(lambda T_in, d, i, d2, pl, summ: self.L.plade_cloud_distances_dev(
+            self.h, tgt_cloud.h, src_cloud.h, T_in, d, i, d2, pl, summ), src_cloud.n, max_dist, T, per_point)
+
+    def evaluate_registration(self, tgt, src, T, max_dist):
+        """Registration quality of T (source -> target) at max_dist: the summary dict of cloud_distances, with no per-point
+        outputs (fitness = the share of source points within max_dist of the target, rmse of their distances, ...)."""
+        return self.cloud_distances(tgt, src, max_dist, T=T, per_point=False)[3]
 
     def pin(self, arr):
         """Page-lock a C-contiguous float32 array the caller keeps alive (plade_host_pin); registration() calls that are

@@ -1,5 +1,6 @@
 // plade_amd/csrc/api.hip -- context management and instrumentation entry points of the C ABI.
 #include "ctx.h"
+#include "distances.h"
 #include "exact_sort.h"
 #include "icp.h"
 #include "normals.h"
@@ -135,6 +136,7 @@ extern "C" void plade_ctx_destroy(plade_ctx *ctx) {
     if (ctx->ransac_work) plade::ransac_work_destroy(ctx->ransac_work);
     if (ctx->normals_work) plade::normals_work_destroy(ctx->normals_work);
     if (ctx->icp_work) plade::icp_work_destroy(ctx->icp_work);
+    if (ctx->dist_work) plade::dist_work_destroy(ctx->dist_work);
     (void)hipStreamDestroy(ctx->stream);
     if (ctx->pf.stream) { (void)hipStreamSynchronize(ctx->pf.stream); (void)hipStreamDestroy(ctx->pf.stream); }
     delete ctx;

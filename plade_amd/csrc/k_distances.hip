@@ -1,0 +1,478 @@
+// plade_amd/csrc/k_distances.hip -- exact bounded nearest-neighbour distances of a source against a target on gfx950
+// (semantics: distances.h).
+//
+// Layout
+//   grid    one dense row index of TargetGrid (overlap.h) over the target.  The cell follows the target's density (about five
+//           points per occupied cell of a surface), or d plus a margin when d is smaller: then one 27-cell block holds every
+//           target point closer than d.  The cell never grows to a large d -- a d-sized cell would hand each probe thousands of
+//           candidates (the ICP's coarse stage).
+//   order   k_distances_keys forms p' and its padded cell id in that grid; the radix sort orders the probes by cell, so the 64
+//           lanes of a wavefront probe neighbouring cells and share their candidate runs.  Outputs go back by original index.
+//   lane    k_distances_lane: one lane per probe scans its 27-cell block for the (d2, j) argmin key.  The probe is finished when
+//           that key is closer than the block's outside, or the outside is at least d away (both less a margin for the fp32 cell
+//           assignment).  A probe at least d from the target's bounding box ends before any load of the grid.  The rest is
+//           appended to a compacted list (one atomic per wavefront).
+//   ring    k_distances_ring: one wavefront per listed probe grows the block as k_normals_ring does (radius + max(1, radius / 2)
+//           per step, each step reading only the runs the previous block did not hold); the 64 keys of a batch are reduced by a
+//           wave min.  It stops at the first block whose outside is at least min(best, d) away, or that covers the grid.
+//   summary k_distances_summary: one lane per original index forms the plane residual in fp64 and the six summary terms; a
+//           butterfly per wave, the waves in order, one partial per workgroup.  k_distances_final sums the partials with one
+//           wavefront in a fixed order (lane l: partials l, l + 64, ..., then a butterfly).  No fp64 atomics.
+#include "distances.h"
+#include "overlap.h"
+#include "prims.h"
+#include "voxel.h"
+
+namespace plade {
+
+namespace {
+
+typedef unsigned long long u64;
+constexpr u64 EMPTY = ~0ull;
+constexpr int KEY_TPB = 256, LANE_TPB = 256, SUM_TPB = 256, RING_WAVES = 4;
+constexpr int SUM_TERMS = 6;   // count, sum d2, sum sqrt(d2), max sqrt(d2), plane_count, sum r^2
+
+struct DistArgs {
+    const float4 *sorted;            // the target in cell order: x y z, bit-cast original index
+    const uint32_t *row_start;
+    float mnx, mny, mnz, inv;        // the grid's cell assignment (k_cell_ids)
+    int dx, dy, dz, DX, DY;          // cells, padded row pitch
+    double mn[3], cell, margin;
+    double bmn[3], bmx[3];           // the target's bounding box
+    float d2;                        // (float)d * (float)d
+    const float4 *probe;             // n probes in the original order: p', bit-cast original index
+    const uint32_t *order;           // the original indices in cell order
+    uint32_t n;
+    int32_t *idx;
+    float *dd;
+    uint32_t *fail, *fail_count;
+};
+
+__device__ __forceinline__ u64 make_key(float d, uint32_t j) { return ((u64)__float_as_uint(d) << 32) | (u64)j; }
+__device__ __forceinline__ float key_d(u64 key) { return __uint_as_float((uint32_t)(key >> 32)); }   // EMPTY: NaN
+
+__device__ __forceinline__ void cell_of(const DistArgs &a, f3 q, int &cx, int &cy, int &cz) {   // = k_cell_ids
+    cx = min(max((int)floorf((q.x - a.mnx) * a.inv), 0), a.dx - 1);
+    cy = min(max((int)floorf((q.y - a.mny) * a.inv), 0), a.dy - 1);
+    cz = min(max((int)floorf((q.z - a.mnz) * a.inv), 0), a.dz - 1);
+}
+
+// margin of one probe: the grid's (1 % of a cell, ulps of the target's coordinates) and a few ulps of the probe's own
+__device__ __forceinline__ double margin_of(const DistArgs &a, f3 q) {
+    return a.margin + 1e-6 * (double)fmaxf(fabsf(q.x), fmaxf(fabsf(q.y), fabsf(q.z)));
+}
+
+// distance from q to the outside of the block of cells [c - R, c + R]^3, less the margin (as k_normals' block_reach: no bound
+// where the block reaches the grid's edge, nothing lies beyond); +inf: the block covers the grid
+__device__ __forceinline__ double block_reach(const DistArgs &a, f3 q, int cx, int cy, int cz, int R, double mg) {
+    double b = INFINITY;
+    const double qv[3] = {q.x, q.y, q.z};
+    const int c[3] = {cx, cy, cz}, d[3] = {a.dx, a.dy, a.dz};
+#pragma unroll
+    for (int t = 0; t < 3; ++t) {
+        if (c[t] - R > 0) b = fmin(b, qv[t] - (a.mn[t] + (double)(c[t] - R) * a.cell));
+        if (c[t] + R < d[t] - 1) b = fmin(b, (a.mn[t] + (double)(c[t] + R + 1) * a.cell) - qv[t]);
+    }
+    return b == INFINITY ? b : b - mg;
+}
+// true: the best key so far is final -- it is closer than every point outside the block, or every point outside the block is
+// at least d away (then a correspondence can only come from inside it)
+__device__ __forceinline__ bool finished(const DistArgs &a, float best, double reach) {
+    if (reach == INFINITY) return true;
+    if (!(reach > 0.0)) return false;
+    const float R2 = (float)(reach * reach);
+    return best < R2 || a.d2 <= R2;      // (best NaN: no key yet)
+}
+
+__device__ __forceinline__ void store(const DistArgs &a, uint32_t orig, u64 best) {
+    const float bd = key_d(best);
+    const bool hit = best != EMPTY && bd < a.d2;
+    a.idx[orig] = hit ? (int32_t)(uint32_t)best : -1;
+    a.dd[orig] = hit ? bd : INFINITY;
+}
+
+// p' and its padded cell id in the target grid (k_cell_ids' formula, clamped: probes outside the grid sort to its edge)
+__global__ __launch_bounds__(KEY_TPB) void k_distances_keys(const float *__restrict__ src, uint32_t n, uint32_t stride, const float *__restrict__ Tf,
+                                                            DistArgs a, uint32_t *__restrict__ keys, uint32_t *__restrict__ vals,
+                                                            float4 *__restrict__ probe) {
+    const uint32_t i = blockIdx.x * KEY_TPB + threadIdx.x;
+    if (i >= n) return;
+    const float *s = src + (size_t)i * stride;
+    const float x = s[0], y = s[1], z = s[2];
+    const f3 q(((Tf[0] * x + Tf[1] * y) + Tf[2] * z) + Tf[3], ((Tf[4] * x + Tf[5] * y) + Tf[6] * z) + Tf[7],
+               ((Tf[8] * x + Tf[9] * y) + Tf[10] * z) + Tf[11]);
+    int cx, cy, cz;
+    cell_of(a, q, cx, cy, cz);
+    keys[i] = (uint32_t)(cx + 2) + (uint32_t)a.DX * ((uint32_t)(cy + 2) + (uint32_t)a.DY * (uint32_t)(cz + 2));
+    vals[i] = i;
+    probe[i] = make_float4(q.x, q.y, q.z, __uint_as_float(i));
+}
+
+__global__ __launch_bounds__(LANE_TPB) void k_distances_lane(const DistArgs a) {
+    const uint32_t s = blockIdx.x * LANE_TPB + threadIdx.x;
+    bool fail = false;
+    uint32_t orig = 0;
+    if (s < a.n) {
+        orig = a.order[s];
+        const float4 q4 = a.probe[orig];
+        const f3 q(q4.x, q4.y, q4.z);
+        const double mg = margin_of(a, q);
+        // gap to the target's bounding box: a probe at least d away has no correspondence and loads nothing of the grid
+        double g2 = 0.0;
+        const double qv[3] = {q.x, q.y, q.z};
+#pragma unroll
+        for (int t = 0; t < 3; ++t) {
+            const double g = fmax(fmax(a.bmn[t] - qv[t], qv[t] - a.bmx[t]), 0.0);
+            g2 += g * g;
+        }
+        const double gap = sqrt(g2) - mg;
+        u64 best = EMPTY;
+        if (!(gap > 0.0 && a.d2 <= (float)(gap * gap))) {
+            int cx, cy, cz;
+            cell_of(a, q, cx, cy, cz);
+            // nine runs of three cells; the padding of the row index makes every row of the block valid
+            for (int dz = -1; dz <= 1; ++dz)
+                for (int dy = -1; dy <= 1; ++dy) {
+                    const uint32_t r = (uint32_t)(cx + 1) + (uint32_t)a.DX * ((uint32_t)(cy + dy + 2) + (uint32_t)a.DY * (uint32_t)(cz + dz + 2));
+                    const uint32_t j1 = a.row_start[r + 3];
+                    for (uint32_t j = a.row_start[r]; j < j1; ++j) {
+                        const float4 p = a.sorted[j];
+                        const u64 key = make_key(flann_d2(q, f3(p.x, p.y, p.z)), __float_as_uint(p.w));
+                        best = key < best ? key : best;
+                    }
+                }
+            fail = !finished(a, key_d(best), block_reach(a, q, cx, cy, cz, 1, mg));
+        }
+        if (!fail) store(a, orig, best);
+    }
+    // wave-aggregated append to the list of the ring pass
+    const u64 mask = __ballot(fail);
+    if (mask) {
+        const uint32_t lane = threadIdx.x & 63u, leader = (uint32_t)__ffsll((long long)mask) - 1u;
+        uint32_t base = 0;
+        if (lane == leader) base = atomicAdd(a.fail_count, (uint32_t)__popcll(mask));
+        base = __shfl(base, (int)leader, 64);
+        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+        if (fail) a.fail[base + rank] = orig;
+    }
+}
+
+__device__ __forceinline__ u64 wave_min(u64 v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        const u64 w = __shfl_xor(v, o, 64);
+        v = w < v ? w : v;
+    }
+    return v;
+}
+
+// One wavefront per probe of the list (persistent workgroups; the list's length stays on the device).  The block [c - rout,
+// c + rout]^3 grows by half its radius per step; a step reads whole x runs of the rows outside the old block's y-z square and the
+// two x runs left and right of it in the rows inside (one or two row look-ups per row: O(R^2) per step, not the O(R^3) of cells).
+// The candidates of all lanes' runs are handed out 64 at a time (a wave prefix sum over the run lengths, each lane finding its
+// run by a binary search over the lanes) and reduced by a wave min of (d2, j) keys.
+__global__ __launch_bounds__(64 * RING_WAVES) void k_distances_ring(const DistArgs a) {
+    const int lane = (int)(threadIdx.x & 63u), wv = (int)(threadIdx.x >> 6);
+    const uint32_t total = *a.fail_count, stride_w = gridDim.x * RING_WAVES;
+    for (uint32_t i = blockIdx.x * RING_WAVES + (uint32_t)wv; i < total; i += stride_w) {
+        const uint32_t orig = a.fail[i];
+        const float4 q4 = a.probe[orig];
+        const f3 q(q4.x, q4.y, q4.z);
+        const double mg = margin_of(a, q);
+        int cx, cy, cz;
+        cell_of(a, q, cx, cy, cz);
+        u64 best = EMPTY;
+        for (int rin = -1, rout = 1;; rin = rout, rout += max(1, rout / 2)) {
+            const int y0 = max(cy - rout, 0), y1 = min(cy + rout, a.dy - 1), z0 = max(cz - rout, 0), z1 = min(cz + rout, a.dz - 1);
+            const int ny = y1 - y0 + 1, rows = ny * (z1 - z0 + 1);
+            const int xo0 = max(cx - rout, 0), xo1 = min(cx + rout, a.dx - 1);   // x range of the new block
+            for (int t0 = 0; t0 < rows; t0 += 64) {                              // (wave-uniform)
+                const int t = t0 + lane;
+                uint32_t a0 = 0, la = 0, b0 = 0, lb = 0;                         // up to two runs of this lane's row
+                if (t < rows) {
+                    const int y = y0 + t % ny, z = z0 + t / ny;
+                    const uint32_t row = (uint32_t)a.DX * ((uint32_t)(y + 2) + (uint32_t)a.DY * (uint32_t)(z + 2)) + 2u;
+                    if (abs(y - cy) > rin || abs(z - cz) > rin) {                // outside the old block's y-z square: the whole run
+                        a0 = a.row_start[row + (uint32_t)xo0];
+                        la = a.row_start[row + (uint32_t)xo1 + 1u] - a0;
+                    } else {                                                     // inside: left and right of the old block
+                        if (cx - rin - 1 >= xo0) {
+                            a0 = a.row_start[row + (uint32_t)xo0];
+                            la = a.row_start[row + (uint32_t)(cx - rin)] - a0;
+                        }
+                        if (cx + rin + 1 <= xo1) {
+                            b0 = a.row_start[row + (uint32_t)(cx + rin + 1)];
+                            lb = a.row_start[row + (uint32_t)xo1 + 1u] - b0;
+                        }
+                    }
+                }
+                const uint32_t len = la + lb;
+                uint32_t incl = len;
+#pragma unroll
+                for (int d = 1; d < 64; d <<= 1) { const uint32_t o = __shfl_up(incl, d, 64); if (lane >= d) incl += o; }
+                const uint32_t pre = incl - len, cand_total = __shfl(incl, 63, 64);
+                for (uint32_t c0 = 0; c0 < cand_total; c0 += 64) {               // (wave-uniform)
+                    const uint32_t idx = c0 + (uint32_t)lane;
+                    int o = 0;                                                   // the last lane whose run starts at or before idx
+#pragma unroll
+                    for (int st = 32; st >= 1; st >>= 1) if (__shfl(pre, o + st, 64) <= idx) o += st;
+                    const uint32_t off = idx - __shfl(pre, o, 64), la_o = __shfl(la, o, 64);
+                    const uint32_t a0_o = __shfl(a0, o, 64), b0_o = __shfl(b0, o, 64);
+                    u64 key = EMPTY;
+                    if (idx < cand_total) {
+                        const float4 p = a.sorted[off < la_o ? a0_o + off : b0_o + (off - la_o)];
+                        key = make_key(flann_d2(q, f3(p.x, p.y, p.z)), __float_as_uint(p.w));
+                    }
+                    const u64 m = wave_min(key);
+                    best = m < best ? m : best;
+                }
+            }
+            if (finished(a, key_d(best), block_reach(a, q, cx, cy, cz, rout, mg))) break;
+        }
+        if (lane == 0) store(a, orig, best);
+    }
+}
+
+struct SumArgs {
+    const int32_t *idx;
+    const float *dd;
+    const float *tgt;                // n_t x 6: the normals are gathered by j
+    const float *src;                // `stride` floats per point
+    uint32_t stride, n;
+    double T[12];                    // double(T16), rows 0..2
+    float *plane;                    // n or nullptr
+    double *partial;                 // gridDim.x x SUM_TERMS
+};
+
+__global__ __launch_bounds__(SUM_TPB) void k_distances_summary(const SumArgs a) {
+    __shared__ double s_red[SUM_TPB / 64][SUM_TERMS];
+    const uint32_t i = blockIdx.x * SUM_TPB + threadIdx.x;
+    double m[SUM_TERMS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (i < a.n) {
+        const int32_t j = a.idx[i];
+        double r = NAN;
+        if (j >= 0) {
+            const double d2 = (double)a.dd[i], dist = sqrt(d2);
+            m[0] = 1.0; m[1] = d2; m[2] = dist; m[3] = dist;
+            const float *t = a.tgt + (size_t)j * 6;
+            const double n0 = t[3], n1 = t[4], n2 = t[5];
+            if (isfinite(n0) && isfinite(n1) && isfinite(n2)) {
+                const float *s = a.src + (size_t)i * a.stride;
+                const double X = s[0], Y = s[1], Z = s[2];
+                const double *T = a.T;
+                const double p0 = ((T[0] * X + T[1] * Y) + T[2] * Z) + T[3];
+                const double p1 = ((T[4] * X + T[5] * Y) + T[6] * Z) + T[7];
+                const double p2 = ((T[8] * X + T[9] * Y) + T[10] * Z) + T[11];
+                r = (n0 * (p0 - (double)t[0]) + n1 * (p1 - (double)t[1])) + n2 * (p2 - (double)t[2]);
+                m[4] = 1.0; m[5] = r * r;
+            }
+        }
+        if (a.plane) a.plane[i] = (float)r;
+    }
+    // fixed-order reduction: butterfly across the wave (lane 0's value), then the waves in order
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < SUM_TERMS; ++k) {
+        double v = m[k];
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) { const double w = __shfl_xor(v, o, 64); v = k == 3 ? fmax(v, w) : v + w; }
+        if (lane == 0) s_red[wave][k] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < SUM_TERMS) {
+        const int k = threadIdx.x;
+        double v = s_red[0][k];
+#pragma unroll
+        for (int w = 1; w < SUM_TPB / 64; ++w) v = k == 3 ? fmax(v, s_red[w][k]) : v + s_red[w][k];
+        a.partial[(size_t)blockIdx.x * SUM_TERMS + k] = v;
+    }
+}
+
+__global__ __launch_bounds__(64) void k_distances_final(const double *__restrict__ partial, uint32_t blocks, double *__restrict__ out) {
+    const int lane = threadIdx.x;
+    double m[SUM_TERMS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (uint32_t b = (uint32_t)lane; b < blocks; b += 64) {
+        const double *p = partial + (size_t)b * SUM_TERMS;
+#pragma unroll
+        for (int k = 0; k < SUM_TERMS; ++k) m[k] = k == 3 ? fmax(m[k], p[k]) : m[k] + p[k];
+    }
+#pragma unroll
+    for (int k = 0; k < SUM_TERMS; ++k)
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) { const double w = __shfl_xor(m[k], o, 64); m[k] = k == 3 ? fmax(m[k], w) : m[k] + w; }
+    if (lane == 0)
+#pragma unroll
+        for (int k = 0; k < SUM_TERMS; ++k) out[k] = m[k];
+}
+
+}  // namespace
+
+struct DistWork {
+    TargetGrid grid;
+    DBuf<float> in_t, in_s, Tf;      // the host-pointer entry points' device copies (grow-only); the fp32 transform
+    DBuf<uint32_t> keys, keys2, vals, vals2, fail, count;
+    DBuf<float4> probe;
+    DBuf<int32_t> idx;
+    DBuf<float> dd, plane;
+    DBuf<double> partial, out;
+    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    float h_T[16];                   // the upload's source (kept until the call's sync)
+    double h_out[SUM_TERMS];
+    uint32_t h_count = 0;
+    ~DistWork() { for (hipEvent_t &e : ev) if (e) (void)hipEventDestroy(e); }
+};
+DistWork *dist_work_create() { return new DistWork; }
+void dist_work_destroy(DistWork *w) { delete w; }
+
+namespace {
+
+const float kIdentity[16] = {1.f, 0.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 0.f, 1.f};
+
+void check_args(const float *T16, float max_dist) {
+    for (int k = 0; k < 16; ++k) PLADE_REQUIRE(std::isfinite(T16[k]), PLADE_EINVAL, "cloud_distances: T must be finite");
+    PLADE_REQUIRE(std::isfinite(max_dist) && max_dist > 0.f, PLADE_EINVAL, "cloud_distances: max_dist must be finite and > 0");
+}
+
+// the distances on device clouds: target n_t x 6, source `stride` floats per point, the target's bounding box known
+void distances_dev(plade_ctx *ctx, DistWork &W, const float *d_tgt, uint32_t n_t, const float tmn[3], const float tmx[3],
+                   const float *d_src, uint32_t n_s, uint32_t stride, const float *T16, float max_dist, int32_t *idx_out,
+                   float *d2_out, float *plane_out, plade_distance_summary *summary) {
+    for (hipEvent_t &e : W.ev) if (!e) HIP_TRY(hipEventCreate(&e));
+    HIP_TRY(hipEventRecord(W.ev[0], ctx->stream));
+    // cell: ~5 points per occupied cell of a surface spread over the faces of the target's box (k_normals' estimate at k = 8); a
+    // d of less than that takes d plus a margin (3 % and ulps of the coordinates), so one 27-cell block holds every point within d
+    const double ex = std::max(1e-9, (double)tmx[0] - tmn[0]), ey = std::max(1e-9, (double)tmx[1] - tmn[1]),
+                 ez = std::max(1e-9, (double)tmx[2] - tmn[2]);
+    const double area = 2 * (ex * ey + ey * ez + ex * ez);
+    double amax = 0.0;
+    for (int t = 0; t < 3; ++t) amax = std::max(amax, std::max(std::fabs((double)tmn[t]), std::fabs((double)tmx[t])));
+    const double dense_cell = 1.5 * std::sqrt(8.0 * area / (M_PI * (double)n_t)), d_cell = 1.03 * (double)max_dist + 4e-6 * amax;
+    TargetGrid &G = W.grid;
+    G.build(ctx, d_tgt, n_t, 6, (float)std::min(dense_cell, d_cell), tmn, tmx, true);
+    PLADE_REQUIRE(G.dense, PLADE_EINVAL, "cloud_distances: needs the dense row index (unset PLADE_OVERLAP_INDEX_COMPACT)");
+    HIP_TRY(hipEventRecord(W.ev[1], ctx->stream));
+
+    DistArgs a;
+    memset(&a, 0, sizeof(a));
+    a.sorted = G.sorted.p; a.row_start = G.row_start.p;
+    a.mnx = G.gp.mnx; a.mny = G.gp.mny; a.mnz = G.gp.mnz; a.inv = G.gp.inv;
+    a.dx = G.gp.dx; a.dy = G.gp.dy; a.dz = G.gp.dz; a.DX = G.DX; a.DY = G.DY;
+    a.mn[0] = G.gp.mnx; a.mn[1] = G.gp.mny; a.mn[2] = G.gp.mnz;
+    a.cell = 1.0 / (double)G.gp.inv;
+    a.margin = 0.01 * a.cell + 1e-6 * amax;   // fp32 cell assignment: a few ulps of the coordinates, 1 % of a cell on top
+    for (int t = 0; t < 3; ++t) { a.bmn[t] = tmn[t]; a.bmx[t] = tmx[t]; }
+    a.d2 = max_dist * max_dist;
+    a.n = n_s;
+    a.probe = W.probe.ensure(n_s);
+    a.idx = W.idx.ensure(n_s); a.dd = W.dd.ensure(n_s);
+    a.fail = W.fail.ensure(n_s); a.fail_count = W.count.ensure(4);
+    memcpy(W.h_T, T16, sizeof(W.h_T));
+    HIP_TRY(hipMemcpyAsync(W.Tf.ensure(16), W.h_T, sizeof(W.h_T), hipMemcpyHostToDevice, ctx->stream));
+    W.keys.ensure(n_s); W.keys2.ensure(n_s); W.vals.ensure(n_s); W.vals2.ensure(n_s);
+    hipLaunchKernelGGL(k_distances_keys, dim3(cdiv(n_s, KEY_TPB)), dim3(KEY_TPB), 0, ctx->stream, d_src, n_s, stride, W.Tf.p, a, W.keys.p,
+                       W.vals.p, W.probe.p);
+    HIP_TRY(hipGetLastError());
+    int bits = 1;
+    while (((size_t)1 << bits) < G.ncells) ++bits;
+    sort_pairs_u32(ctx, W.keys.p, W.keys2.p, W.vals.p, W.vals2.p, n_s, bits);
+    a.order = W.vals2.p;
+    ctx->fill_async(a.fail_count, 0, 4);
+    HIP_TRY(hipEventRecord(W.ev[2], ctx->stream));
+    hipLaunchKernelGGL(k_distances_lane, dim3(cdiv(n_s, LANE_TPB)), dim3(LANE_TPB), 0, ctx->stream, a);
+    HIP_TRY(hipEventRecord(W.ev[3], ctx->stream));
+    hipLaunchKernelGGL(k_distances_ring, dim3(std::min(cdiv(n_s, RING_WAVES), 2048u)), dim3(64 * RING_WAVES), 0, ctx->stream, a);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(W.ev[4], ctx->stream));
+
+    SumArgs sa;
+    memset(&sa, 0, sizeof(sa));
+    const uint32_t blocks = cdiv(n_s, SUM_TPB);
+    sa.idx = a.idx; sa.dd = a.dd; sa.tgt = d_tgt; sa.src = d_src; sa.stride = stride; sa.n = n_s;
+    for (int k = 0; k < 12; ++k) sa.T[k] = (double)T16[k];
+    sa.plane = plane_out ? W.plane.ensure(n_s) : nullptr;
+    sa.partial = W.partial.ensure((size_t)blocks * SUM_TERMS);
+    double *d_out = W.out.ensure(SUM_TERMS);
+    hipLaunchKernelGGL(k_distances_summary, dim3(blocks), dim3(SUM_TPB), 0, ctx->stream, sa);
+    hipLaunchKernelGGL(k_distances_final, dim3(1), dim3(64), 0, ctx->stream, sa.partial, blocks, d_out);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(W.ev[5], ctx->stream));
+    HIP_TRY(hipMemcpyAsync(W.h_out, d_out, sizeof(W.h_out), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(&W.h_count, a.fail_count, 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (idx_out) HIP_TRY(hipMemcpyAsync(idx_out, a.idx, (size_t)n_s * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (d2_out) HIP_TRY(hipMemcpyAsync(d2_out, a.dd, (size_t)n_s * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (plane_out) HIP_TRY(hipMemcpyAsync(plane_out, sa.plane, (size_t)n_s * 4, hipMemcpyDeviceToHost, ctx->stream));
+    ctx->sync();
+
+    const double *o = W.h_out;
+    plade_distance_summary r;
+    memset(&r, 0, sizeof(r));
+    r.n = n_s;
+    r.count = (uint64_t)o[0];
+    r.plane_count = (uint64_t)o[4];
+    r.fitness = (double)r.count / (double)r.n;
+    r.rmse = r.count ? std::sqrt(o[1] / (double)r.count) : NAN;
+    r.mean = r.count ? o[2] / (double)r.count : NAN;
+    r.max = r.count ? o[3] : NAN;
+    r.plane_rmse = r.plane_count ? std::sqrt(o[5] / (double)r.plane_count) : NAN;
+    *summary = r;
+
+    float ms[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int k = 0; k < 5; ++k) HIP_TRY(hipEventElapsedTime(&ms[k], W.ev[k], W.ev[k + 1]));
+    ctx->stats.clear();
+    ctx->stats.add("distances_grid_s", 1e-3 * ms[0]);
+    ctx->stats.add("distances_sort_s", 1e-3 * ms[1]);
+    ctx->stats.add("distances_search_s", 1e-3 * (ms[2] + ms[3]));
+    ctx->stats.add("distances_lane_s", 1e-3 * ms[2]);
+    ctx->stats.add("distances_ring_s", 1e-3 * ms[3]);
+    ctx->stats.add("distances_summary_s", 1e-3 * ms[4]);
+    ctx->stats.add("distances_ring_queries", W.h_count);
+}
+
+void upload(plade_ctx *ctx, DBuf<float> &buf, const float *h, uint32_t n, uint32_t stride, float mn[3], float mx[3]) {
+    buf.ensure((size_t)n * stride + 4);
+    HIP_TRY(hipMemcpyAsync(buf.p, h, (size_t)n * stride * 4, hipMemcpyHostToDevice, ctx->stream));
+    bbox_host(ctx, buf.p, n, stride, mn, mx);   // (waits; refuses non-finite coordinates)
+}
+
+DistWork &work_of(plade_ctx *ctx) {
+    if (!ctx->dist_work) ctx->dist_work = dist_work_create();
+    return *ctx->dist_work;
+}
+
+}  // namespace
+}  // namespace plade
+
+using namespace plade;
+
+// ---- C ABI (include/plade_hip.h) ---------------------------------------------------------------------------------------------
+extern "C" int plade_cloud_distances(plade_ctx *ctx, const float *tgt_pos_nrm, uint32_t n_t, const float *src_xyz, uint32_t n_s,
+                                     uint32_t stride, const float *T16, float max_dist, int32_t *idx_out, float *d2_out,
+                                     float *plane_out, plade_distance_summary *summary) {
+    return guarded(ctx, [&]() -> int {
+        PLADE_REQUIRE(tgt_pos_nrm && src_xyz && summary, PLADE_EINVAL, "plade_cloud_distances: NULL cloud or summary");
+        PLADE_REQUIRE(n_t >= 1 && n_s >= 1, PLADE_EINVAL, "plade_cloud_distances: empty cloud (n = 0)");
+        PLADE_REQUIRE(stride >= 3, PLADE_EINVAL, "plade_cloud_distances: stride must be >= 3 floats");
+        const float *T = T16 ? T16 : kIdentity;
+        check_args(T, max_dist);
+        DistWork &W = work_of(ctx);
+        float tmn[3], tmx[3], smn[3], smx[3];
+        upload(ctx, W.in_t, tgt_pos_nrm, n_t, 6, tmn, tmx);
+        upload(ctx, W.in_s, src_xyz, n_s, stride, smn, smx);
+        distances_dev(ctx, W, W.in_t.p, n_t, tmn, tmx, W.in_s.p, n_s, stride, T, max_dist, idx_out, d2_out, plane_out, summary);
+        return PLADE_OK;
+    });
+}
+
+extern "C" int plade_cloud_distances_dev(plade_ctx *ctx, plade_cloud *tgt, plade_cloud *src, const float *T16, float max_dist,
+                                         int32_t *idx_out, float *d2_out, float *plane_out, plade_distance_summary *summary) {
+    return guarded(ctx, [&]() -> int {
+        PLADE_REQUIRE(tgt && src && summary, PLADE_EINVAL, "plade_cloud_distances_dev: NULL cloud or summary");
+        PLADE_REQUIRE(tgt->dev.n >= 1 && src->dev.n >= 1, PLADE_EINVAL, "plade_cloud_distances_dev: empty cloud (n = 0)");
+        const float *T = T16 ? T16 : kIdentity;
+        check_args(T, max_dist);
+        DistWork &W = work_of(ctx);
+        const CloudDev &t = tgt->dev, &s = src->dev;
+        distances_dev(ctx, W, t.aos.p, t.n, t.bbmin, t.bbmax, s.aos.p, s.n, 6, T, max_dist, idx_out, d2_out, plane_out, summary);
+        return PLADE_OK;
+    });
+}

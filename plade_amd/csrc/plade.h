@@ -58,6 +58,18 @@ bool refine_registration(Eigen::Matrix<float, 4, 4> &transformation,
                          pcl::PointCloud<pcl::PointNormal>::Ptr target_cloud,
                          pcl::PointCloud<pcl::PointNormal>::Ptr source_cloud);
 
+/** Registration quality (no counterpart in the reference): the fields of plade_distance_summary (include/plade_hip.h). */
+struct RegistrationQuality {
+    uint64_t n = 0, count = 0, plane_count = 0;   // source points, those within max_dist, those of them with a finite target normal
+    double fitness = 0, rmse = 0, mean = 0, max = 0, plane_rmse = 0;
+};
+/** Evaluates `transformation` (source -> target) on the GPU (plade_cloud_distances, no per-point outputs): fitness = the share of
+ *  source points whose nearest target point is closer than max_dist (absolute, in the clouds' units), the rmse / mean / max of
+ *  those distances and the point-to-plane rmse.  false: invalid input or no GPU; a warning is printed and `out` is unchanged.
+ *  The CLI prints one such evaluation per registered pair when PLADE_EVALUATE=<max_dist> is set. */
+bool evaluate_registration(const Eigen::Matrix4f &transformation, pcl::PointCloud<pcl::PointNormal>::Ptr target_cloud,
+                           pcl::PointCloud<pcl::PointNormal>::Ptr source_cloud, float max_dist, RegistrationQuality &out);
+
 /** Batch extension (no counterpart in the reference, whose batch mode is a plain loop of the file overload above,
  *  code/PLADE/main.cpp:122-148): `count` (1..registration_group_max = PLADE_GROUP_MAX) consecutive pairs of the list as ONE group.  Every pair gets the result,
  *  the messages and the identity-on-failure of the file overload -- its transformation is bit for bit the one the file overload

@@ -6,6 +6,7 @@
 #include "ply_reader.h"
 
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <cstdlib>
@@ -158,6 +159,46 @@ bool refine_packed(plade_ctx *ctx, float *T16, const float *tg, size_t n_t, cons
     return true;
 }
 
+// PLADE_EVALUATE=<d> (opt-in, absolute, in the clouds' units): every pair that registered -- after the ICP refinement when that
+// is on -- is evaluated at max_dist d (plade_cloud_distances, no per-point outputs) and one console line reports its fitness.
+// The pair is evaluated as it was registered (after the target / source switch).  A value that is not a positive finite number
+// prints one warning and evaluates nothing; unset, nothing changes.
+float evaluate_dist() {
+    static const float d = [] {
+        const char *w = getenv("PLADE_EVALUATE");
+        if (!w) return 0.f;
+        char *end = nullptr;
+        const double v = strtod(w, &end);
+        const float f = (float)v;
+        if (end == w || *end != '\0' || !std::isfinite(f) || !(f > 0.f)) {
+            std::cerr << "warning: PLADE_EVALUATE=" << w << " is not a positive finite distance; no evaluation" << std::endl;
+            return 0.f;
+        }
+        return f;
+    }();
+    return d;
+}
+bool evaluate_packed(plade_ctx *ctx, const float *T16, const float *tg, size_t n_t, const float *sr, size_t n_s, float max_dist,
+                     plade_distance_summary &s) {
+    trace("evaluate: measuring");
+    const int rc = plade_cloud_distances(ctx, tg, (uint32_t)n_t, sr, (uint32_t)n_s, 6, T16, max_dist, nullptr, nullptr, nullptr, &s);
+    trace("evaluate: done");
+    if (rc != PLADE_OK) {
+        con_err() << "warning: evaluation failed (" << plade_last_error(ctx) << ")" << std::endl;
+        return false;
+    }
+    return true;
+}
+void evaluate_line(plade_ctx *ctx, const float *T16, const float *tg, size_t n_t, const float *sr, size_t n_s) {
+    const float d = evaluate_dist();
+    plade_distance_summary s;
+    if (!(d > 0.f) || !evaluate_packed(ctx, T16, tg, n_t, sr, n_s, d, s)) return;
+    char b[240];
+    snprintf(b, sizeof(b), "evaluation: fitness %.4f, rmse %.6g, %llu of %llu source points within %g", s.fitness, s.rmse,
+             (unsigned long long)s.count, (unsigned long long)s.n, (double)d);
+    con_out() << b << std::endl;
+}
+
 std::string extension(const std::string &file_name) {  // util.cpp:525-531
     std::string::size_type dot = file_name.find_last_of('.');
     std::string::size_type slash = file_name.find_last_of("/\\");
@@ -288,6 +329,7 @@ bool register_packed(Eigen::Matrix<float, 4, 4> &transformation, const float *tg
     }
     con_out() << "done. time: " << w.str() << std::endl;
     if (refine_icp_on()) refine_packed(ctx, T16, tg, n_t, sr, n_s);
+    if (evaluate_dist() > 0.f) evaluate_line(ctx, T16, tg, n_t, sr, n_s);
     to_matrix(T16, transformation);
     return true;
 }
@@ -449,6 +491,7 @@ void registration_group(size_t count, Eigen::Matrix<float, 4, 4> *transformation
         }
         con_out() << "done. time: " << w.str() << std::endl;
         if (refine_icp_on()) refine_packed(ctx, T16 + 16 * q, it.tg, it.n_t, it.sr, it.n_s);
+        if (evaluate_dist() > 0.f) evaluate_line(ctx, T16 + 16 * q, it.tg, it.n_t, it.sr, it.n_s);
         to_matrix(T16 + 16 * q, transformations[it.pair]);
         if (it.switched) transformations[it.pair] = transformations[it.pair].inverse();
         ok[it.pair] = true;
@@ -466,6 +509,21 @@ bool refine_registration(Eigen::Matrix<float, 4, 4> &transformation, pcl::PointC
     for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) T16[4 * r + c] = transformation(r, c);
     if (!refine_packed(ctx, T16, tg.data(), target_cloud->size(), sr.data(), source_cloud->size())) return false;
     to_matrix(T16, transformation);
+    return true;
+}
+
+// registration quality: see plade.h
+bool evaluate_registration(const Eigen::Matrix4f &transformation, pcl::PointCloud<pcl::PointNormal>::Ptr target_cloud,
+                           pcl::PointCloud<pcl::PointNormal>::Ptr source_cloud, float max_dist, RegistrationQuality &out) {
+    plade_ctx *ctx = context();
+    if (!ctx) return false;
+    std::vector<float> tg = flatten(*target_cloud), sr = flatten(*source_cloud);
+    float T16[16];
+    for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) T16[4 * r + c] = transformation(r, c);
+    plade_distance_summary s;
+    if (!evaluate_packed(ctx, T16, tg.data(), target_cloud->size(), sr.data(), source_cloud->size(), max_dist, s)) return false;
+    out.n = s.n; out.count = s.count; out.plane_count = s.plane_count;
+    out.fitness = s.fitness; out.rmse = s.rmse; out.mean = s.mean; out.max = s.max; out.plane_rmse = s.plane_rmse;
     return true;
 }
 

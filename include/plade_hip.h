@@ -342,14 +342,19 @@ int plade_cloud_upload_xyz(plade_ctx *ctx, const float *xyz, uint32_t n, uint32_
  * parameter that is 0 takes the automatic value in brackets.
  *   sample       S = plade_voxel_downsample of the source's x y z with leaf source_leaf [0.005 D]
  *   iterate      T_k in fp64, T_0 = T_in; the stage distance d starts at max_dist [0.025 D]
+ *   centre       s-bar = the fp64 mean of S (summed once in a fixed order), c_k = T_k s-bar in fp64
  *   match        p' = fp32(R) s + fp32(t), each row ((r0 x + r1 y) + r2 z) + t in fp32; j = the argmin over ALL target points
  *                of (fp32 FLANN L2 (p', q_j), j); s has a correspondence when that distance < (float)d * (float)d and n_j is
  *                finite.  An exact set: independent of grid cell sizes and launch shapes.
- *   linearise    fp64 over the correspondences, p = T_k double(s): r = n . (p - q), J = [p x n, n]; the 21 values of J^T J, the 6 of
+ *   linearise    fp64 over the correspondences, p = T_k double(s): r = n . (p - q), J = [(p - c_k) x n, n]; the 21 values of J^T J, the 6 of
  *                J^T r, sum r^2 and the count, summed in a fixed order (bit-identical from run to run)
- *   solve        J^T J x = -J^T r by fp64 Cholesky; a pivot <= 1e-12 max(diag) is a degenerate geometry
- *   update       T_{k+1} = [Rodrigues(x0..2) | x3..5] T_k
- *   schedule     a stage converges when |x0..2| < eps_rotation [1e-6 rad] and |x3..5| < eps_translation [1e-6 D]; then
+ *   solve        J^T J x = -J^T r by fp64 Cholesky; pivot j <= 1e-12 A[j][j] (its own diagonal entry, so an exactly zero column
+ *                counts) is a degenerate geometry; the test does not depend on the units or the distance from the origin
+ *   update       T_{k+1} = [R | (c_k - R c_k) + x3..5] T_k, R = Rodrigues(x0..2): a rotation about c_k; x3..5 moves the centre
+ *   tolerances   with A = the target's max |coordinate|, the effective tolerances are eps_t = max(eps_translation, 4 2^-23 A) and
+ *                eps_r = max(eps_rotation, 4 2^-23 A / D), given values included: no step can shrink below the fp32 resolution of
+ *                the coordinates, so a tighter tolerance would only run the loop to max_iterations
+ *   schedule     a stage converges when |x0..2| < eps_r [1e-6 rad] and |x3..5| < eps_t [1e-6 D]; then
  *                d = max(min_dist, d / 2) while d > min_dist [0.0025 D], else stop with converged = 1; at most max_iterations
  *                [60] updates in all (then converged = 0, still PLADE_OK, T_out = the last iterate)
  *   failure      PLADE_EFAIL and T_out = T_in when an iteration has fewer than min_correspondences [100] correspondences
@@ -389,10 +394,11 @@ int plade_refine_icp(plade_ctx *ctx, const float *tgt_pos_nrm, uint32_t n_t, con
 /* The same on resident clouds (plade_cloud_upload, plade_cloud_upload_xyz): bit-identical results. */
 int plade_refine_icp_dev(plade_ctx *ctx, plade_cloud *tgt, plade_cloud *src, const float *T_in16, const plade_icp_params *params,
                          float *T_out16, plade_icp_result *result);
-/* Test seam: one match + linearise pass at stage distance `dist` on the given points (no sample): corr_out[i] = j or -1 (n_s
- * int32, may be NULL); moments_out = J^T J (21 values, row-major upper triangle), J^T r (6), sum r^2, count. */
+/* Test seam: one match + linearise pass at stage distance `dist` on the given points (no sample), with J taken about the fp64
+ * point center[3] (the refinement uses c_k = T_k s-bar): corr_out[i] = j or -1 (n_s int32, may be NULL); moments_out = J^T J
+ * (21 values, row-major upper triangle), J^T r (6), sum r^2, count. */
 int plade_icp_linearize(plade_ctx *ctx, const float *tgt_pos_nrm, uint32_t n_t, const float *src_xyz, uint32_t n_s, uint32_t stride,
-                        const double *T16, float dist, int32_t *corr_out, double *moments_out);
+                        const double *T16, const double *center, float dist, int32_t *corr_out, double *moments_out);
 
 /* ---- cloud-to-cloud distances and registration quality (no reference counterpart) ------------------------------------------
  * Semantics (plade_amd/csrc/distances.h).  Target: n_t points x y z nx ny nz (the normals may be NaN, as

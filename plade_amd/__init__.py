@@ -130,7 +130,7 @@ def load_library(path=LIB_PATH):
     sig("plade_icp_default_params", argtypes=[C.POINTER(IcpParams)], restype=None)
     sig("plade_refine_icp", argtypes=[p, p, u32, p, u32, p, C.POINTER(IcpParams), p, C.POINTER(IcpResult)])
     sig("plade_refine_icp_dev", argtypes=[p, p, p, p, C.POINTER(IcpParams), p, C.POINTER(IcpResult)])
-    sig("plade_icp_linearize", argtypes=[p, p, u32, p, u32, u32, p, f, p, p])
+    sig("plade_icp_linearize", argtypes=[p, p, u32, p, u32, u32, p, p, f, p, p])
     sig("plade_cloud_distances", argtypes=[p, p, u32, p, u32, u32, p, f, p, p, p, C.POINTER(DistanceSummary)])
     sig("plade_cloud_distances_dev", argtypes=[p, p, p, p, f, p, p, p, C.POINTER(DistanceSummary)])
     sig("plade_sort_segments", argtypes=[p, p, p, p, u32, C.c_int, p, p])
@@ -691,18 +691,20 @@ class Context:
         return self._refine(lambda T_in, prm, T_out, res: self.L.plade_refine_icp_dev(
             self.h, tgt_cloud.h, src_cloud.h, _ptr(T_in), C.byref(prm), _ptr(T_out), C.byref(res)), T, icp_params)
 
-    def icp_linearize(self, tgt, src_xyz, T, dist):
+    def icp_linearize(self, tgt, src_xyz, T, dist, center=None):
         """plade_icp_linearize (test seam): one match + linearise pass of the ICP at stage distance `dist` with the fp64 4 x 4 T on
-        every point of src_xyz (no sample).  Returns (corr, moments): corr (N,) int32 = the target index or -1, moments (29,)
+        every point of src_xyz (no sample), J about the fp64 point `center` (None: the origin, J = [p x n, n]; the refinement
+        linearises about c_k = T_k s-bar, s-bar = the fp64 mean of its sample).  Returns (corr, moments): corr (N,) int32 = the target index or -1, moments (29,)
         float64 = J^T J (upper triangle, row-major), J^T r, sum r^2, count."""
         tgt = _f32(tgt)
         self._check_cloud(tgt, "icp_linearize")
         a, n, stride = _xyz_view(src_xyz)
         T64 = np.ascontiguousarray(T, dtype=np.float64).reshape(4, 4)
+        c64 = np.ascontiguousarray((0.0, 0.0, 0.0) if center is None else center, dtype=np.float64).reshape(3)
         corr = np.empty(n, np.int32)
         mom = np.zeros(29, np.float64)
-        self._check(self.L.plade_icp_linearize(self.h, _ptr(tgt), len(tgt), _ptr(a), n, stride, _ptr(T64), float(dist), _ptr(corr),
-                                               _ptr(mom)))
+        self._check(self.L.plade_icp_linearize(self.h, _ptr(tgt), len(tgt), _ptr(a), n, stride, _ptr(T64), _ptr(c64), float(dist),
+                                               _ptr(corr), _ptr(mom)))
         return corr, mom
 
     # ---- cloud-to-cloud distances ------------------------------------------------------------

@@ -4,13 +4,16 @@
 //   grids   one dense row index of TargetGrid (overlap.h) per stage distance d, cell >= d: the 27 cells around a probe's cell
 //           are nine contiguous runs of `sorted` and hold every target point closer than d, so the argmin over them is the
 //           exact one whenever it is below d (and the probe has no correspondence otherwise).  The grids are built up front.
+//   mean    k_icp_mean_part / k_icp_mean: the fp64 mean s-bar of the sample, once, in a fixed order (one partial per workgroup:
+//           a butterfly across each wave, then the waves in order; one wavefront then sums the partials like k_icp_solve); the
+//           second kernel also sets the first centre c_0 = T_0 s-bar.
 //   loop    max_iterations pairs (k_icp_corr_lin, k_icp_solve) queued on the context's stream with no host wait in between; the
 //           state word lives on the device (IcpState), and once it says done every later kernel returns at once.
 //   corr    k_icp_corr_lin: one lane per sample point.  The lane forms p' in fp32, takes the exact (d, j) argmin key over the
-//           nine runs of the current stage's grid, and -- with a correspondence -- r and J in fp64; the 29 moments are summed
+//           nine runs of the current stage's grid, and -- with a correspondence -- r and J (about the centre c_k) in fp64; the 29 moments are summed
 //           across the wave (butterfly), then the four waves in order, and each workgroup writes one partial to its own slot.
 //   solve   k_icp_solve: one wavefront sums the partials in a fixed order (lane l: partials l, l + 64, ..., then a butterfly),
-//           and lane 0 runs the Cholesky solve, Rodrigues, the update of T and the stage / convergence / failure rules.
+//           and lane 0 runs the Cholesky solve, Rodrigues, the update of T and c and the stage / convergence / failure rules.
 #include "icp.h"
 #include "overlap.h"
 #include "voxel.h"
@@ -26,8 +29,11 @@ constexpr int CORR_TPB = 256;
 // the device state of one refinement (one allocation, uploaded once per call)
 struct IcpState {
     double T[12];        // the fp64 iterate, rows 0..2 of [R | t]
+    double c[3];         // the centre of the linearisation, c_k = T_k s-bar (the seam: given)
+    double sbar[3];      // the fp64 mean of the sample
     float Tf[12];        // its fp32 rounding (the match step's transform)
-    int32_t done, iter, stage, converged, failure, pad0;
+    int32_t done, iter, stage, converged, failure;
+    int32_t lin_stage;   // the stage of the last linearisation (stage may have moved on after it: the result reports this one)
     uint32_t count, pad1;
     double sum_r2;
 };
@@ -105,7 +111,8 @@ __global__ __launch_bounds__(CORR_TPB) void k_icp_corr_lin(const IcpArgs a) {
                 const double p1 = ((T[4] * X + T[5] * Y) + T[6] * Z) + T[7];
                 const double p2 = ((T[8] * X + T[9] * Y) + T[10] * Z) + T[11];
                 const double r = (n0 * (p0 - (double)t[0]) + n1 * (p1 - (double)t[1])) + n2 * (p2 - (double)t[2]);
-                const double J[6] = {p1 * n2 - p2 * n1, p2 * n0 - p0 * n2, p0 * n1 - p1 * n0, n0, n1, n2};
+                const double u0 = p0 - st->c[0], u1 = p1 - st->c[1], u2 = p2 - st->c[2];
+                const double J[6] = {u1 * n2 - u2 * n1, u2 * n0 - u0 * n2, u0 * n1 - u1 * n0, n0, n1, n2};
                 int k = 0;
 #pragma unroll
                 for (int u = 0; u < 6; ++u)
@@ -135,6 +142,55 @@ __global__ __launch_bounds__(CORR_TPB) void k_icp_corr_lin(const IcpArgs a) {
         for (int w = 1; w < CORR_TPB / 64; ++w) v += s_red[w][threadIdx.x];
         a.partial[(size_t)blockIdx.x * ICP_MOMENTS + threadIdx.x] = v;
     }
+}
+
+// the fp64 sums of the sample's x y z, one partial per workgroup (the fixed order of k_icp_corr_lin's reduction)
+__global__ __launch_bounds__(CORR_TPB) void k_icp_mean_part(const float *src, uint32_t n, double *partial) {
+    __shared__ double s_red[CORR_TPB / 64][3];
+    const uint32_t i = blockIdx.x * CORR_TPB + threadIdx.x;
+    double m[3] = {0.0, 0.0, 0.0};
+    if (i < n) { m[0] = src[(size_t)i * 3]; m[1] = src[(size_t)i * 3 + 1]; m[2] = src[(size_t)i * 3 + 2]; }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        double v = m[k];
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+        if (lane == 0) s_red[wave][k] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        double v = s_red[0][threadIdx.x];
+#pragma unroll
+        for (int w = 1; w < CORR_TPB / 64; ++w) v += s_red[w][threadIdx.x];
+        partial[(size_t)blockIdx.x * 3 + threadIdx.x] = v;
+    }
+}
+
+// T v for the fp64 rows of T (((r0 x + r1 y) + r2 z) + t)
+__device__ __forceinline__ void apply_T(const double T[12], const double v[3], double out[3]) {
+#pragma unroll
+    for (int r = 0; r < 3; ++r) out[r] = ((T[4 * r] * v[0] + T[4 * r + 1] * v[1]) + T[4 * r + 2] * v[2]) + T[4 * r + 3];
+}
+
+// one wavefront: s-bar = the sum of the partials (lane l: l, l + 64, ..., then a butterfly) / n, and c_0 = T_0 s-bar
+__global__ __launch_bounds__(64) void k_icp_mean(IcpState *st, const double *partial, uint32_t blocks, uint32_t n) {
+    const int lane = threadIdx.x;
+    double m[3] = {0.0, 0.0, 0.0};
+    for (uint32_t b = (uint32_t)lane; b < blocks; b += 64)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) m[k] += partial[(size_t)b * 3 + k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) m[k] += __shfl_xor(m[k], o, 64);
+    if (lane != 0) return;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) st->sbar[k] = n ? m[k] / (double)n : 0.0;
+    double c[3];
+    apply_T(st->T, st->sbar, c);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) st->c[k] = c[k];
 }
 
 // fp64 rotation of the axis-angle vector w (Rodrigues); w = 0: the identity
@@ -172,6 +228,7 @@ __global__ __launch_bounds__(64) void k_icp_solve(const IcpSolveArgs a) {
         return;
     }
     const uint32_t count = (uint32_t)m[28];
+    st->lin_stage = st->stage;
     st->count = count;
     st->sum_r2 = m[27];
     if (count < a.min_corr) { st->failure = PLADE_ICP_TOO_FEW; st->done = 1; return; }
@@ -184,16 +241,15 @@ __global__ __launch_bounds__(64) void k_icp_solve(const IcpSolveArgs a) {
 #pragma unroll
             for (int v = u; v < 6; ++v) { A[u][v] = m[k]; A[v][u] = m[k]; ++k; }
     }
-    double dmax = 0.0;
-#pragma unroll
-    for (int u = 0; u < 6; ++u) dmax = fmax(dmax, A[u][u]);
-    bool degenerate = !(dmax > 0.0);
+    // a pivot is compared with its own diagonal entry: the test does not change when a column is rescaled (units, lever
+    // arms), and an exactly zero column (an unconstrained motion) is degenerate
+    bool degenerate = false;
 #pragma unroll
     for (int j = 0; j < 6; ++j) {
         double piv = A[j][j];
 #pragma unroll
         for (int k = 0; k < j; ++k) piv -= L[j][k] * L[j][k];
-        if (!(piv > 1e-12 * dmax)) degenerate = true;
+        if (!(piv > 1e-12 * A[j][j])) degenerate = true;
         L[j][j] = sqrt(fmax(piv, 1e-300));
 #pragma unroll
         for (int i = j + 1; i < 6; ++i) {
@@ -219,18 +275,27 @@ __global__ __launch_bounds__(64) void k_icp_solve(const IcpSolveArgs a) {
         for (int k = i + 1; k < 6; ++k) v -= L[k][i] * x[k];
         x[i] = v / L[i][i];
     }
+    // T_{k+1} = [R | (c - R c) + x3..5] T_k: a rotation about the centre c = c_k, then x3..5 moves the centre
     double R[9];
     rodrigues(x, R);
+    double c[3], tu[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) c[r] = st->c[r];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) tu[r] = (c[r] - ((R[3 * r] * c[0] + R[3 * r + 1] * c[1]) + R[3 * r + 2] * c[2])) + x[3 + r];
     double Tn[12];
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
 #pragma unroll
-        for (int c = 0; c < 3; ++c)
-            Tn[4 * r + c] = (R[3 * r] * st->T[c] + R[3 * r + 1] * st->T[4 + c]) + R[3 * r + 2] * st->T[8 + c];
-        Tn[4 * r + 3] = ((R[3 * r] * st->T[3] + R[3 * r + 1] * st->T[7]) + R[3 * r + 2] * st->T[11]) + x[3 + r];
+        for (int k = 0; k < 3; ++k)
+            Tn[4 * r + k] = (R[3 * r] * st->T[k] + R[3 * r + 1] * st->T[4 + k]) + R[3 * r + 2] * st->T[8 + k];
+        Tn[4 * r + 3] = ((R[3 * r] * st->T[3] + R[3 * r + 1] * st->T[7]) + R[3 * r + 2] * st->T[11]) + tu[r];
     }
 #pragma unroll
     for (int k = 0; k < 12; ++k) { st->T[k] = Tn[k]; st->Tf[k] = (float)Tn[k]; }
+    apply_T(Tn, st->sbar, c);
+#pragma unroll
+    for (int r = 0; r < 3; ++r) st->c[r] = c[r];
     const int iter = st->iter + 1;
     st->iter = iter;
     const double nr = sqrt((x[0] * x[0] + x[1] * x[1]) + x[2] * x[2]), nt = sqrt((x[3] * x[3] + x[4] * x[4]) + x[5] * x[5]);
@@ -272,6 +337,12 @@ double diag_of(const float mn[3], const float mx[3]) {
     return std::sqrt(ex * ex + ey * ey + ez * ez);
 }
 
+double amax_of(const float mn[3], const float mx[3]) {
+    double a = 0.0;
+    for (int t = 0; t < 3; ++t) a = std::max(a, std::max(std::fabs((double)mn[t]), std::fabs((double)mx[t])));
+    return a;
+}
+
 void check_param(double v, const char *what) {
     PLADE_REQUIRE(std::isfinite(v) && v >= 0.0, PLADE_EINVAL, std::string("refine_icp: ") + what + " must be finite and >= 0");
 }
@@ -289,8 +360,11 @@ IcpConfig resolve(const plade_icp_params *prm, const float tmn[3], const float t
     c.leaf = p.source_leaf > 0.0 ? p.source_leaf : 0.005 * D;
     c.max_dist = p.max_dist > 0.0 ? p.max_dist : 0.025 * D;
     c.min_dist = p.min_dist > 0.0 ? p.min_dist : std::min(0.0025 * D, c.max_dist);
-    c.eps_rot = p.eps_rotation > 0.0 ? p.eps_rotation : 1e-6;
-    c.eps_trans = p.eps_translation > 0.0 ? p.eps_translation : 1e-6 * D;
+    // the tolerances never fall below what fp32 coordinates of the target's size resolve (4 ulp(1) max|coordinate|): below it
+    // a step cannot shrink and the loop would spin to the cap
+    const double floor_t = 4.0 * std::ldexp(1.0, -23) * amax_of(tmn, tmx);
+    c.eps_rot = std::max(p.eps_rotation > 0.0 ? p.eps_rotation : 1e-6, floor_t / D);
+    c.eps_trans = std::max(p.eps_translation > 0.0 ? p.eps_translation : 1e-6 * D, floor_t);
     c.max_iter = p.max_iterations > 0 ? p.max_iterations : 60;
     c.min_corr = p.min_correspondences > 0 ? (uint32_t)p.min_correspondences : 100u;
     PLADE_REQUIRE(c.min_dist <= c.max_dist, PLADE_EINVAL, "refine_icp: min_dist > max_dist");
@@ -308,9 +382,7 @@ IcpGridArgs stage_grid(plade_ctx *ctx, TargetGrid &G, const float *d_tgt, uint32
                        double d) {
     // cell >= d with a margin for the fp32 cell assignment: 1 % of d and a few ulps of the largest coordinate (build() adds 0.1 %
     // and may enlarge the cell further; a larger cell only adds candidates)
-    double amax = 0.0;
-    for (int t = 0; t < 3; ++t) amax = std::max(amax, std::max(std::fabs((double)tmn[t]), std::fabs((double)tmx[t])));
-    G.build(ctx, d_tgt, n_t, 6, (float)(1.01 * d + 4e-6 * amax), tmn, tmx, true);
+    G.build(ctx, d_tgt, n_t, 6, (float)(1.01 * d + 4e-6 * amax_of(tmn, tmx)), tmn, tmx, true);
     PLADE_REQUIRE(G.dense, PLADE_EINVAL, "refine_icp: needs the dense row index (unset PLADE_OVERLAP_INDEX_COMPACT)");
     IcpGridArgs g;
     g.sorted = G.sorted.p; g.row_start = G.row_start.p;
@@ -321,9 +393,10 @@ IcpGridArgs stage_grid(plade_ctx *ctx, TargetGrid &G, const float *d_tgt, uint32
     return g;
 }
 
-void init_state(IcpState &s, const double T[16]) {
+void init_state(IcpState &s, const double T[16], const double *center) {
     memset(&s, 0, sizeof(s));
     for (int k = 0; k < 12; ++k) { s.T[k] = T[k]; s.Tf[k] = (float)T[k]; }
+    if (center) for (int k = 0; k < 3; ++k) s.c[k] = center[k];
 }
 
 void check_T(const float *T16) {
@@ -353,8 +426,10 @@ int refine_dev(plade_ctx *ctx, IcpWork &W, const float *d_tgt, uint32_t n_t, con
     a.corr = nullptr;
     double T[16];
     for (int k = 0; k < 16; ++k) T[k] = T_in[k];
-    init_state(W.h_init, T);
+    init_state(W.h_init, T, nullptr);
     HIP_TRY(hipMemcpyAsync(W.st.p, &W.h_init, sizeof(IcpState), hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_icp_mean_part, dim3(blocks), dim3(CORR_TPB), 0, ctx->stream, a.src, n, a.partial);
+    hipLaunchKernelGGL(k_icp_mean, dim3(1), dim3(64), 0, ctx->stream, a.st, (const double *)a.partial, blocks, n);
     IcpSolveArgs sa;
     sa.st = a.st; sa.partial = a.partial; sa.blocks = blocks; sa.n_stages = c.n_stages; sa.max_iter = c.max_iter;
     sa.min_corr = c.min_corr; sa.eps_rot = c.eps_rot; sa.eps_trans = c.eps_trans; sa.moments = nullptr;
@@ -370,14 +445,14 @@ int refine_dev(plade_ctx *ctx, IcpWork &W, const float *d_tgt, uint32_t n_t, con
     plade_icp_result r;
     memset(&r, 0, sizeof(r));
     r.iterations = s.iter;
-    r.stages = s.stage + 1;
+    r.stages = s.lin_stage + 1;
     r.converged = s.converged;
     r.failure = s.failure;
     r.correspondences = s.count;
     r.samples = n;
     r.rmse = s.count ? std::sqrt(s.sum_r2 / (double)s.count) : 0.0;
     r.fitness = n ? (double)s.count / (double)n : 0.0;
-    r.final_dist = c.dist[s.stage];
+    r.final_dist = c.dist[s.lin_stage];
     if (res) *res = r;
     float ms[3] = {0.f, 0.f, 0.f};
     for (int k = 0; k < 3; ++k) HIP_TRY(hipEventElapsedTime(&ms[k], W.ev[k], W.ev[k + 1]));
@@ -453,12 +528,14 @@ extern "C" int plade_refine_icp_dev(plade_ctx *ctx, plade_cloud *tgt, plade_clou
 }
 
 extern "C" int plade_icp_linearize(plade_ctx *ctx, const float *tgt_pos_nrm, uint32_t n_t, const float *src_xyz, uint32_t n_s,
-                                   uint32_t stride, const double *T16, float dist, int32_t *corr_out, double *moments_out) {
+                                   uint32_t stride, const double *T16, const double *center, float dist, int32_t *corr_out,
+                                   double *moments_out) {
     return guarded(ctx, [&]() -> int {
-        PLADE_REQUIRE(tgt_pos_nrm && src_xyz && T16 && moments_out, PLADE_EINVAL, "plade_icp_linearize: bad argument");
+        PLADE_REQUIRE(tgt_pos_nrm && src_xyz && T16 && center && moments_out, PLADE_EINVAL, "plade_icp_linearize: bad argument");
         PLADE_REQUIRE(n_t >= 1 && n_s >= 1 && stride >= 3, PLADE_EINVAL, "plade_icp_linearize: empty cloud or stride < 3");
         PLADE_REQUIRE(std::isfinite(dist) && dist > 0.f, PLADE_EINVAL, "plade_icp_linearize: dist must be finite and > 0");
         for (int k = 0; k < 16; ++k) PLADE_REQUIRE(std::isfinite(T16[k]), PLADE_EINVAL, "plade_icp_linearize: T must be finite");
+        for (int k = 0; k < 3; ++k) PLADE_REQUIRE(std::isfinite(center[k]), PLADE_EINVAL, "plade_icp_linearize: center must be finite");
         IcpWork &W = work_of(ctx);
         float tmn[3], tmx[3], smn[3], smx[3];
         upload(ctx, W.in_t, tgt_pos_nrm, n_t, 6, tmn, tmx);
@@ -472,7 +549,7 @@ extern "C" int plade_icp_linearize(plade_ctx *ctx, const float *tgt_pos_nrm, uin
         a.st = W.st.ensure(1);
         a.partial = W.partial.ensure((size_t)blocks * ICP_MOMENTS);
         a.corr = W.corr.ensure(n_s);
-        init_state(W.h_init, T16);
+        init_state(W.h_init, T16, center);
         HIP_TRY(hipMemcpyAsync(W.st.p, &W.h_init, sizeof(IcpState), hipMemcpyHostToDevice, ctx->stream));
         IcpSolveArgs sa;
         memset(&sa, 0, sizeof(sa));

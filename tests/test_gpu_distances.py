@@ -11,6 +11,7 @@ import plade_amd
 from plade_amd.plyio import write_ply
 from plade_amd.synth import make_pair
 import distance_restate as R
+import icp_restate as IR
 
 pytestmark = pytest.mark.gpu
 
@@ -89,6 +90,18 @@ def test_20k_scene_at_every_scale(dctx, frac):
     idx, _, _, s = _check(dctx, tg, sr, frac * D, T=T)
     if frac == 2.0:
         assert s["count"] == len(sr)           # every point corresponds
+
+
+@pytest.mark.parametrize("offset", [100.0, 500.0])
+@pytest.mark.parametrize("frac", [0.002, 0.01, 0.05, 2.0])
+def test_20k_scene_at_every_scale_far_from_the_origin(dctx, frac, offset):
+    tg, sr, T = make_pair(20_000, seed=0)
+    D = R.diag(tg)
+    F = IR.frame(offset * D)
+    tg, sr = IR.move(tg, F), IR.move(sr, F)
+    idx, _, _, s = _check(dctx, tg, sr, frac * D, T=IR.conjugate(T, F).astype(np.float32))
+    if frac == 2.0:
+        assert s["count"] == len(sr)
 
 
 def test_1m_pair_sample(dctx):

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import plade_amd
+import icp_restate as IR
 from plade_amd.synth import make_pair, sample_scene
 from conftest import GT_TOL, ORIENTED
 from test_normals_host import PARENT_RESULT, PARENT_STDERR, PARENT_STDOUT
@@ -103,6 +104,20 @@ def test_every_query_of_a_20k_scene(nctx):
     assert np.array_equal(out[:, :3].view(np.uint32), P.view(np.uint32))
     checked = check_against_ref(P, out, curv, nbr, np.arange(len(P)), 16)
     assert checked > 0.8 * len(P)
+
+
+@pytest.mark.timeout(600)
+@pytest.mark.parametrize("offset", [100.0, 500.0])
+def test_20k_scene_far_from_the_origin(nctx, offset):
+    """The 20k scene moved offset x D away (fp32 coordinates of ~10^4 with a 13 m room): the grid's cell keeps its slack of
+    4e-6 max|coordinate|, so the neighbour lists stay exact."""
+    P = scene_xyz(20000)
+    D = float(np.linalg.norm(P.max(0).astype(np.float64) - P.min(0)))
+    P = IR.move(P, IR.frame(offset * D))
+    out, curv, nbr = nctx.estimate_normals(P, k=16, curvature=True, neighbours=True)
+    assert np.array_equal(out[:, :3].view(np.uint32), P.view(np.uint32))
+    checked = check_against_ref(P, out, curv, nbr, gen_queries(len(P), 4000, seed=int(offset)), 16)
+    assert checked > 0.8 * 4000
 
 
 @pytest.mark.parametrize("k", [3, 8, 24, 40, 64])

@@ -43,6 +43,18 @@ def test_stage_schedule():
     assert R.resolve(10.0, max_dist=0.01)["dists"] == [0.01]     # an automatic min_dist is capped at max_dist
 
 
+def test_tolerances_never_fall_below_the_fp32_resolution():
+    ulp = 2.0 ** -23
+    c = R.resolve(10.0, amax=6.0)                                 # near the origin the floor (2.9e-6) is inactive
+    assert (c["eps_trans"], c["eps_rot"]) == (1e-6 * 10.0, 1e-6)
+    c = R.resolve(10.0, amax=5000.0)                              # 500 D away: 4 ulp(5000) = 2.4e-3 > 1e-5
+    assert c["eps_trans"] == 4 * ulp * 5000.0 and c["eps_rot"] == 4 * ulp * 5000.0 / 10.0
+    c = R.resolve(10.0, eps_translation=1e-9, eps_rotation=1e-12, amax=5000.0)   # given values are floored too
+    assert c["eps_trans"] == 4 * ulp * 5000.0 and c["eps_rot"] == 4 * ulp * 5000.0 / 10.0
+    c = R.resolve(10.0, eps_translation=1.0, eps_rotation=0.5, amax=5000.0)      # and a looser value stays
+    assert (c["eps_trans"], c["eps_rot"]) == (1.0, 0.5)
+
+
 def test_exact_match_breaks_ties_by_index_and_skips_nan_normals():
     tgt = np.zeros((4, 6), np.float32)
     tgt[:, :3] = [[1, 0, 0], [0, 1, 0], [1, 0, 0], [0, 0, 5]]
@@ -87,4 +99,73 @@ def test_restatement_failure_reasons():
     far[:, 2] += 100
     T, info = R.refine(plane, far, np.eye(4))
     assert info["failure"] == R.TOO_FEW and info["correspondences"] == 0
+
+
+# ---- changes of frame and units -------------------------------------------------------------------------------------------------
+def planes(normals, n=6000, seed=0):
+    """Points on the unit squares through the origin with the given exact axis normals (the other two coordinates in [0, 1])."""
+    rng = np.random.default_rng(seed)
+    parts = []
+    for ax in normals:
+        p = np.zeros((n // len(normals), 6), np.float32)
+        free = [k for k in range(3) if k != ax]
+        p[:, free] = rng.uniform(0, 1, size=(len(p), 2))
+        p[:, 3 + ax] = 1
+        parts.append(p)
+    return np.ascontiguousarray(np.concatenate(parts))
+
+
+@pytest.mark.parametrize("offset", [0.0, 1000.0])
+def test_restatement_single_plane_and_crease_are_degenerate_in_any_frame(offset):
+    for normals in ((2,), (0, 1)):            # a crease of two planes: translation along their common line is unconstrained
+        cloud = planes(normals)
+        F = R.frame(offset * R.Target(cloud).diag)
+        moved = R.move(cloud, F)
+        T, info = R.refine(moved, moved, np.eye(4), S=moved[:, :3])
+        assert info["failure"] == R.DEGENERATE and info["iterations"] == 0, (normals, info)
+
+
+def test_restatement_three_planes_are_not_degenerate_far_away():
+    cloud = planes((0, 1, 2))
+    for offset in (0.0, 1000.0):
+        F = R.frame(offset * R.Target(cloud).diag)
+        moved = R.move(cloud, F)
+        T0 = R.conjugate(R.perturb(np.eye(4), 0.01, 0.01, seed=2), F)
+        T, info = R.refine(moved, moved, T0, S=moved[:, :3])
+        assert info["failure"] == 0 and info["converged"], info
+        assert np.linalg.norm(R.back(T, F) - np.eye(4)) <= 1e-3
+
+
+def _g9_subsample(n=4000):
+    z = _fixture("g9_room.npz")
+    target = R.Target(z["target"])
+    S = R.voxel_downsample(z["source"][:, :3], 0.005 * target.diag)
+    S = S[np.random.default_rng(1).choice(len(S), n, replace=False)]
+    return z, target.diag, np.ascontiguousarray(S)
+
+
+def test_restatement_is_equivariant_under_changes_of_frame():
+    """g9 on a subsample of S, moved up to 500 D from the origin (and rotated): the far frames converge like the near one, to
+    the same T.  About the origin, the linearisation spins to the cap from ~16 D and fails from ~160 D."""
+    z, D, S = _g9_subsample()
+    T0, gt = R.perturb(z["groundtruth"], 0.05, 0.05, seed=1), z["groundtruth"]
+    base, info0 = R.refine(z["target"], None, T0, S=S)
+    assert info0["converged"] and np.linalg.norm(base - gt) <= 1e-3
+    for offset, rot in ((100.0, 0.0), (500.0, 0.0), (100.0, 0.4)):
+        F = R.frame(offset * D, rot)
+        T, info = R.refine(R.move(z["target"], F), None, R.conjugate(T0, F), S=R.move(S, F))
+        assert info["converged"] and info["failure"] == 0 and info["iterations"] < 60, (offset, rot, info)
+        assert np.linalg.norm(R.back(T, F) - gt) <= 1e-3
+        assert np.linalg.norm(R.back(T, F) - base) <= 1e-4, (offset, rot, np.linalg.norm(R.back(T, F) - base))
+
+
+def test_restatement_does_not_depend_on_the_units():
+    z, D, S = _g9_subsample()
+    T0, gt = R.perturb(z["groundtruth"], 0.05, 0.05, seed=1), z["groundtruth"]
+    _, info0 = R.refine(z["target"], None, T0, S=S)
+    F = np.eye(4)
+    for scale in (1000.0, 0.001):
+        T, info = R.refine(R.move(z["target"], F, scale), None, R.conjugate(T0, F, scale), S=R.move(S, F, scale))
+        assert info["converged"] and abs(info["iterations"] - info0["iterations"]) <= 2, (scale, info, info0)
+        assert np.linalg.norm(R.back(T, F, scale) - gt) <= 1e-3
 

@@ -2,6 +2,7 @@
 """bench.py -- scan-pair registrations/sec on synthetic 1M-point indoor scan pairs (BASELINE.json metric).
 
     python bench.py --gpus N --steps K --warmup W          (N = 1)
+    python bench.py --gpus N --steps K --warmup W --full   (the same, and every other leg after it)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 One "step" = one full registration(T, target, source) (code/PLADE/plade.h:58: plane extraction +
@@ -16,17 +17,25 @@ is one launch sequence).  Exactly K steps are timed: the groups after the lead-i
 that are left when K is not a multiple of S.  With the pipeline full on both sides (lead-in before, M untimed groups
 after), each timed group cost the pipeline the time it occupied its worker / M (Little's law); `ms_per_step` is the
 sum of that over the timed groups / K, `value` = 1000 / `ms_per_step` x ranks.
-Rank 0 prints ONE JSON line.  `resident_rank0` is the same pipeline on clouds already resident in HBM.
+Rank 0 prints ONE JSON line.
+A plain run does what that figure rests on and stops: it generates, uploads and pins the pairs, warms every context up on every
+group composition, times the K steps, writes --dump-outputs and prints the line.  Everything else the benchmark measures or
+checks runs after the timed steps and only with --full: every timed result against the pair registered alone and against the
+ground truth (`results_bit_identical_to_the_pair_alone_rank0`, `max_frobenius_vs_ground_truth_rank0`, `value_by_seed`),
+`resident_rank0` (the same pipeline on clouds already resident in HBM), `closed_form_mode_rank0`, `parity_vs_reference_solver`,
+`default_mode_rank0`, the latency of one registration alone, the roofline objects, the CPU baselines and `cli_end_to_end`.  A
+plain run's line holds null for those objects and `"full": false`; everything up to and including the timed steps is the same
+with and without --full.
 --dump-outputs DIR writes what the timed path returned for its last step (timed step K - 1, pair (K - 1) mod pairs of
 rank 0): DIR/T.npy (4 x 4 float32) and DIR/ok.npy (1.0 or 0.0, float32).
 
-Extra objects on the line:
+Extra objects on the line of a --full run, among others:
   roofline     -- the dominant kernel of the step, timed live after the timed region under the same load, in two legs:
                   HIP events on the launch stream around every launch (the loop launched kernel by kernel), and
                   the kernel's own device clock with the loop launched as in the timed region (one hipGraph per
                   iteration; `launch_path`): achieved = algorithmic bytes per launch / average
                   launch duration of the graph leg, peak = 8 TB/s HBM3E.
-  cpu_baseline -- the CPU path on this box's host cores, single thread like the reference: plane
+  cpu_baseline -- the CPU path on the host's cores, single thread like the reference: plane
                   extraction by the reference's own Schnabel RANSAC compiled from its sources
                   (oracle/_ref) when that library is present, everything after it by the oracle's
                   restatement (oracle/plade_oracle.cpp); bounded sample of the same workload.
@@ -523,6 +532,12 @@ def main():
     ap.add_argument("--no-cli", action="store_true", help="skip the CLI end-to-end leg (64-pair file_pairs.txt through plade_amd/PLADE)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the timed path returned for its last step to DIR/T.npy and DIR/ok.npy (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every other leg (each timed result against the pair registered alone, accuracy "
+                         "against the ground truth, resident and closed-form rates, parity with the oracle, the shipped default's success "
+                         "rate, latency, roofline, CPU baselines, the CLI end to end) and put their objects on the line.  Without it the "
+                         "run sets up, warms up, times --steps registrations, writes --dump-outputs and prints the line with those "
+                         "objects null; the options that size or skip a single leg only matter together with --full")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
@@ -608,7 +623,10 @@ def main():
     t_gen = time.perf_counter() - t_gen
     NP = len(pairs)
     # resident copies (plade_cloud_upload): context 0 holds every pair (the pair-alone comparison), the others the first NR
-    # (the resident leg and the background load of the roofline leg cycle over those)
+    # (the resident leg and the background load of the roofline leg cycle over those).  Only legs of --full register them after
+    # the warm-up, but a plain run uploads and warms them too (under a second): the timed steps then start from the same
+    # allocations and the same amount of GPU work behind them with and without --full.  (Nine alternating runs each of
+    # --steps 20 without / with them: 1.415 / 1.390 ms per step, single runs spread by +- 4 %.)
     NR = min(NP, 16)
     clouds = [[] for _ in range(M)]
     for k, (tg, sr, _) in enumerate(pairs):
@@ -678,7 +696,7 @@ def main():
         return sum(occ.values()) / M, steps, max(stamps) - ts
 
     # warm-up: every worker (context) registers every group composition once through BOTH entry points, so that no
-    # first-use allocation or graph capture falls into the timed region; the W warm-up steps the driver asks for are part
+    # first-use allocation or graph capture falls into the timed region; the W warm-up steps that --warmup asks for are part
     # of the lead-in of the pipelined run below
     n_comp = NP // S if NP % S == 0 else NP          # distinct group compositions of the cycle
     n_comp_r = NR // S if NR % S == 0 else NR
@@ -745,52 +763,55 @@ def main():
         elapsed, bracketed = (float(tmax[k].item()) for k in range(2))
         total_ok = int(okt.item())
 
-    # every registration of the same pair, whichever context ran it and whatever its partners in the group were, must
-    # return the same bits -- and the bits of the pair registered ALONE (one plade_registration_dev per distinct pair)
-    alone, alone_ms, work_by_seed = [], [], []
-    for k in range(NP):
-        t1 = time.perf_counter()
-        alone.append(step(k))
-        alone_ms.append((time.perf_counter() - t1) * 1e3)
-        st_k = ctx.stats()
-        work_by_seed.append({q: st_k.get(q) for q in ("ransac_iterations", "n_planes_tgt", "n_planes_src", "n_matches", "n_clusters",
-                                                        "n_candidates_verified")})
-    # service time by group composition: a group of S consecutive pairs occupied one of the M workers for occ seconds, i.e. it
-    # cost the pipeline occ / M of wall time = occ / (M * S) per registration (Little's law, as `value`); a shorter last
-    # group is a composition of its own and left out
-    by_comp = {}
-    for j, o in host_occ.items():
-        if j not in group_size:
-            by_comp.setdefault(j % max(n_comp, 1), []).append(o / (M * S) * 1e3)
-    comp_ms = sorted(float(np.mean(v)) for v in by_comp.values())
-    group_size.clear()      # the legs below run whole groups
+    # ---- everything below, up to the result line, is behind --full: a plain run has its figure by now
+    value_by_seed = identical = errs = None
+    if args.full:
+        # every registration of the same pair, whichever context ran it and whatever its partners in the group were, must
+        # return the same bits -- and the bits of the pair registered ALONE (one plade_registration_dev per distinct pair)
+        alone, alone_ms, work_by_seed = [], [], []
+        for k in range(NP):
+            t1 = time.perf_counter()
+            alone.append(step(k))
+            alone_ms.append((time.perf_counter() - t1) * 1e3)
+            st_k = ctx.stats()
+            work_by_seed.append({q: st_k.get(q) for q in ("ransac_iterations", "n_planes_tgt", "n_planes_src", "n_matches", "n_clusters",
+                                                            "n_candidates_verified")})
+        # service time by group composition: a group of S consecutive pairs occupied one of the M workers for occ seconds, i.e. it
+        # cost the pipeline occ / M of wall time = occ / (M * S) per registration (Little's law, as `value`); a shorter last
+        # group is a composition of its own and left out
+        by_comp = {}
+        for j, o in host_occ.items():
+            if j not in group_size:
+                by_comp.setdefault(j % max(n_comp, 1), []).append(o / (M * S) * 1e3)
+        comp_ms = sorted(float(np.mean(v)) for v in by_comp.values())
+        group_size.clear()      # the legs below run whole groups
 
-    def mmm(v):
-        v = sorted(float(x) for x in v if x is not None)
-        return {"min": v[0], "median": v[len(v) // 2], "max": v[-1]} if v else None
-    value_by_seed = {
-        "distinct_pairs_this_rank": NP, "seeds": [seeds[0], seeds[-1]],
-        "ms_per_registration_by_group_composition": mmm(comp_ms), "group_compositions": len(comp_ms),
-        "registrations_per_s_by_group_composition": ({"min": 1e3 / comp_ms[-1], "median": 1e3 / comp_ms[len(comp_ms) // 2], "max": 1e3 / comp_ms[0]}
-                                                     if comp_ms else None),
-        "pair_alone_latency_ms": mmm(alone_ms),
-        "ransac_iterations": mmm([w_["ransac_iterations"] for w_ in work_by_seed]),
-        "planes_target": mmm([w_["n_planes_tgt"] for w_ in work_by_seed]), "planes_source": mmm([w_["n_planes_src"] for w_ in work_by_seed]),
-        "descriptor_matches": mmm([w_["n_matches"] for w_ in work_by_seed]), "clusters": mmm([w_["n_clusters"] for w_ in work_by_seed]),
-        "candidates_verified": mmm([w_["n_candidates_verified"] for w_ in work_by_seed]),
-        "note": "every pair of the cycle is a different scene (seed); the timed steps run through them in input order, so `value` is the "
-                "batch average; by group composition = mean time a group of consecutive pairs occupied its worker / (groups in flight "
-                "x pairs per group); pair alone = one plade_registration_dev with sleeping host waits"}
-    identical = all(np.array_equal(results[k], alone[timed_ids[k] % NP][1]) and oks[k] == bool(alone[timed_ids[k] % NP][0])
-                    for k in range(len(results)))
-    ref_result = {k: alone[k][1] for k in range(NP)}
-    # accuracy of the timed registrations on this rank vs the generator's ground truth
-    errs = [float(np.linalg.norm(results[k].astype(np.float64) - pairs[timed_ids[k] % NP][2])) for k in range(len(results))]
+        def mmm(v):
+            v = sorted(float(x) for x in v if x is not None)
+            return {"min": v[0], "median": v[len(v) // 2], "max": v[-1]} if v else None
+        value_by_seed = {
+            "distinct_pairs_this_rank": NP, "seeds": [seeds[0], seeds[-1]],
+            "ms_per_registration_by_group_composition": mmm(comp_ms), "group_compositions": len(comp_ms),
+            "registrations_per_s_by_group_composition": ({"min": 1e3 / comp_ms[-1], "median": 1e3 / comp_ms[len(comp_ms) // 2], "max": 1e3 / comp_ms[0]}
+                                                         if comp_ms else None),
+            "pair_alone_latency_ms": mmm(alone_ms),
+            "ransac_iterations": mmm([w_["ransac_iterations"] for w_ in work_by_seed]),
+            "planes_target": mmm([w_["n_planes_tgt"] for w_ in work_by_seed]), "planes_source": mmm([w_["n_planes_src"] for w_ in work_by_seed]),
+            "descriptor_matches": mmm([w_["n_matches"] for w_ in work_by_seed]), "clusters": mmm([w_["n_clusters"] for w_ in work_by_seed]),
+            "candidates_verified": mmm([w_["n_candidates_verified"] for w_ in work_by_seed]),
+            "note": "every pair of the cycle is a different scene (seed); the timed steps run through them in input order, so `value` is the "
+                    "batch average; by group composition = mean time a group of consecutive pairs occupied its worker / (groups in flight "
+                    "x pairs per group); pair alone = one plade_registration_dev with sleeping host waits"}
+        identical = all(np.array_equal(results[k], alone[timed_ids[k] % NP][1]) and oks[k] == bool(alone[timed_ids[k] % NP][0])
+                        for k in range(len(results)))
+        ref_result = {k: alone[k][1] for k in range(NP)}
+        # accuracy of the timed registrations on this rank vs the generator's ground truth
+        errs = [float(np.linalg.norm(results[k].astype(np.float64) - pairs[timed_ids[k] % NP][2])) for k in range(len(results))]
 
     # ---- resident leg (clouds already in HBM, plade_registration_pairs_dev): the same pipeline without the uploads,
     #      reported next to `value`
     resident_leg = None
-    if args.resident_steps > 0:
+    if args.full and args.resident_steps > 0:
         r_groups = (args.resident_steps + S - 1) // S
         r_win, r_res, _ = run_pipeline(rgroup, 2 * M, r_groups)
         device_sync()
@@ -802,7 +823,7 @@ def main():
     # ---- the same host-cloud pipeline with the opt-in closed-form closest points (closest_point_mode = 0: fp64 formula instead
     #      of the reference's fp32 SVD solves): what the parity with the reference's solver costs
     closed_leg = None
-    if args.closed_form_steps > 0:
+    if args.full and args.closed_form_steps > 0:
         for c_ in ctxs:
             c_.set_params(closest_point_mode=0)
         s_groups = (args.closed_form_steps + S - 1) // S
@@ -819,7 +840,7 @@ def main():
                       "note": "plade_params.closest_point_mode = 0 on host clouds, same pipeline as `value`: NOT the reference's arithmetic (on "
                               "these axis-aligned scenes the reference's fp32 solves are ill-conditioned and the two modes part, DESIGN.md section 2)"}
     parity = None
-    if rank == 0 and world == 1 and not args.no_parity and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_parity and not args.no_cpu_baseline:
         try:
             parity = parity_vs_reference_solver(local_rank, pairs, seeds, _cpu_budget())
         except Exception as e:   # the oracle is test infrastructure: its absence must not hide the GPU number
@@ -832,7 +853,7 @@ def main():
 
     # ---- the library's shipped default on the same scenes: orient_normals = 0 (reference behaviour)
     default_mode = None
-    if rank == 0 and not args.no_default_mode:
+    if args.full and rank == 0 and not args.no_default_mode:
         dctx = plade_amd.Context(local_rank, host_wait=host_wait)          # plade_default_params: orient_normals = 0
         good, tried = 0, 0
         for k, (tg, sr, Tgt) in enumerate(pairs):
@@ -856,9 +877,9 @@ def main():
 
     # ---- roofline leg: one extra profiled step (HIP events on the ctx stream around every launch) ----
     roofline = roofline_sort = dominant = None
-    stage = {}
+    stage, stage_times = {}, {}
     latency_ms = latency_by_scene = None
-    if rank == 0:
+    if args.full and rank == 0:
         lat = []
         ctx.set_params(host_wait=0)   # alone, a spinning wait is the faster one
         for i in range(NP):   # one registration at a time, every scene of the cycle once: the latency figure is the MEDIAN over the scenes
@@ -1034,7 +1055,7 @@ def main():
             roofline["step_frac_of_hbm_peak"] = b_total / (elapsed / n_timed) / 1e9 / HBM_PEAK_GBS
             roofline["single_registration_frac_of_hbm_peak"] = b_total / (latency_ms * 1e-3) / 1e9 / HBM_PEAK_GBS
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             sample = []
             for (tg, sr, Tgt) in pairs[:6]:       # >= 4 distinct seeds
@@ -1044,12 +1065,12 @@ def main():
             cpu = {"value": None, "unit": "registrations/s", "cores": 1, "kind": "port", "sample": f"unavailable: {e}"}
 
     cpu_batch = cli_e2e = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             cpu_batch = cpu_baseline_batch(pairs[:16])
         except Exception as e:
             cpu_batch = {"value": None, "sample": f"unavailable: {e}"}
-    if rank == 0 and world == 1 and not args.no_cli:
+    if args.full and rank == 0 and world == 1 and not args.no_cli:
         try:
             cli_e2e = cli_end_to_end(pairs[:64])
         except Exception as e:
@@ -1066,6 +1087,7 @@ def main():
             "steps": n_timed,
             "warmup": args.warmup,
             "requested_steps": args.steps,
+            "full": args.full,
             "ms_per_step": elapsed / n_timed * 1e3,
             "higher_is_better": True,
             "scaling": "weak",
@@ -1093,7 +1115,7 @@ def main():
             "single_registration_latency_by_scene_ms": latency_by_scene,
             "registrations_timed": total,
             "registrations_ok": total_ok,
-            "results_bit_identical_to_the_pair_alone_rank0": bool(identical),
+            "results_bit_identical_to_the_pair_alone_rank0": identical,
             "value_by_seed": value_by_seed,
             "parity_vs_reference_solver": parity,
             "closed_form_mode_rank0": closed_leg,

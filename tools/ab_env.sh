@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B of environment switches of ONE build on one box: AB_VARIANTS="name:ENV=1 name2:X=1,Y=2", alternating, AB_REPS times
 R=${GRAFT_REPO_ROOT:-/root/repo}; cd $R
-run() { name=$1; shift; env "$@" python bench.py --pairs ${AB_PAIRS:-32} --no-cpu-baseline --no-cli --no-default-mode --closed-form-steps 0 --resident-steps 0 --profiled-steps 0 --no-parity $BENCH_ARGS 2>&1 | python -c "
+run() { name=$1; shift; env "$@" python bench.py --full --pairs ${AB_PAIRS:-32} --no-cpu-baseline --no-cli --no-default-mode --closed-form-steps 0 --resident-steps 0 --profiled-steps 0 --no-parity $BENCH_ARGS 2>&1 | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

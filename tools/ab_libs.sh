@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}; cd $R
 cp plade_amd/libplade_hip.so gpurun_ab/.current.so
 for rep in $(seq 1 ${AB_REPS:-3}); do for v in ${AB_LIBS:-old new}; do
   cp gpurun_ab/$v.so plade_amd/libplade_hip.so
-  python bench.py --pairs ${AB_PAIRS:-32} --no-cpu-baseline --no-cli --no-default-mode --closed-form-steps ${AB_CLOSED:-0} --resident-steps 0 --profiled-steps 0 --no-parity $BENCH_ARGS 2>&1 | python -c "
+  python bench.py --full --pairs ${AB_PAIRS:-32} --no-cpu-baseline --no-cli --no-default-mode --closed-form-steps ${AB_CLOSED:-0} --resident-steps 0 --profiled-steps 0 --no-parity $BENCH_ARGS 2>&1 | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

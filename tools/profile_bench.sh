@@ -10,9 +10,9 @@ TAG=${1:-r5}
 mkdir -p $O
 cd $R
 if [ -z "${ONLY_PROF:-}" ]; then
-timeout -k 10 900 python bench.py > $O/bench_$TAG.json 2> $O/bench_$TAG.err
+timeout -k 10 900 python bench.py --full > $O/bench_$TAG.json 2> $O/bench_$TAG.err
 tail -c 600 $O/bench_$TAG.json
-timeout -k 10 900 python bench.py --steps 20 --warmup 5 > $O/bench_${TAG}_driver.json 2> $O/bench_${TAG}_driver.err
+timeout -k 10 900 python bench.py --steps 20 --warmup 5 --full > $O/bench_${TAG}_driver.json 2> $O/bench_${TAG}_driver.err
 python -c "import json; d=json.load(open('$O/bench_${TAG}_driver.json')); print('driver command:', d['value'], d['ms_per_step'], d['resident_rank0']['value'], d['default_mode_rank0'], d['cpu_baseline']['value'])"
 fi
 cd /tmp && export TMPDIR=/tmp

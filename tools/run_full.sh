@@ -3,7 +3,7 @@
 O=gpurun_out; mkdir -p $O
 timeout 3000 python -m pytest tests -x -q -m gpu > $O/full_tests.log 2>&1; echo "gpu tests rc=$?"; tail -4 $O/full_tests.log
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2
-timeout 900 python bench.py --steps 20 --warmup 5 > $O/full_bench.json 2> $O/full_bench.err; echo "bench rc=$?"
+timeout 900 python bench.py --steps 20 --warmup 5 --full > $O/full_bench.json 2> $O/full_bench.err; echo "bench rc=$?"
 python - <<'PY'
 import json
 d=json.load(open('gpurun_out/full_bench.json'))

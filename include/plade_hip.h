@@ -431,6 +431,54 @@ int plade_cloud_distances(plade_ctx *ctx, const float *tgt_pos_nrm, uint32_t n_t
 int plade_cloud_distances_dev(plade_ctx *ctx, plade_cloud *tgt, plade_cloud *src, const float *T16, float max_dist,
                               int32_t *idx_out, float *d2_out, float *plane_out, plade_distance_summary *summary);
 
+/* ---- outlier removal: the step a chain on a raw scan starts with (no reference counterpart; PCL, Open3D and CloudCompare ship
+ * both filters) ---------------------------------------------------------------------------------------------------------------
+ * Semantics (plade_amd/csrc/outliers.h).  Input: n points, rows of `stride` >= 3 floats, x y z first, all
+ * coordinates finite.  d(i, j) = the fp32 FLANN L2 of (p_i, p_j), ((dx*dx + dy*dy) + dz*dz).
+ *   statistical  k in [1, 64], alpha >= 0.  Neighbours of i: the k_eff = min(k, n - 1) points j != i with the smallest keys
+ *                (d(i, j), j); i is left out by its index, so a duplicate of i is a neighbour at distance 0.  m_i = (the sum of
+ *                sqrt(double(d(i, j))) in ascending key order) / k_eff in fp64 (n = 1: 0).  mu = sum m_i / n, sigma =
+ *                sqrt(sum (m_i - mu)^2 / (n - 1)) in a second pass (n = 1: 0), both fp64 in a fixed order of the original index:
+ *                the same bits on every run.  Point i is kept when m_i <= mu + alpha * sigma (fp64).
+ *   radius       radius > 0, min_neighbours >= 1.  c_i = the number of j != i with d(i, j) < (float)radius * (float)radius;
+ *                point i is kept when c_i >= min_neighbours.
+ *   output       each array may be NULL.  keep_out: n bytes 0 / 1; kept_index_out: the kept original indices, ascending (room
+ *                for n); rows_out: the kept rows in that order, every float copied bit for bit (room for n rows; may be `rows`
+ *                itself); mean_dist_out: m_i (n doubles, statistical mode only); count_out: c_i (n uint32, radius mode only --
+ *                without it a point's count may stop at min_neighbours); summary: n, kept, mu, sigma, threshold (NaN in radius
+ *                mode).  The result depends on the point set and the parameters only.
+ * Errors: PLADE_EINVAL for n = 0, stride < 3, a non-finite coordinate, k outside [1, 64], alpha negative or not finite, radius
+ * <= 0 or not finite, min_neighbours < 1; the context stays usable.  A filter that keeps nothing is PLADE_OK with kept = 0.
+ * plade_stats_get then reports outliers_grid_s, outliers_search_s, outliers_reduce_s (mu, sigma, flags), outliers_compact_s
+ * (scan, kept list and row gather; HIP events on the context's stream), outliers_grid_builds, outliers_ring_queries (points the
+ * 27-cell search could not finish) and outliers_kept. */
+#define PLADE_OUTLIER_STATISTICAL 0
+#define PLADE_OUTLIER_RADIUS 1
+typedef struct plade_outlier_params {
+    int32_t mode;                /* PLADE_OUTLIER_STATISTICAL or PLADE_OUTLIER_RADIUS */
+    int32_t k;                   /* statistical: neighbours, 1..64 */
+    double alpha;                /* statistical: the threshold is mu + alpha sigma */
+    double radius;               /* radius mode: must be set (> 0) */
+    int32_t min_neighbours;      /* radius mode: >= 1 */
+    int32_t reserved;            /* 0 */
+} plade_outlier_params;
+typedef struct plade_outlier_summary {
+    uint64_t n, kept;
+    double mu, sigma, threshold; /* NaN in radius mode */
+} plade_outlier_summary;
+/* The defaults: statistical mode, k = 16, alpha = 1.0, radius = 0 (unset), min_neighbours = 1.  Needs no GPU. */
+void plade_outlier_default_params(plade_outlier_params *p);
+/* params NULL: the defaults. */
+int plade_filter_outliers(plade_ctx *ctx, const float *rows, uint32_t n, uint32_t stride, const plade_outlier_params *params,
+                          uint8_t *keep_out, uint32_t *kept_index_out, float *rows_out, double *mean_dist_out, uint32_t *count_out,
+                          plade_outlier_summary *summary);
+/* The same on a resident cloud (plade_cloud_upload / plade_cloud_upload_xyz; rows x y z nx ny nz) into a NEW resident cloud: the
+ * point data makes no host round trip.  The same keep, kept_index and summary bits as plade_filter_outliers on the cloud's rows.
+ * PLADE_EFAIL (summary filled, *out NULL) when nothing is kept: a resident cloud has no empty form.  Free both clouds with
+ * plade_cloud_free. */
+int plade_cloud_filter_outliers_dev(plade_ctx *ctx, plade_cloud *cloud, const plade_outlier_params *params, plade_cloud **out,
+                                    uint8_t *keep_out, uint32_t *kept_index_out, plade_outlier_summary *summary);
+
 /* ---- instrumentation ---------------------------------------------------------------------- */
 /* Named intermediates of the last registration (when params.dump != 0). Returns 0 if found;
  * the pointer stays valid until the next call on this ctx. */

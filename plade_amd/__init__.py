@@ -29,6 +29,7 @@ ABI_SYMBOLS = [
     "plade_estimate_normals", "plade_cloud_upload_xyz", "plade_ply_read_points",
     "plade_icp_default_params", "plade_refine_icp", "plade_refine_icp_dev", "plade_icp_linearize",
     "plade_cloud_distances", "plade_cloud_distances_dev",
+    "plade_outlier_default_params", "plade_filter_outliers", "plade_cloud_filter_outliers_dev",
 ]
 
 
@@ -65,6 +66,21 @@ class DistanceSummary(C.Structure):
     _fields_ = [("n", C.c_uint64), ("count", C.c_uint64), ("plane_count", C.c_uint64), ("fitness", C.c_double), ("rmse", C.c_double),
                 ("mean", C.c_double), ("max", C.c_double), ("plane_rmse", C.c_double)]
 
+
+class OutlierParams(C.Structure):
+    """plade_outlier_params: mode (PLADE_OUTLIER_STATISTICAL / PLADE_OUTLIER_RADIUS), k and alpha of the statistical filter, radius
+    and min_neighbours of the radius filter."""
+    _fields_ = [("mode", C.c_int32), ("k", C.c_int32), ("alpha", C.c_double), ("radius", C.c_double), ("min_neighbours", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class OutlierSummary(C.Structure):
+    """plade_outlier_summary: n, kept, and mu, sigma, threshold = mu + alpha sigma of the statistical filter (NaN in radius mode)."""
+    _fields_ = [("n", C.c_uint64), ("kept", C.c_uint64), ("mu", C.c_double), ("sigma", C.c_double), ("threshold", C.c_double)]
+
+
+PLADE_OUTLIER_STATISTICAL, PLADE_OUTLIER_RADIUS = 0, 1
+OUTLIER_MODES = {"statistical": PLADE_OUTLIER_STATISTICAL, "radius": PLADE_OUTLIER_RADIUS}
 
 PLADE_ICP_TOO_FEW, PLADE_ICP_DEGENERATE = 1, 2
 ICP_FAILURES = {0: None, PLADE_ICP_TOO_FEW: "too few correspondences", PLADE_ICP_DEGENERATE: "degenerate"}
@@ -133,6 +149,9 @@ def load_library(path=LIB_PATH):
     sig("plade_icp_linearize", argtypes=[p, p, u32, p, u32, u32, p, p, f, p, p])
     sig("plade_cloud_distances", argtypes=[p, p, u32, p, u32, u32, p, f, p, p, p, C.POINTER(DistanceSummary)])
     sig("plade_cloud_distances_dev", argtypes=[p, p, p, p, f, p, p, p, C.POINTER(DistanceSummary)])
+    sig("plade_outlier_default_params", argtypes=[C.POINTER(OutlierParams)], restype=None)
+    sig("plade_filter_outliers", argtypes=[p, p, u32, u32, C.POINTER(OutlierParams), p, p, p, p, p, C.POINTER(OutlierSummary)])
+    sig("plade_cloud_filter_outliers_dev", argtypes=[p, p, C.POINTER(OutlierParams), C.POINTER(p), p, p, C.POINTER(OutlierSummary)])
     sig("plade_sort_segments", argtypes=[p, p, p, p, u32, C.c_int, p, p])
     sig("plade_set_candidate_shard", argtypes=[p, u32, u32, u32, EXCHANGE_FN, p])
     sig("plade_registration_minsupport", argtypes=[p, p, u32, p, u32, i32, i32, p])
@@ -203,6 +222,36 @@ def icp_default_params():
     prm = IcpParams()
     load_library().plade_icp_default_params(C.byref(prm))
     return {k: getattr(prm, k) for k, _ in IcpParams._fields_}
+
+
+def outlier_default_params():
+    """plade_outlier_default_params (pure: needs no GPU) as a dict of the plade_outlier_params fields."""
+    prm = OutlierParams()
+    load_library().plade_outlier_default_params(C.byref(prm))
+    return {k: getattr(prm, k) for k, _ in OutlierParams._fields_ if k != "reserved"}
+
+
+def _outlier_params(mode, k, alpha, radius, min_neighbours):
+    prm = OutlierParams()
+    load_library().plade_outlier_default_params(C.byref(prm))
+    if mode not in OUTLIER_MODES:
+        raise ValueError(f"mode: 'statistical' or 'radius', got {mode!r}")
+    prm.mode = OUTLIER_MODES[mode]
+    if k is not None:
+        prm.k = int(k)
+    if alpha is not None:
+        prm.alpha = float(alpha)
+    if radius is not None:
+        prm.radius = float(radius)
+    if min_neighbours is not None:
+        prm.min_neighbours = int(min_neighbours)
+    return prm
+
+
+def _outlier_info(summ, keep):
+    info = {k: getattr(summ, k) for k, _ in OutlierSummary._fields_}
+    info["keep"] = keep.view(np.bool_)
+    return info
 
 
 def _icp_params(kw):
@@ -737,6 +786,45 @@ class Context:
         """Registration quality of T (source -> target) at max_dist: the summary dict of cloud_distances, with no per-point
         outputs (fitness = the share of source points within max_dist of the target, rmse of their distances, ...)."""
         return self.cloud_distances(tgt, src, max_dist, T=T, per_point=False)[3]
+
+    # ---- outlier removal -------------------------------------------------------------------------
+    def remove_outliers(self, points, mode="statistical", k=None, alpha=None, radius=None, min_neighbours=None, per_point=True):
+        """plade_filter_outliers: the statistical (k nearest neighbours, threshold mu + alpha sigma of their mean distances;
+        defaults k = 16, alpha = 1) or radius (at least min_neighbours other points closer than radius) outlier filter of an
+        (N, >= 3) float32 array whose first three columns are x y z.  Returns (filtered, kept_index, info): the kept rows in
+        their original order with every column copied bit for bit, their original indices (uint32, ascending), and a dict with
+        n, kept, mu, sigma, threshold (NaN in radius mode), keep (N bools) and -- with per_point -- mean_dist (N float64,
+        statistical) or count (N uint32, radius; without per_point a count may stop at min_neighbours)."""
+        a, n, stride = _xyz_view(points)
+        prm = _outlier_params(mode, k, alpha, radius, min_neighbours)
+        stat = prm.mode == PLADE_OUTLIER_STATISTICAL
+        keep = np.zeros(n, np.uint8)
+        kept = np.empty(n, np.uint32)
+        rows = np.empty((n, stride), np.float32)
+        mean = np.empty(n, np.float64) if per_point and stat else None
+        count = np.empty(n, np.uint32) if per_point and not stat else None
+        summ = OutlierSummary()
+        self._check(self.L.plade_filter_outliers(self.h, _ptr(a), n, stride, C.byref(prm), _ptr(keep), _ptr(kept), _ptr(rows),
+                                                 _ptr(mean), _ptr(count), C.byref(summ)))
+        info = _outlier_info(summ, keep)
+        if mean is not None:
+            info["mean_dist"] = mean
+        if count is not None:
+            info["count"] = count
+        return rows[:summ.kept].copy(), kept[:summ.kept].copy(), info
+
+    def remove_outliers_dev(self, cloud, mode="statistical", k=None, alpha=None, radius=None, min_neighbours=None, info=False):
+        """plade_cloud_filter_outliers_dev: remove_outliers on a resident cloud (upload, upload_xyz) into a new resident Cloud;
+        the point data makes no host round trip.  With info also (kept_index, info dict) as remove_outliers gives them (no
+        per-point values): the same bits.  Raises PladeError (PLADE_EFAIL) when nothing is kept."""
+        prm = _outlier_params(mode, k, alpha, radius, min_neighbours)
+        keep = np.zeros(cloud.n, np.uint8) if info else None
+        kept = np.empty(cloud.n, np.uint32) if info else None
+        summ = OutlierSummary()
+        h = C.c_void_p()
+        self._check(self.L.plade_cloud_filter_outliers_dev(self.h, cloud.h, C.byref(prm), C.byref(h), _ptr(keep), _ptr(kept), C.byref(summ)))
+        out = Cloud(self, None, handle=(int(summ.kept), h))
+        return (out, kept[:summ.kept].copy(), _outlier_info(summ, keep)) if info else out
 
     def pin(self, arr):
         """Page-lock a C-contiguous float32 array the caller keeps alive (plade_host_pin); registration() calls that are

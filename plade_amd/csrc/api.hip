@@ -4,6 +4,7 @@
 #include "exact_sort.h"
 #include "icp.h"
 #include "normals.h"
+#include "outliers.h"
 #include "pipeline.h"
 #include "ransac.h"
 
@@ -137,6 +138,7 @@ extern "C" void plade_ctx_destroy(plade_ctx *ctx) {
     if (ctx->normals_work) plade::normals_work_destroy(ctx->normals_work);
     if (ctx->icp_work) plade::icp_work_destroy(ctx->icp_work);
     if (ctx->dist_work) plade::dist_work_destroy(ctx->dist_work);
+    if (ctx->outlier_work) plade::outlier_work_destroy(ctx->outlier_work);
     (void)hipStreamDestroy(ctx->stream);
     if (ctx->pf.stream) { (void)hipStreamSynchronize(ctx->pf.stream); (void)hipStreamDestroy(ctx->pf.stream); }
     delete ctx;

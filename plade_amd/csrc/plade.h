@@ -70,6 +70,19 @@ struct RegistrationQuality {
 bool evaluate_registration(const Eigen::Matrix4f &transformation, pcl::PointCloud<pcl::PointNormal>::Ptr target_cloud,
                            pcl::PointCloud<pcl::PointNormal>::Ptr source_cloud, float max_dist, RegistrationQuality &out);
 
+/** Outlier removal (no counterpart in the reference): the fields of plade_outlier_summary (include/plade_hip.h). */
+struct OutlierRemoval {
+    uint64_t n = 0, kept = 0;                  // points in, points kept
+    double mu = 0, sigma = 0, threshold = 0;   // of the mean neighbour distances; threshold = mu + alpha sigma
+};
+/** Statistical outlier filter on the GPU (plade_filter_outliers): a point is kept when the mean distance to its k (1..64) nearest
+ *  neighbours is at most mu + alpha sigma of those means over the cloud.  `filtered` receives the kept points in their original
+ *  order, coordinates and normals copied bit for bit (it may be *cloud).  false: invalid input or no GPU; a message is printed and
+ *  `filtered` is unchanged.  The CLI and the file overload of registration() filter both clouds of a pair after reading them, and
+ *  before PLADE_ESTIMATE_NORMALS, when PLADE_REMOVE_OUTLIERS=<k>[,<alpha>] is set, and print one line per cloud. */
+bool remove_outliers(pcl::PointCloud<pcl::PointNormal>::Ptr cloud, pcl::PointCloud<pcl::PointNormal> &filtered, int k = 16,
+                     double alpha = 1.0, OutlierRemoval *info = nullptr);
+
 /** Batch extension (no counterpart in the reference, whose batch mode is a plain loop of the file overload above,
  *  code/PLADE/main.cpp:122-148): `count` (1..registration_group_max = PLADE_GROUP_MAX) consecutive pairs of the list as ONE group.  Every pair gets the result,
  *  the messages and the identity-on-failure of the file overload -- its transformation is bit for bit the one the file overload

@@ -199,6 +199,66 @@ void evaluate_line(plade_ctx *ctx, const float *T16, const float *tg, size_t n_t
     con_out() << b << std::endl;
 }
 
+// PLADE_REMOVE_OUTLIERS=<k>[,<alpha>] (opt-in, 0 / unset = off): both clouds of a pair pass the statistical outlier filter on the
+// GPU (plade_filter_outliers: k nearest neighbours, threshold mu + alpha sigma, alpha 1 when not given) after they are read and
+// before PLADE_ESTIMATE_NORMALS; one console line per cloud.  A value that does not parse (k not an integer in [1, 64], alpha
+// negative or not finite, anything behind them) prints one warning and filters nothing; unset, nothing changes.
+struct OutlierSwitch { int k = 0; double alpha = 1.0; };
+const OutlierSwitch &remove_outliers_switch() {
+    static const OutlierSwitch sw = [] {
+        OutlierSwitch v;
+        const char *w = getenv("PLADE_REMOVE_OUTLIERS");
+        if (!w) return v;
+        char *end = nullptr;
+        const long k = strtol(w, &end, 10);
+        bool ok = end != w && k >= 0 && k <= 64;
+        double alpha = 1.0;
+        if (ok && *end == ',') {
+            const char *a = end + 1;
+            alpha = strtod(a, &end);
+            ok = end != a && std::isfinite(alpha) && alpha >= 0.0;
+        }
+        if (!ok || *end != '\0') {
+            std::cerr << "warning: PLADE_REMOVE_OUTLIERS=" << w << " is not <k>[,<alpha>] with k in [1, 64] and alpha >= 0; no outlier removal"
+                      << std::endl;
+            return v;
+        }
+        v.k = (int)k; v.alpha = alpha;
+        return v;
+    }();
+    return sw;
+}
+// the rows of an x y z nx ny nz array that pass the filter, in place (the normal columns, NaN included, keep their bits)
+bool filter_packed(plade_ctx *ctx, std::vector<float> &buf, int k, double alpha, plade_outlier_summary &s) {
+    plade_outlier_params prm;
+    plade_outlier_default_params(&prm);
+    prm.k = k; prm.alpha = alpha;
+    const size_t n = buf.size() / 6;
+    trace("outliers: filtering");
+    // (in place: the upload of the rows precedes the read-back of the kept ones on the context's stream)
+    const int rc = plade_filter_outliers(ctx, buf.data(), (uint32_t)n, 6, &prm, nullptr, nullptr, buf.data(), nullptr, nullptr, &s);
+    trace("outliers: done");
+    if (rc != PLADE_OK) {
+        con_err() << "outlier removal failed: " << plade_last_error(ctx) << std::endl;
+        return false;
+    }
+    buf.resize((size_t)s.kept * 6);
+    return true;
+}
+bool remove_outliers_in_place(std::vector<float> &buf) {
+    const OutlierSwitch &sw = remove_outliers_switch();
+    if (!sw.k || buf.empty()) return true;
+    plade_ctx *ctx = context();
+    if (!ctx) return false;
+    plade_outlier_summary s;
+    if (!filter_packed(ctx, buf, sw.k, sw.alpha, s)) return false;
+    char b[200];
+    snprintf(b, sizeof(b), "outlier removal: kept %llu of %llu points (threshold %.6g)", (unsigned long long)s.kept,
+             (unsigned long long)s.n, s.threshold);
+    con_out() << b << std::endl;
+    return true;
+}
+
 std::string extension(const std::string &file_name) {  // util.cpp:525-531
     std::string::size_type dot = file_name.find_last_of('.');
     std::string::size_type slash = file_name.find_last_of("/\\");
@@ -345,7 +405,8 @@ bool load_packed(const std::string &file_name, std::vector<float> &buf) {
         return false;
     }
     for (auto &w : warnings) con_out() << w << std::endl;
-    if (estimate && !estimate_in_place(file_name, buf)) return false;
+    if (!remove_outliers_in_place(buf)) return false;
+    if (estimate && !buf.empty() && !estimate_in_place(file_name, buf)) return false;
     return !buf.empty();
 }
 
@@ -441,6 +502,8 @@ void registration_group(size_t count, Eigen::Matrix<float, 4, 4> *transformation
     auto report = [&](const Loaded &l, const std::string &file, std::vector<float> &buf) {   // load_packed's messages
         if (!l.ok && !l.err.empty()) con_err() << l.err << std::endl;
         if (l.ok || l.err.empty()) for (auto &w : l.warnings) con_out() << w << std::endl;
+        if (l.ok && !remove_outliers_in_place(buf)) return false;
+        if (l.ok && buf.empty()) return false;
         if (l.ok && l.estimate) return estimate_in_place(file, buf);
         return l.ok;
     };
@@ -527,6 +590,23 @@ bool evaluate_registration(const Eigen::Matrix4f &transformation, pcl::PointClou
     return true;
 }
 
+// outlier removal: see plade.h
+bool remove_outliers(pcl::PointCloud<pcl::PointNormal>::Ptr cloud, pcl::PointCloud<pcl::PointNormal> &filtered, int k, double alpha,
+                     OutlierRemoval *info) {
+    plade_ctx *ctx = context();
+    if (!ctx) return false;
+    std::vector<float> buf = flatten(*cloud);
+    plade_outlier_summary s;
+    if (!filter_packed(ctx, buf, k, alpha, s)) return false;
+    filtered.resize((size_t)s.kept);
+    for (size_t i = 0; i < (size_t)s.kept; ++i) {
+        const float *p = &buf[6 * i];
+        filtered.at(i) = pcl::PointNormal(p[0], p[1], p[2], p[3], p[4], p[5]);
+    }
+    if (info) { info->n = s.n; info->kept = s.kept; info->mu = s.mu; info->sigma = s.sigma; info->threshold = s.threshold; }
+    return true;
+}
+
 bool load_ply_cloud(const std::string &file_name, pcl::PointCloud<pcl::PointNormal> &cloud) {
     std::vector<float> pos_nrm;
     std::string err;
@@ -537,7 +617,8 @@ bool load_ply_cloud(const std::string &file_name, pcl::PointCloud<pcl::PointNorm
         return false;
     }
     for (auto &w : warnings) con_out() << w << std::endl;
-    if (estimate && !estimate_in_place(file_name, pos_nrm)) return false;
+    if (!remove_outliers_in_place(pos_nrm)) return false;
+    if (estimate && !pos_nrm.empty() && !estimate_in_place(file_name, pos_nrm)) return false;
     const size_t n = pos_nrm.size() / 6;
     cloud.resize(n);
     for (size_t i = 0; i < n; ++i) {

@@ -479,6 +479,42 @@ int plade_filter_outliers(plade_ctx *ctx, const float *rows, uint32_t n, uint32_
 int plade_cloud_filter_outliers_dev(plade_ctx *ctx, plade_cloud *cloud, const plade_outlier_params *params, plade_cloud **out,
                                     uint8_t *keep_out, uint32_t *kept_index_out, plade_outlier_summary *summary);
 
+/* ---- merging registered clouds: the step a scan-to-scan chain ends with (no reference counterpart) -----------------------------
+ * Semantics (plade_amd/csrc/merge.h).  k clouds, 1 <= k <= 16; cloud c: n_c >= 1 rows x y z nx ny nz with
+ * finite coordinates (the normals may be NaN); T: k row-major fp32 4 x 4 matrices, cloud c -> the output frame (NULL: identities,
+ * which go through the same arithmetic); leaf >= 0 (fp32).
+ *   transform  p' = ((r0 x + r1 y) + r2 z) + t and n' = (r0 nx + r1 ny) + r2 nz, row by row in fp32 (the match rule of ICP and
+ *              distances).  n' gets no translation and is not renormalised; a non-finite normal stays non-finite.
+ *   leaf = 0   the output is the transformed concatenation in (cloud, index) order: sum n_c rows, count = 1, mask = 1 << c.
+ *   leaf > 0   inv = 1.f / leaf; voxel of p' = floor(p' * inv) per axis in fp32 minus floor(min * inv) of the bounding box of all
+ *              p' (the key of plade_voxel_downsample); one row per occupied voxel in ascending (k, j, i).  Position: the fp64 sum of
+ *              double(p') over the voxel's points, added one after the other in ascending (cloud, index) order, divided by the
+ *              count in fp64, rounded to fp32.  Normal: s = the fp64 sum of double(n') in the same order over the points with a
+ *              finite n'; q = (sx sx + sy sy) + sz sz; three NaNs when there is no such point or q == 0, else fp32(s / sqrt(q)).
+ *              A plain sum, as PCL's normal accumulator: OPPOSITE NORMALS CANCEL (orient the scans consistently first).
+ *   per row    count (uint32): the voxel's points; mask (uint32): bit c set when cloud c contributed.
+ *   summary    n_in = sum n_c, n_out = rows, n_shared = rows whose mask has two or more bits, max_count = the largest count.
+ * The result depends on the inputs only (not on launch shapes), is the same bits for host and resident clouds and on every run;
+ * there are no floating-point atomics.  out_rows (6 floats per row), out_count and out_mask hold sum n_c rows; out_count and
+ * out_mask may be NULL.
+ * Errors: PLADE_EINVAL for k outside [1, 16], a NULL cloud, n_c = 0, a non-finite coordinate or T, leaf negative or not finite;
+ * PLADE_ELIMIT for more than 2^18 leaves along an axis or sum n_c >= 2^31; the context stays usable.  plade_stats_get then reports
+ * merge_transform_s, merge_sort_s (keys + sort), merge_runs_s, merge_fuse_s (HIP events on the context's stream) and merge_rows. */
+typedef struct plade_merge_summary {
+    uint64_t n_in, n_out, n_shared;
+    uint32_t max_count;
+    uint32_t reserved;           /* 0 */
+} plade_merge_summary;
+int plade_merge_clouds(plade_ctx *ctx, uint32_t k, const float *const *clouds, const uint32_t *n, const float *T /* k x 16 or NULL */,
+                       float leaf, float *out_rows, uint32_t *out_count, uint32_t *out_mask, plade_merge_summary *summary);
+/* The same on resident clouds into a NEW resident cloud (free it with plade_cloud_free): the point data makes no host round trip;
+ * out_count / out_mask are host arrays of sum n_c entries or NULL.  The merged cloud is a resident cloud like any other. */
+int plade_merge_clouds_dev(plade_ctx *ctx, uint32_t k, plade_cloud *const *clouds, const float *T /* k x 16 or NULL */, float leaf,
+                           plade_cloud **out, uint32_t *out_count, uint32_t *out_mask, plade_merge_summary *summary);
+/* Reads a resident cloud back, whichever call made it: *n = its rows; rows (x y z nx ny nz, room for capacity_rows rows) may be
+ * NULL to ask for n only.  PLADE_ECAP when capacity_rows < n. */
+int plade_cloud_download(plade_ctx *ctx, const plade_cloud *cloud, float *rows, uint32_t capacity_rows, uint32_t *n);
+
 /* ---- instrumentation ---------------------------------------------------------------------- */
 /* Named intermediates of the last registration (when params.dump != 0). Returns 0 if found;
  * the pointer stays valid until the next call on this ctx. */

@@ -30,6 +30,7 @@ ABI_SYMBOLS = [
     "plade_icp_default_params", "plade_refine_icp", "plade_refine_icp_dev", "plade_icp_linearize",
     "plade_cloud_distances", "plade_cloud_distances_dev",
     "plade_outlier_default_params", "plade_filter_outliers", "plade_cloud_filter_outliers_dev",
+    "plade_merge_clouds", "plade_merge_clouds_dev", "plade_cloud_download",
 ]
 
 
@@ -77,6 +78,12 @@ class OutlierParams(C.Structure):
 class OutlierSummary(C.Structure):
     """plade_outlier_summary: n, kept, and mu, sigma, threshold = mu + alpha sigma of the statistical filter (NaN in radius mode)."""
     _fields_ = [("n", C.c_uint64), ("kept", C.c_uint64), ("mu", C.c_double), ("sigma", C.c_double), ("threshold", C.c_double)]
+
+
+class MergeSummary(C.Structure):
+    """plade_merge_summary: points in, rows out, rows seen by two or more clouds, the largest per-voxel count."""
+    _fields_ = [("n_in", C.c_uint64), ("n_out", C.c_uint64), ("n_shared", C.c_uint64), ("max_count", C.c_uint32),
+                ("reserved", C.c_uint32)]
 
 
 PLADE_OUTLIER_STATISTICAL, PLADE_OUTLIER_RADIUS = 0, 1
@@ -152,6 +159,9 @@ def load_library(path=LIB_PATH):
     sig("plade_outlier_default_params", argtypes=[C.POINTER(OutlierParams)], restype=None)
     sig("plade_filter_outliers", argtypes=[p, p, u32, u32, C.POINTER(OutlierParams), p, p, p, p, p, C.POINTER(OutlierSummary)])
     sig("plade_cloud_filter_outliers_dev", argtypes=[p, p, C.POINTER(OutlierParams), C.POINTER(p), p, p, C.POINTER(OutlierSummary)])
+    sig("plade_merge_clouds", argtypes=[p, u32, p, p, p, f, p, p, p, C.POINTER(MergeSummary)])
+    sig("plade_merge_clouds_dev", argtypes=[p, u32, p, p, f, C.POINTER(p), p, p, C.POINTER(MergeSummary)])
+    sig("plade_cloud_download", argtypes=[p, p, p, u32, C.POINTER(u32)])
     sig("plade_sort_segments", argtypes=[p, p, p, p, u32, C.c_int, p, p])
     sig("plade_set_candidate_shard", argtypes=[p, u32, u32, u32, EXCHANGE_FN, p])
     sig("plade_registration_minsupport", argtypes=[p, p, u32, p, u32, i32, i32, p])
@@ -356,6 +366,14 @@ class Cloud:
         self.n = len(a)
         self.h = C.c_void_p()
         ctx._check(ctx.L.plade_cloud_upload(ctx.h, _ptr(a), self.n, C.byref(self.h)))
+
+    def download(self):
+        """plade_cloud_download: the cloud's rows x y z nx ny nz as an (N, 6) float32 array, whichever call made the cloud."""
+        n = C.c_uint32(0)
+        self.ctx._check(self.ctx.L.plade_cloud_download(self.ctx.h, self.h, None, 0, C.byref(n)))
+        rows = np.empty((n.value, 6), np.float32)
+        self.ctx._check(self.ctx.L.plade_cloud_download(self.ctx.h, self.h, _ptr(rows), n.value, C.byref(n)))
+        return rows
 
     def free(self):
         if self.h:
@@ -825,6 +843,62 @@ class Context:
         self._check(self.L.plade_cloud_filter_outliers_dev(self.h, cloud.h, C.byref(prm), C.byref(h), _ptr(keep), _ptr(kept), C.byref(summ)))
         out = Cloud(self, None, handle=(int(summ.kept), h))
         return (out, kept[:summ.kept].copy(), _outlier_info(summ, keep)) if info else out
+
+    # ---- merging registered clouds ---------------------------------------------------------------
+    @staticmethod
+    def _merge_transforms(transforms, k):
+        if transforms is None:
+            return None
+        if len(transforms) != k:
+            raise ValueError("merge_clouds: one transform per cloud (None entries: the identity)")
+        T = np.empty((k, 4, 4), np.float32)
+        for c, t in enumerate(transforms):
+            T[c] = np.eye(4, dtype=np.float32) if t is None else _f32(t).reshape(4, 4)
+        return T
+
+    @staticmethod
+    def _merge_info(summ, count, mask):
+        info = {k: getattr(summ, k) for k, _ in MergeSummary._fields_ if k != "reserved"}
+        if count is not None:
+            info["count"], info["mask"] = count[:summ.n_out].copy(), mask[:summ.n_out].copy()
+        return info
+
+    def merge_clouds(self, clouds, transforms=None, leaf=0.0, per_voxel=True):
+        """plade_merge_clouds: 1..16 (N_c, 6) float32 clouds x y z nx ny nz, each taken into the output frame by its 4 x 4
+        transform (None: the identity), fused per voxel of edge `leaf` -- fp64 mean position, normalised fp64 sum of the finite
+        normals (opposite normals cancel: NaN) -- or, with leaf = 0, concatenated.  Returns (rows, info): the (M, 6) float32 rows in
+        voxel order and a dict with n_in, n_out, n_shared, max_count and -- with per_voxel -- count and mask (M uint32: the
+        voxel's points, bit c set when cloud c contributed)."""
+        arrs = [_f32(a) for a in clouds]
+        k = len(arrs)
+        for a in arrs:
+            if a.ndim != 2 or a.shape[1] != 6:
+                raise ValueError(f"merge_clouds: (N, 6) arrays x y z nx ny nz are required, got shape {a.shape}")
+        T = self._merge_transforms(transforms, k)
+        ptrs, ns = self._cloud_table(arrs)
+        total = sum(len(a) for a in arrs)
+        rows = np.empty((total, 6), np.float32)
+        count = np.empty(total, np.uint32) if per_voxel else None
+        mask = np.empty(total, np.uint32) if per_voxel else None
+        summ = MergeSummary()
+        self._check(self.L.plade_merge_clouds(self.h, k, ptrs, ns, _ptr(T), float(leaf), _ptr(rows), _ptr(count), _ptr(mask),
+                                              C.byref(summ)))
+        return rows[:summ.n_out].copy(), self._merge_info(summ, count, mask)
+
+    def merge_clouds_dev(self, clouds, transforms=None, leaf=0.0, info=False, per_voxel=True):
+        """plade_merge_clouds_dev: merge_clouds on resident clouds into a new resident Cloud (the point data makes no host round
+        trip); the same bits.  With info also the info dict of merge_clouds."""
+        k = len(clouds)
+        T = self._merge_transforms(transforms, k)
+        hs = (C.c_void_p * k)(*[c.h.value for c in clouds])
+        total = sum(c.n for c in clouds)
+        count = np.empty(total, np.uint32) if info and per_voxel else None
+        mask = np.empty(total, np.uint32) if info and per_voxel else None
+        summ = MergeSummary()
+        h = C.c_void_p()
+        self._check(self.L.plade_merge_clouds_dev(self.h, k, hs, _ptr(T), float(leaf), C.byref(h), _ptr(count), _ptr(mask), C.byref(summ)))
+        out = Cloud(self, None, handle=(int(summ.n_out), h))
+        return (out, self._merge_info(summ, count, mask)) if info else out
 
     def pin(self, arr):
         """Page-lock a C-contiguous float32 array the caller keeps alive (plade_host_pin); registration() calls that are

@@ -3,6 +3,7 @@
 #include "distances.h"
 #include "exact_sort.h"
 #include "icp.h"
+#include "merge.h"
 #include "normals.h"
 #include "outliers.h"
 #include "pipeline.h"
@@ -139,6 +140,7 @@ extern "C" void plade_ctx_destroy(plade_ctx *ctx) {
     if (ctx->icp_work) plade::icp_work_destroy(ctx->icp_work);
     if (ctx->dist_work) plade::dist_work_destroy(ctx->dist_work);
     if (ctx->outlier_work) plade::outlier_work_destroy(ctx->outlier_work);
+    if (ctx->merge_work) plade::merge_work_destroy(ctx->merge_work);
     (void)hipStreamDestroy(ctx->stream);
     if (ctx->pf.stream) { (void)hipStreamSynchronize(ctx->pf.stream); (void)hipStreamDestroy(ctx->pf.stream); }
     delete ctx;

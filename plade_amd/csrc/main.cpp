@@ -144,8 +144,9 @@ private:
     int n_ok_ = 0, n_failed_ = 0;
 };
 
-Outcome run_job(const Job &job, bool capture_console) {
+Outcome run_job(const Job &job, bool capture_console, const char *result_path, long pair) {
     Outcome r;
+    plade_set_thread_merge_output(result_path, pair);
     std::ostringstream out, err;
     if (capture_console) plade_set_thread_console(&out, &err);
     try {
@@ -169,7 +170,7 @@ int single_pair(const char *target, const char *source, const char *result_path)
         return EXIT_FAILURE;
     }
     const Job job{target, source};
-    const Outcome r = run_job(job, false);
+    const Outcome r = run_job(job, false, result_path, -1);
     write_block(output, job, r, false);
     if (!r.ok) return EXIT_FAILURE;
     std::cout << text::written << result_path << std::endl;
@@ -222,7 +223,7 @@ int batch(const char *list_path, const char *result_path) {
             { std::lock_guard<std::mutex> lk(take); i0 = next; next += group; }
             if (i0 >= jobs.size()) break;
             const size_t k = std::min(group, jobs.size() - i0);
-            if (k == 1) { writer.submit(i0, run_job(jobs[i0], true)); continue; }
+            if (k == 1) { writer.submit(i0, run_job(jobs[i0], true, result_path, (long)i0)); continue; }
             Outcome res[registration_group_max];
             std::ostringstream outs[registration_group_max], errs[registration_group_max];
             std::ostream *op[registration_group_max], *ep[registration_group_max];
@@ -230,6 +231,7 @@ int batch(const char *list_path, const char *result_path) {
             Matrix4 T[registration_group_max];
             bool ok[registration_group_max];
             for (size_t q = 0; q < k; ++q) { op[q] = &outs[q]; ep[q] = &errs[q]; tg[q] = jobs[i0 + q].target; sr[q] = jobs[i0 + q].source; }
+            plade_set_thread_merge_output(result_path, (long)i0);
             try {
                 registration_group(k, T, tg, sr, ok, op, ep);
             } catch (const std::exception &e) {   // nothing a malformed pair does may take the batch down

@@ -83,6 +83,19 @@ struct OutlierRemoval {
 bool remove_outliers(pcl::PointCloud<pcl::PointNormal>::Ptr cloud, pcl::PointCloud<pcl::PointNormal> &filtered, int k = 16,
                      double alpha = 1.0, OutlierRemoval *info = nullptr);
 
+/** Merging registered clouds (no counterpart in the reference): the fields of plade_merge_summary (include/plade_hip.h). */
+struct CloudMerge {
+    uint64_t n_in = 0, n_out = 0, n_shared = 0;   // points in, rows out, rows to which two or more clouds contributed
+    uint32_t max_count = 0;                       // the largest number of points fused into one row
+};
+/** Merges 1..16 clouds on the GPU (plade_merge_clouds): cloud c is taken into the common frame by transformations[c] (an empty
+ *  vector: identities), and the points of every voxel of edge `leaf` are fused into one -- the mean position and the normalised
+ *  sum of the finite normals (opposite normals cancel: NaN), both summed in fp64 in a fixed order; leaf = 0 concatenates.  false:
+ *  invalid input or no GPU; a message is printed and `merged` is unchanged.  The CLI writes the merged target and source of every
+ *  registered pair, in the target file's frame, when PLADE_MERGE=<leaf> is set, and prints one line per pair. */
+bool merge_clouds(const std::vector<pcl::PointCloud<pcl::PointNormal>::Ptr> &clouds, const std::vector<Eigen::Matrix4f> &transformations,
+                  float leaf, pcl::PointCloud<pcl::PointNormal> &merged, CloudMerge *info = nullptr);
+
 /** Batch extension (no counterpart in the reference, whose batch mode is a plain loop of the file overload above,
  *  code/PLADE/main.cpp:122-148): `count` (1..registration_group_max = PLADE_GROUP_MAX) consecutive pairs of the list as ONE group.  Every pair gets the result,
  *  the messages and the identity-on-failure of the file overload -- its transformation is bit for bit the one the file overload
@@ -105,6 +118,11 @@ int plade_gpu_count();
 /** Console of the calling thread's registrations: the messages the reference prints on std::cout / std::cerr go to
  *  these streams instead (nullptr = std::cout / std::cerr again).  Used by the CLI's batch workers. */
 void plade_set_thread_console(std::ostream *out, std::ostream *err);
+
+/** PLADE_MERGE: the result file whose name the merged clouds of the calling thread's registrations take -- <result_file>.merged.ply
+ *  with first_pair < 0, <result_file>.<first_pair + i>.merged.ply for pair i of a registration_group call (an empty name: no
+ *  merged cloud is written).  Used by the CLI. */
+void plade_set_thread_merge_output(const std::string &result_file, long first_pair);
 
 /** Destroy the calling thread's GPU context (it is created on first use and otherwise lives as long as the thread). */
 void plade_release_thread_context();

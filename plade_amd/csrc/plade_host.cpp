@@ -259,6 +259,66 @@ bool remove_outliers_in_place(std::vector<float> &buf) {
     return true;
 }
 
+// PLADE_MERGE=<leaf> (opt-in, absolute, in the clouds' units; 0 = plain concatenation): every pair that registered is merged on
+// the GPU (plade_merge_clouds: the target as it is, the source under the pair's final transformation -- after ICP when that is
+// on) into <result file>.merged.ply (one pair) or <result file>.<pair index>.merged.ply (a list), in the target file's frame; one
+// console line per pair.  The CLI names the result file (plade_set_thread_merge_output).  A value that is not a finite number
+// >= 0 prints one warning and merges nothing; unset, nothing changes.
+float merge_leaf() {   // < 0: off
+    static const float leaf = [] {
+        const char *w = getenv("PLADE_MERGE");
+        if (!w) return -1.f;
+        char *end = nullptr;
+        const double v = strtod(w, &end);
+        const float f = (float)v;
+        if (end == w || *end != '\0' || !std::isfinite(f) || !(f >= 0.f)) {
+            std::cerr << "warning: PLADE_MERGE=" << w << " is not a finite leaf size >= 0; no merge" << std::endl;
+            return -1.f;
+        }
+        return f;
+    }();
+    return leaf;
+}
+thread_local std::string g_merge_result;   // the result file whose name the merged clouds take; empty: no merge
+thread_local long g_merge_first = -1;      // index in the list of the first pair of the running call; < 0: a single pair
+// k packed clouds under their row-major 4 x 4 transforms (T16: k x 16 or nullptr) -> rows (sum n_c x 6, cut to the output)
+bool merge_packed(plade_ctx *ctx, uint32_t k, const float *const *clouds, const uint32_t *n, const float *T16, float leaf,
+                  std::vector<float> &rows, plade_merge_summary &s) {
+    size_t total = 0;
+    for (uint32_t c = 0; c < k; ++c) total += n[c];
+    rows.resize(total * 6);
+    trace("merge: merging");
+    const int rc = plade_merge_clouds(ctx, k, clouds, n, T16, leaf, rows.data(), nullptr, nullptr, &s);
+    trace("merge: done");
+    if (rc != PLADE_OK) {
+        con_err() << "warning: merge failed (" << plade_last_error(ctx) << ")" << std::endl;
+        return false;
+    }
+    rows.resize((size_t)s.n_out * 6);
+    return true;
+}
+// the pair as the FILES name it: T = source file -> target file
+void merge_pair(plade_ctx *ctx, const Eigen::Matrix<float, 4, 4> &T, const float *tg, size_t n_t, const float *sr, size_t n_s, long pair) {
+    const float leaf = merge_leaf();
+    if (leaf < 0.f || g_merge_result.empty() || !ctx) return;
+    float T16[32];
+    for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) { T16[4 * r + c] = r == c ? 1.f : 0.f; T16[16 + 4 * r + c] = T(r, c); }
+    const float *clouds[2] = {tg, sr};
+    const uint32_t n[2] = {(uint32_t)n_t, (uint32_t)n_s};
+    std::vector<float> rows;
+    plade_merge_summary s;
+    if (!merge_packed(ctx, 2, clouds, n, T16, leaf, rows, s)) return;
+    const std::string path = g_merge_result + (pair < 0 ? std::string() : "." + std::to_string(pair)) + ".merged.ply";
+    if (!plade::write_ply_pos_nrm(path, rows.data(), (size_t)s.n_out)) {
+        con_err() << "warning: writing " << path << " failed" << std::endl;
+        return;
+    }
+    char b[200];
+    snprintf(b, sizeof(b), "merge: %llu of %llu points kept, %llu voxels seen by both clouds", (unsigned long long)s.n_out,
+             (unsigned long long)s.n_in, (unsigned long long)s.n_shared);
+    con_out() << b << std::endl;
+}
+
 std::string extension(const std::string &file_name) {  // util.cpp:525-531
     std::string::size_type dot = file_name.find_last_of('.');
     std::string::size_type slash = file_name.find_last_of("/\\");
@@ -291,6 +351,7 @@ void plade_select_device(int device) { g_device = device; }
 int plade_gpu_count() { return plade_device_count(); }
 
 void plade_set_thread_console(std::ostream *out, std::ostream *err) { g_out = out; g_err = err; }
+void plade_set_thread_merge_output(const std::string &result_file, long first_pair) { g_merge_result = result_file; g_merge_first = first_pair; }
 
 void plade_release_thread_context() {
     for (PinnedVec &p : g_pins) p.release();     // before the arrays themselves go with the thread
@@ -456,6 +517,8 @@ bool registration(Eigen::Matrix<float, 4, 4> &transformation, const std::string 
         return false;
     }
     if (switched) transformation = transformation.inverse();
+    if (merge_leaf() >= 0.f)
+        merge_pair(context(), transformation, target_buf.data(), target_buf.size() / 6, source_buf.data(), source_buf.size() / 6, g_merge_first);
     return true;
 }
 
@@ -557,6 +620,9 @@ void registration_group(size_t count, Eigen::Matrix<float, 4, 4> *transformation
         if (evaluate_dist() > 0.f) evaluate_line(ctx, T16 + 16 * q, it.tg, it.n_t, it.sr, it.n_s);
         to_matrix(T16 + 16 * q, transformations[it.pair]);
         if (it.switched) transformations[it.pair] = transformations[it.pair].inverse();
+        if (merge_leaf() >= 0.f)
+            merge_pair(ctx, transformations[it.pair], bufs[2 * it.pair].data(), bufs[2 * it.pair].size() / 6, bufs[2 * it.pair + 1].data(),
+                       bufs[2 * it.pair + 1].size() / 6, g_merge_first < 0 ? (long)it.pair : g_merge_first + (long)it.pair);
         ok[it.pair] = true;
     }
     plade_set_thread_console(nullptr, nullptr);
@@ -604,6 +670,39 @@ bool remove_outliers(pcl::PointCloud<pcl::PointNormal>::Ptr cloud, pcl::PointClo
         filtered.at(i) = pcl::PointNormal(p[0], p[1], p[2], p[3], p[4], p[5]);
     }
     if (info) { info->n = s.n; info->kept = s.kept; info->mu = s.mu; info->sigma = s.sigma; info->threshold = s.threshold; }
+    return true;
+}
+
+// merging registered clouds: see plade.h
+bool merge_clouds(const std::vector<pcl::PointCloud<pcl::PointNormal>::Ptr> &clouds, const std::vector<Eigen::Matrix4f> &transformations,
+                  float leaf, pcl::PointCloud<pcl::PointNormal> &merged, CloudMerge *info) {
+    plade_ctx *ctx = context();
+    if (!ctx) return false;
+    if (clouds.empty() || clouds.size() > 16 || (!transformations.empty() && transformations.size() != clouds.size())) {
+        con_err() << "merge_clouds: 1 to 16 clouds and one transformation per cloud (or none) are required" << std::endl;
+        return false;
+    }
+    std::vector<std::vector<float>> flat;
+    std::vector<const float *> ptr;
+    std::vector<uint32_t> n;
+    std::vector<float> T16;
+    for (size_t c = 0; c < clouds.size(); ++c) {
+        if (!clouds[c]) { con_err() << "merge_clouds: null cloud" << std::endl; return false; }
+        flat.push_back(flatten(*clouds[c]));
+        n.push_back((uint32_t)clouds[c]->size());
+        if (!transformations.empty())
+            for (int r = 0; r < 4; ++r) for (int q = 0; q < 4; ++q) T16.push_back(transformations[c](r, q));
+    }
+    for (auto &f : flat) ptr.push_back(f.data());
+    std::vector<float> rows;
+    plade_merge_summary s;
+    if (!merge_packed(ctx, (uint32_t)clouds.size(), ptr.data(), n.data(), T16.empty() ? nullptr : T16.data(), leaf, rows, s)) return false;
+    merged.resize((size_t)s.n_out);
+    for (size_t i = 0; i < (size_t)s.n_out; ++i) {
+        const float *p = &rows[6 * i];
+        merged.at(i) = pcl::PointNormal(p[0], p[1], p[2], p[3], p[4], p[5]);
+    }
+    if (info) { info->n_in = s.n_in; info->n_out = s.n_out; info->n_shared = s.n_shared; info->max_count = s.max_count; }
     return true;
 }
 

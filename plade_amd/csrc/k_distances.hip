@@ -2,24 +2,24 @@
 // (semantics: distances.h).
 //
 // Layout
-//   grid    one dense row index of TargetGrid (overlap.h) over the target.  The cell follows the target's density (about five
-//           points per occupied cell of a surface), or d plus a margin when d is smaller: then one 27-cell block holds every
-//           target point closer than d.  The cell never grows to a large d -- a d-sized cell would hand each probe thousands of
-//           candidates (the ICP's coarse stage).
+//   grid    one dense row index of TargetGrid over the target, walked with the pieces of grid_walk.h.  The cell follows the
+//           target's density (about five points per occupied cell of a surface), or d plus a margin when d is smaller: then one
+//           27-cell block holds every target point closer than d.  The cell never grows to a large d -- a d-sized cell would
+//           hand each probe thousands of candidates (the ICP's coarse stage).
 //   order   k_distances_keys forms p' and its padded cell id in that grid; the radix sort orders the probes by cell, so the 64
 //           lanes of a wavefront probe neighbouring cells and share their candidate runs.  Outputs go back by original index.
 //   lane    k_distances_lane: one lane per probe scans its 27-cell block for the (d2, j) argmin key.  The probe is finished when
 //           that key is closer than the block's outside, or the outside is at least d away (both less a margin for the fp32 cell
 //           assignment).  A probe at least d from the target's bounding box ends before any load of the grid.  The rest is
 //           appended to a compacted list (one atomic per wavefront).
-//   ring    k_distances_ring: one wavefront per listed probe grows the block as k_normals_ring does (radius + max(1, radius / 2)
-//           per step, each step reading only the runs the previous block did not hold); the 64 keys of a batch are reduced by a
-//           wave min.  It stops at the first block whose outside is at least min(best, d) away, or that covers the grid.
+//   ring    k_distances_ring: one wavefront per listed probe grows the block as k_normals_ring does (ring_step); the 64 keys of a
+//           batch are reduced by a wave min.  It stops at the first block whose outside is at least min(best, d) away, or that
+//           covers the grid.
 //   summary k_distances_summary: one lane per original index forms the plane residual in fp64 and the six summary terms; a
 //           butterfly per wave, the waves in order, one partial per workgroup.  k_distances_final sums the partials with one
 //           wavefront in a fixed order (lane l: partials l, l + 64, ..., then a butterfly).  No fp64 atomics.
 #include "distances.h"
-#include "overlap.h"
+#include "grid_walk.h"
 #include "prims.h"
 #include "voxel.h"
 
@@ -27,17 +27,12 @@ namespace plade {
 
 namespace {
 
-typedef unsigned long long u64;
-constexpr u64 EMPTY = ~0ull;
 constexpr int KEY_TPB = 256, LANE_TPB = 256, SUM_TPB = 256, RING_WAVES = 4;
 constexpr int SUM_TERMS = 6;   // count, sum d2, sum sqrt(d2), max sqrt(d2), plane_count, sum r^2
 
 struct DistArgs {
-    const float4 *sorted;            // the target in cell order: x y z, bit-cast original index
-    const uint32_t *row_start;
-    float mnx, mny, mnz, inv;        // the grid's cell assignment (k_cell_ids)
-    int dx, dy, dz, DX, DY;          // cells, padded row pitch
-    double mn[3], cell, margin;
+    GridView g;                      // over the target
+    double margin;                   // grid_margin
     double bmn[3], bmx[3];           // the target's bounding box
     float d2;                        // (float)d * (float)d
     const float4 *probe;             // n probes in the original order: p', bit-cast original index
@@ -48,33 +43,11 @@ struct DistArgs {
     uint32_t *fail, *fail_count;
 };
 
-__device__ __forceinline__ u64 make_key(float d, uint32_t j) { return ((u64)__float_as_uint(d) << 32) | (u64)j; }
-__device__ __forceinline__ float key_d(u64 key) { return __uint_as_float((uint32_t)(key >> 32)); }   // EMPTY: NaN
-
-__device__ __forceinline__ void cell_of(const DistArgs &a, f3 q, int &cx, int &cy, int &cz) {   // = k_cell_ids
-    cx = min(max((int)floorf((q.x - a.mnx) * a.inv), 0), a.dx - 1);
-    cy = min(max((int)floorf((q.y - a.mny) * a.inv), 0), a.dy - 1);
-    cz = min(max((int)floorf((q.z - a.mnz) * a.inv), 0), a.dz - 1);
-}
-
 // margin of one probe: the grid's (1 % of a cell, ulps of the target's coordinates) and a few ulps of the probe's own
 __device__ __forceinline__ double margin_of(const DistArgs &a, f3 q) {
     return a.margin + 1e-6 * (double)fmaxf(fabsf(q.x), fmaxf(fabsf(q.y), fabsf(q.z)));
 }
 
-// distance from q to the outside of the block of cells [c - R, c + R]^3, less the margin (as k_normals' block_reach: no bound
-// where the block reaches the grid's edge, nothing lies beyond); +inf: the block covers the grid
-__device__ __forceinline__ double block_reach(const DistArgs &a, f3 q, int cx, int cy, int cz, int R, double mg) {
-    double b = INFINITY;
-    const double qv[3] = {q.x, q.y, q.z};
-    const int c[3] = {cx, cy, cz}, d[3] = {a.dx, a.dy, a.dz};
-#pragma unroll
-    for (int t = 0; t < 3; ++t) {
-        if (c[t] - R > 0) b = fmin(b, qv[t] - (a.mn[t] + (double)(c[t] - R) * a.cell));
-        if (c[t] + R < d[t] - 1) b = fmin(b, (a.mn[t] + (double)(c[t] + R + 1) * a.cell) - qv[t]);
-    }
-    return b == INFINITY ? b : b - mg;
-}
 // true: the best key so far is final -- it is closer than every point outside the block, or every point outside the block is
 // at least d away (then a correspondence can only come from inside it)
 __device__ __forceinline__ bool finished(const DistArgs &a, float best, double reach) {
@@ -102,8 +75,8 @@ __global__ __launch_bounds__(KEY_TPB) void k_distances_keys(const float *__restr
     const f3 q(((Tf[0] * x + Tf[1] * y) + Tf[2] * z) + Tf[3], ((Tf[4] * x + Tf[5] * y) + Tf[6] * z) + Tf[7],
                ((Tf[8] * x + Tf[9] * y) + Tf[10] * z) + Tf[11]);
     int cx, cy, cz;
-    cell_of(a, q, cx, cy, cz);
-    keys[i] = (uint32_t)(cx + 2) + (uint32_t)a.DX * ((uint32_t)(cy + 2) + (uint32_t)a.DY * (uint32_t)(cz + 2));
+    cell_of(a.g, q, cx, cy, cz);
+    keys[i] = (uint32_t)(cx + 2) + row_base(a.g, cy, cz);
     vals[i] = i;
     probe[i] = make_float4(q.x, q.y, q.z, __uint_as_float(i));
 }
@@ -129,48 +102,23 @@ __global__ __launch_bounds__(LANE_TPB) void k_distances_lane(const DistArgs a) {
         u64 best = EMPTY;
         if (!(gap > 0.0 && a.d2 <= (float)(gap * gap))) {
             int cx, cy, cz;
-            cell_of(a, q, cx, cy, cz);
-            // nine runs of three cells; the padding of the row index makes every row of the block valid
-            for (int dz = -1; dz <= 1; ++dz)
-                for (int dy = -1; dy <= 1; ++dy) {
-                    const uint32_t r = (uint32_t)(cx + 1) + (uint32_t)a.DX * ((uint32_t)(cy + dy + 2) + (uint32_t)a.DY * (uint32_t)(cz + dz + 2));
-                    const uint32_t j1 = a.row_start[r + 3];
-                    for (uint32_t j = a.row_start[r]; j < j1; ++j) {
-                        const float4 p = a.sorted[j];
-                        const u64 key = make_key(flann_d2(q, f3(p.x, p.y, p.z)), __float_as_uint(p.w));
-                        best = key < best ? key : best;
-                    }
+            cell_of(a.g, q, cx, cy, cz);
+            for_block27(a.g, cx, cy, cz, [&](uint32_t j0, uint32_t j1) {
+                for (uint32_t j = j0; j < j1; ++j) {
+                    const float4 p = a.g.sorted[j];
+                    const u64 key = make_key(flann_d2(q, f3(p.x, p.y, p.z)), __float_as_uint(p.w));
+                    best = key < best ? key : best;
                 }
-            fail = !finished(a, key_d(best), block_reach(a, q, cx, cy, cz, 1, mg));
+            });
+            fail = !finished(a, key_d(best), block_reach(a.g, q, cx, cy, cz, 1, mg));
         }
         if (!fail) store(a, orig, best);
     }
-    // wave-aggregated append to the list of the ring pass
-    const u64 mask = __ballot(fail);
-    if (mask) {
-        const uint32_t lane = threadIdx.x & 63u, leader = (uint32_t)__ffsll((long long)mask) - 1u;
-        uint32_t base = 0;
-        if (lane == leader) base = atomicAdd(a.fail_count, (uint32_t)__popcll(mask));
-        base = __shfl(base, (int)leader, 64);
-        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-        if (fail) a.fail[base + rank] = orig;
-    }
+    fail_append(fail, orig, a.fail, a.fail_count);   // to the list of the ring pass
 }
 
-__device__ __forceinline__ u64 wave_min(u64 v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        const u64 w = __shfl_xor(v, o, 64);
-        v = w < v ? w : v;
-    }
-    return v;
-}
-
-// One wavefront per probe of the list (persistent workgroups; the list's length stays on the device).  The block [c - rout,
-// c + rout]^3 grows by half its radius per step; a step reads whole x runs of the rows outside the old block's y-z square and the
-// two x runs left and right of it in the rows inside (one or two row look-ups per row: O(R^2) per step, not the O(R^3) of cells).
-// The candidates of all lanes' runs are handed out 64 at a time (a wave prefix sum over the run lengths, each lane finding its
-// run by a binary search over the lanes) and reduced by a wave min of (d2, j) keys.
+// One wavefront per probe of the list (persistent workgroups; the list's length stays on the device): the growing blocks of
+// ring_step, each batch reduced by a wave min of (d2, j) keys.
 __global__ __launch_bounds__(64 * RING_WAVES) void k_distances_ring(const DistArgs a) {
     const int lane = (int)(threadIdx.x & 63u), wv = (int)(threadIdx.x >> 6);
     const uint32_t total = *a.fail_count, stride_w = gridDim.x * RING_WAVES;
@@ -180,54 +128,14 @@ __global__ __launch_bounds__(64 * RING_WAVES) void k_distances_ring(const DistAr
         const f3 q(q4.x, q4.y, q4.z);
         const double mg = margin_of(a, q);
         int cx, cy, cz;
-        cell_of(a, q, cx, cy, cz);
+        cell_of(a.g, q, cx, cy, cz);
         u64 best = EMPTY;
         for (int rin = -1, rout = 1;; rin = rout, rout += max(1, rout / 2)) {
-            const int y0 = max(cy - rout, 0), y1 = min(cy + rout, a.dy - 1), z0 = max(cz - rout, 0), z1 = min(cz + rout, a.dz - 1);
-            const int ny = y1 - y0 + 1, rows = ny * (z1 - z0 + 1);
-            const int xo0 = max(cx - rout, 0), xo1 = min(cx + rout, a.dx - 1);   // x range of the new block
-            for (int t0 = 0; t0 < rows; t0 += 64) {                              // (wave-uniform)
-                const int t = t0 + lane;
-                uint32_t a0 = 0, la = 0, b0 = 0, lb = 0;                         // up to two runs of this lane's row
-                if (t < rows) {
-                    const int y = y0 + t % ny, z = z0 + t / ny;
-                    const uint32_t row = (uint32_t)a.DX * ((uint32_t)(y + 2) + (uint32_t)a.DY * (uint32_t)(z + 2)) + 2u;
-                    if (abs(y - cy) > rin || abs(z - cz) > rin) {                // outside the old block's y-z square: the whole run
-                        a0 = a.row_start[row + (uint32_t)xo0];
-                        la = a.row_start[row + (uint32_t)xo1 + 1u] - a0;
-                    } else {                                                     // inside: left and right of the old block
-                        if (cx - rin - 1 >= xo0) {
-                            a0 = a.row_start[row + (uint32_t)xo0];
-                            la = a.row_start[row + (uint32_t)(cx - rin)] - a0;
-                        }
-                        if (cx + rin + 1 <= xo1) {
-                            b0 = a.row_start[row + (uint32_t)(cx + rin + 1)];
-                            lb = a.row_start[row + (uint32_t)xo1 + 1u] - b0;
-                        }
-                    }
-                }
-                const uint32_t len = la + lb;
-                uint32_t incl = len;
-#pragma unroll
-                for (int d = 1; d < 64; d <<= 1) { const uint32_t o = __shfl_up(incl, d, 64); if (lane >= d) incl += o; }
-                const uint32_t pre = incl - len, cand_total = __shfl(incl, 63, 64);
-                for (uint32_t c0 = 0; c0 < cand_total; c0 += 64) {               // (wave-uniform)
-                    const uint32_t idx = c0 + (uint32_t)lane;
-                    int o = 0;                                                   // the last lane whose run starts at or before idx
-#pragma unroll
-                    for (int st = 32; st >= 1; st >>= 1) if (__shfl(pre, o + st, 64) <= idx) o += st;
-                    const uint32_t off = idx - __shfl(pre, o, 64), la_o = __shfl(la, o, 64);
-                    const uint32_t a0_o = __shfl(a0, o, 64), b0_o = __shfl(b0, o, 64);
-                    u64 key = EMPTY;
-                    if (idx < cand_total) {
-                        const float4 p = a.sorted[off < la_o ? a0_o + off : b0_o + (off - la_o)];
-                        key = make_key(flann_d2(q, f3(p.x, p.y, p.z)), __float_as_uint(p.w));
-                    }
-                    const u64 m = wave_min(key);
-                    best = m < best ? m : best;
-                }
-            }
-            if (finished(a, key_d(best), block_reach(a, q, cx, cy, cz, rout, mg))) break;
+            ring_step(a.g, cx, cy, cz, rin, rout, lane, [&](bool valid, float4 p) {
+                const u64 m = wave_min(valid ? make_key(flann_d2(q, f3(p.x, p.y, p.z)), __float_as_uint(p.w)) : EMPTY);
+                best = m < best ? m : best;
+            });
+            if (finished(a, key_d(best), block_reach(a.g, q, cx, cy, cz, rout, mg))) break;
         }
         if (lane == 0) store(a, orig, best);
     }
@@ -349,17 +257,12 @@ void distances_dev(plade_ctx *ctx, DistWork &W, const float *d_tgt, uint32_t n_t
     const double dense_cell = 1.5 * std::sqrt(8.0 * area / (M_PI * (double)n_t)), d_cell = 1.03 * (double)max_dist + 4e-6 * amax;
     TargetGrid &G = W.grid;
     G.build(ctx, d_tgt, n_t, 6, (float)std::min(dense_cell, d_cell), tmn, tmx, true);
-    PLADE_REQUIRE(G.dense, PLADE_EINVAL, "cloud_distances: needs the dense row index (unset PLADE_OVERLAP_INDEX_COMPACT)");
     HIP_TRY(hipEventRecord(W.ev[1], ctx->stream));
 
     DistArgs a;
     memset(&a, 0, sizeof(a));
-    a.sorted = G.sorted.p; a.row_start = G.row_start.p;
-    a.mnx = G.gp.mnx; a.mny = G.gp.mny; a.mnz = G.gp.mnz; a.inv = G.gp.inv;
-    a.dx = G.gp.dx; a.dy = G.gp.dy; a.dz = G.gp.dz; a.DX = G.DX; a.DY = G.DY;
-    a.mn[0] = G.gp.mnx; a.mn[1] = G.gp.mny; a.mn[2] = G.gp.mnz;
-    a.cell = 1.0 / (double)G.gp.inv;
-    a.margin = 0.01 * a.cell + 1e-6 * amax;   // fp32 cell assignment: a few ulps of the coordinates, 1 % of a cell on top
+    a.g = view_of(G, "cloud_distances");
+    a.margin = grid_margin(a.g, tmn, tmx);
     for (int t = 0; t < 3; ++t) { a.bmn[t] = tmn[t]; a.bmx[t] = tmx[t]; }
     a.d2 = max_dist * max_dist;
     a.n = n_s;
@@ -428,12 +331,6 @@ void distances_dev(plade_ctx *ctx, DistWork &W, const float *d_tgt, uint32_t n_t
     ctx->stats.add("distances_ring_queries", W.h_count);
 }
 
-void upload(plade_ctx *ctx, DBuf<float> &buf, const float *h, uint32_t n, uint32_t stride, float mn[3], float mx[3]) {
-    buf.ensure((size_t)n * stride + 4);
-    HIP_TRY(hipMemcpyAsync(buf.p, h, (size_t)n * stride * 4, hipMemcpyHostToDevice, ctx->stream));
-    bbox_host(ctx, buf.p, n, stride, mn, mx);   // (waits; refuses non-finite coordinates)
-}
-
 DistWork &work_of(plade_ctx *ctx) {
     if (!ctx->dist_work) ctx->dist_work = dist_work_create();
     return *ctx->dist_work;
@@ -456,8 +353,8 @@ extern "C" int plade_cloud_distances(plade_ctx *ctx, const float *tgt_pos_nrm, u
         check_args(T, max_dist);
         DistWork &W = work_of(ctx);
         float tmn[3], tmx[3], smn[3], smx[3];
-        upload(ctx, W.in_t, tgt_pos_nrm, n_t, 6, tmn, tmx);
-        upload(ctx, W.in_s, src_xyz, n_s, stride, smn, smx);
+        upload_rows(ctx, W.in_t, tgt_pos_nrm, n_t, 6, tmn, tmx);
+        upload_rows(ctx, W.in_s, src_xyz, n_s, stride, smn, smx);
         distances_dev(ctx, W, W.in_t.p, n_t, tmn, tmx, W.in_s.p, n_s, stride, T, max_dist, idx_out, d2_out, plane_out, summary);
         return PLADE_OK;
     });

@@ -1,9 +1,9 @@
 // plade_amd/csrc/k_icp.hip -- point-to-plane ICP refinement on gfx950 (semantics: icp.h).
 //
 // Layout
-//   grids   one dense row index of TargetGrid (overlap.h) per stage distance d, cell >= d: the 27 cells around a probe's cell
-//           are nine contiguous runs of `sorted` and hold every target point closer than d, so the argmin over them is the
-//           exact one whenever it is below d (and the probe has no correspondence otherwise).  The grids are built up front.
+//   grids   one dense row index of TargetGrid per stage distance d, cell >= d: the 27 cells around a probe's cell (for_block27,
+//           grid_walk.h) hold every target point closer than d, so the argmin over them is the exact one whenever it is below d
+//           (and the probe has no correspondence otherwise).  The grids are built up front.
 //   mean    k_icp_mean_part / k_icp_mean: the fp64 mean s-bar of the sample, once, in a fixed order (one partial per workgroup:
 //           a butterfly across each wave, then the waves in order; one wavefront then sums the partials like k_icp_solve); the
 //           second kernel also sets the first centre c_0 = T_0 s-bar.
@@ -15,15 +15,13 @@
 //   solve   k_icp_solve: one wavefront sums the partials in a fixed order (lane l: partials l, l + 64, ..., then a butterfly),
 //           and lane 0 runs the Cholesky solve, Rodrigues, the update of T and c and the stage / convergence / failure rules.
 #include "icp.h"
-#include "overlap.h"
+#include "grid_walk.h"
 #include "voxel.h"
 
 namespace plade {
 
 namespace {
 
-typedef unsigned long long u64;
-constexpr u64 EMPTY = ~0ull;
 constexpr int CORR_TPB = 256;
 
 // the device state of one refinement (one allocation, uploaded once per call)
@@ -39,10 +37,7 @@ struct IcpState {
 };
 
 struct IcpGridArgs {
-    const float4 *sorted;
-    const uint32_t *row_start;
-    float mnx, mny, mnz, inv;
-    int dx, dy, dz, DX, DY;
+    GridView g;
     float d2;            // (float)d * (float)d
 };
 
@@ -66,8 +61,6 @@ struct IcpSolveArgs {
     double *moments;     // seam: the summed moments (nullptr in the loop: solve and update)
 };
 
-__device__ __forceinline__ u64 make_key(float d, uint32_t j) { return ((u64)__float_as_uint(d) << 32) | (u64)j; }
-
 __global__ __launch_bounds__(CORR_TPB) void k_icp_corr_lin(const IcpArgs a) {
     __shared__ double s_red[CORR_TPB / 64][ICP_MOMENTS];
     const IcpState *st = a.st;
@@ -83,23 +76,18 @@ __global__ __launch_bounds__(CORR_TPB) void k_icp_corr_lin(const IcpArgs a) {
         const float *Tf = st->Tf;
         const f3 q(((Tf[0] * x + Tf[1] * y) + Tf[2] * z) + Tf[3], ((Tf[4] * x + Tf[5] * y) + Tf[6] * z) + Tf[7],
                    ((Tf[8] * x + Tf[9] * y) + Tf[10] * z) + Tf[11]);
-        const int cx = min(max((int)floorf((q.x - G.mnx) * G.inv), 0), G.dx - 1);   // = k_cell_ids
-        const int cy = min(max((int)floorf((q.y - G.mny) * G.inv), 0), G.dy - 1);
-        const int cz = min(max((int)floorf((q.z - G.mnz) * G.inv), 0), G.dz - 1);
+        int cx, cy, cz;
+        cell_of(G.g, q, cx, cy, cz);
         u64 best = EMPTY;
-        // nine runs of three cells; the padding of the row index makes every row of the block valid
-        for (int dz = -1; dz <= 1; ++dz)
-            for (int dy = -1; dy <= 1; ++dy) {
-                const uint32_t r = (uint32_t)(cx + 1) + (uint32_t)G.DX * ((uint32_t)(cy + dy + 2) + (uint32_t)G.DY * (uint32_t)(cz + dz + 2));
-                const uint32_t j1 = G.row_start[r + 3];
-                for (uint32_t j = G.row_start[r]; j < j1; ++j) {
-                    const float4 p = G.sorted[j];
-                    const u64 key = make_key(flann_d2(q, f3(p.x, p.y, p.z)), __float_as_uint(p.w));
-                    best = key < best ? key : best;
-                }
+        for_block27(G.g, cx, cy, cz, [&](uint32_t j0, uint32_t j1) {
+            for (uint32_t j = j0; j < j1; ++j) {
+                const float4 p = G.g.sorted[j];
+                const u64 key = make_key(flann_d2(q, f3(p.x, p.y, p.z)), __float_as_uint(p.w));
+                best = key < best ? key : best;
             }
+        });
         int32_t jout = -1;
-        if (best != EMPTY && __uint_as_float((uint32_t)(best >> 32)) < G.d2) {
+        if (best != EMPTY && key_d(best) < G.d2) {
             const uint32_t j = (uint32_t)best;
             const float *t = a.tgt + (size_t)j * 6;
             const double n0 = t[3], n1 = t[4], n2 = t[5];
@@ -383,11 +371,8 @@ IcpGridArgs stage_grid(plade_ctx *ctx, TargetGrid &G, const float *d_tgt, uint32
     // cell >= d with a margin for the fp32 cell assignment: 1 % of d and a few ulps of the largest coordinate (build() adds 0.1 %
     // and may enlarge the cell further; a larger cell only adds candidates)
     G.build(ctx, d_tgt, n_t, 6, (float)(1.01 * d + 4e-6 * amax_of(tmn, tmx)), tmn, tmx, true);
-    PLADE_REQUIRE(G.dense, PLADE_EINVAL, "refine_icp: needs the dense row index (unset PLADE_OVERLAP_INDEX_COMPACT)");
     IcpGridArgs g;
-    g.sorted = G.sorted.p; g.row_start = G.row_start.p;
-    g.mnx = G.gp.mnx; g.mny = G.gp.mny; g.mnz = G.gp.mnz; g.inv = G.gp.inv;
-    g.dx = G.gp.dx; g.dy = G.gp.dy; g.dz = G.gp.dz; g.DX = G.DX; g.DY = G.DY;
+    g.g = view_of(G, "refine_icp");
     const float df = (float)d;
     g.d2 = df * df;
     return g;
@@ -473,12 +458,6 @@ int refine_dev(plade_ctx *ctx, IcpWork &W, const float *d_tgt, uint32_t n_t, con
     return PLADE_OK;
 }
 
-void upload(plade_ctx *ctx, DBuf<float> &buf, const float *h, uint32_t n, uint32_t stride, float mn[3], float mx[3]) {
-    buf.ensure((size_t)n * stride + 4);
-    HIP_TRY(hipMemcpyAsync(buf.p, h, (size_t)n * stride * 4, hipMemcpyHostToDevice, ctx->stream));
-    bbox_host(ctx, buf.p, n, stride, mn, mx);   // (waits: the host array may be released after the call)
-}
-
 IcpWork &work_of(plade_ctx *ctx) {
     if (!ctx->icp_work) ctx->icp_work = icp_work_create();
     return *ctx->icp_work;
@@ -509,8 +488,8 @@ extern "C" int plade_refine_icp(plade_ctx *ctx, const float *tgt_pos_nrm, uint32
         check_T(T_in16);
         IcpWork &W = work_of(ctx);
         float tmn[3], tmx[3], smn[3], smx[3];
-        upload(ctx, W.in_t, tgt_pos_nrm, n_t, 6, tmn, tmx);
-        upload(ctx, W.in_s, src_pos_nrm, n_s, 6, smn, smx);
+        upload_rows(ctx, W.in_t, tgt_pos_nrm, n_t, 6, tmn, tmx);
+        upload_rows(ctx, W.in_s, src_pos_nrm, n_s, 6, smn, smx);
         return refine_dev(ctx, W, W.in_t.p, n_t, tmn, tmx, W.in_s.p, n_s, 6, smn, smx, T_in16, params, T_out16, result);
     });
 }
@@ -538,8 +517,8 @@ extern "C" int plade_icp_linearize(plade_ctx *ctx, const float *tgt_pos_nrm, uin
         for (int k = 0; k < 3; ++k) PLADE_REQUIRE(std::isfinite(center[k]), PLADE_EINVAL, "plade_icp_linearize: center must be finite");
         IcpWork &W = work_of(ctx);
         float tmn[3], tmx[3], smn[3], smx[3];
-        upload(ctx, W.in_t, tgt_pos_nrm, n_t, 6, tmn, tmx);
-        upload(ctx, W.in_s, src_xyz, n_s, stride, smn, smx);
+        upload_rows(ctx, W.in_t, tgt_pos_nrm, n_t, 6, tmn, tmx);
+        upload_rows(ctx, W.in_s, src_xyz, n_s, stride, smn, smx);
         IcpArgs a;
         memset(&a, 0, sizeof(a));
         a.g[0] = stage_grid(ctx, W.grids[0], W.in_t.p, n_t, tmn, tmx, (double)dist);

@@ -1,15 +1,16 @@
 // plade_amd/csrc/k_outliers.hip -- statistical and radius outlier removal on gfx950 (semantics: outliers.h).
 //
 // Layout
-//   grid     the dense row index of TargetGrid (overlap.h).  Statistical mode: the cell of k_normals (an occupied cell holds about
-//            0.7 k points, adapted to the measured occupancy).  Radius mode: the cell is 1.03 r + 4e-6 max|coordinate| (the rule of
-//            DESIGN.md section 10), so the 27-cell block around a point holds everything closer than r.
+//   grid     the dense row index of TargetGrid, walked with the pieces of grid_walk.h.  Statistical mode: the cell of k_normals
+//            (build_knn_grid: an occupied cell holds about 0.7 k points, adapted to the measured occupancy).  Radius mode: the cell
+//            is 1.03 r + 4e-6 max|coordinate| (the rule of DESIGN.md section 10), so the 27-cell block around a point holds
+//            everything closer than r.
 //   search   k_outliers_grid<K>: one lane per point in the grid's sorted order keeps its K best (d, j) keys -- 64-bit words
 //            d_bits << 32 | j -- as a sorted list in registers, the point itself left out by its index.  A point whose k-th key is
 //            closer than the outside of its 27-cell block is finished: m_i is summed from the registers in ascending key order.
 //            The others are appended to a compacted list.
-//   rings    k_outliers_ring: one wavefront per listed point, the growing blocks of k_normals_ring (one key per lane, bitonic
-//            merges).  m_i is summed in the same order by a broadcast per key: the same bits as the grid kernel would give.
+//   rings    k_outliers_ring: one wavefront per listed point, the growing blocks of k_normals_ring (ring_step; one key per lane,
+//            wave_merge).  m_i is summed in the same order by a broadcast per key: the same bits as the grid kernel would give.
 //   radius   k_outliers_radius: one lane per point in grid order counts the points of its 27-cell block closer than r.  Without
 //            the per-point counts a lane stops at the end of the row run that reaches min_neighbours.
 //   mu sigma k_outliers_sum / k_outliers_final, twice: a butterfly per wave, the waves in order, one partial per workgroup; one
@@ -18,7 +19,7 @@
 //   keep     k_outliers_flags; compact_flags (one scan) gives the ascending kept list; k_outliers_gather copies the kept rows
 //            word by word.
 #include "outliers.h"
-#include "overlap.h"
+#include "grid_walk.h"
 #include "prims.h"
 #include "stages.h"
 #include "voxel.h"
@@ -28,29 +29,20 @@ namespace plade {
 
 namespace {
 
-typedef unsigned long long u64;
-constexpr u64 EMPTY = ~0ull;
 constexpr int GRID_TPB = 128, RING_WAVES = 4, RAD_TPB = 256, SUM_TPB = 256, ROW_TPB = 256;
-
-// the dense row index and its cell assignment (k_cell_ids)
-struct GridView {
-    const float4 *sorted;            // the points in cell order: x y z, bit-cast original index
-    const uint32_t *row_start;
-    uint32_t n;
-    float mnx, mny, mnz, inv;
-    int dx, dy, dz, DX, DY;          // cells, padded row pitch
-};
 
 struct StatArgs {
     GridView g;
+    uint32_t n;
     int m;                           // k_eff = min(k, n - 1) >= 1
-    double mn[3], cell, margin;
+    double margin;                   // grid_margin
     double *mean;                    // m_i by original index
     uint32_t *fail, *fail_count;
 };
 
 struct RadArgs {
     GridView g;
+    uint32_t n;
     float r2;                        // (float)r * (float)r
     uint32_t min_nb, stop;           // stop: the count at which a lane may end (0xffffffff: count everything)
     uint32_t *count;                 // c_i by original index, or nullptr
@@ -58,49 +50,11 @@ struct RadArgs {
     uint32_t *flags;
 };
 
-__device__ __forceinline__ u64 make_key(float d, uint32_t j) { return ((u64)__float_as_uint(d) << 32) | (u64)j; }
-__device__ __forceinline__ float key_d(u64 key) { return __uint_as_float((uint32_t)(key >> 32)); }   // EMPTY: NaN
-
-__device__ __forceinline__ void cell_of(const GridView &g, f3 q, int &cx, int &cy, int &cz) {   // = k_cell_ids
-    cx = min(max((int)floorf((q.x - g.mnx) * g.inv), 0), g.dx - 1);
-    cy = min(max((int)floorf((q.y - g.mny) * g.inv), 0), g.dy - 1);
-    cz = min(max((int)floorf((q.z - g.mnz) * g.inv), 0), g.dz - 1);
-}
-
-template <int K>
-__device__ __forceinline__ void insert(u64 (&best)[K], u64 key) {
-    if (key < best[K - 1]) {
-        // top down, in place: the new entry b depends only on the old entries b - 1 and b
-#pragma unroll
-        for (int b = K - 1; b > 0; --b) best[b] = key < best[b - 1] ? best[b - 1] : (key < best[b] ? key : best[b]);
-        best[0] = key < best[0] ? key : best[0];
-    }
-}
-
-// distance from q to the outside of the block of cells [c - R, c + R]^3 (no bound where the block reaches the grid's edge: cell
-// ids are clamped there, nothing lies beyond), less the margin; +inf: the block covers the grid
-__device__ __forceinline__ double block_reach(const StatArgs &a, f3 q, int cx, int cy, int cz, int R) {
-    double b = INFINITY;
-    const double qv[3] = {q.x, q.y, q.z};
-    const int c[3] = {cx, cy, cz}, d[3] = {a.g.dx, a.g.dy, a.g.dz};
-#pragma unroll
-    for (int t = 0; t < 3; ++t) {
-        if (c[t] - R > 0) b = fmin(b, qv[t] - (a.mn[t] + (double)(c[t] - R) * a.cell));
-        if (c[t] + R < d[t] - 1) b = fmin(b, (a.mn[t] + (double)(c[t] + R + 1) * a.cell) - qv[t]);
-    }
-    return b == INFINITY ? b : b - a.margin;
-}
-// true: every point outside the block is farther than d (squared distance)
-__device__ __forceinline__ bool inside_reach(float d, double reach) {
-    if (reach == INFINITY) return true;
-    return reach > 0.0 && d < (float)(reach * reach);
-}
-
 template <int K>
 __global__ __launch_bounds__(GRID_TPB) void k_outliers_grid(const StatArgs a) {
     const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
     bool fail = false;
-    if (s < a.g.n) {
+    if (s < a.n) {
         const float4 q4 = a.g.sorted[s];
         const f3 q(q4.x, q4.y, q4.z);
         const uint32_t self = __float_as_uint(q4.w);
@@ -109,10 +63,10 @@ __global__ __launch_bounds__(GRID_TPB) void k_outliers_grid(const StatArgs a) {
         u64 best[K];
 #pragma unroll
         for (int b = 0; b < K; ++b) best[b] = EMPTY;
-        // nine runs of three cells; the padding of the row index makes every row of the block valid
+        // for_block27's runs, written out (as in k_normals_grid: the register list is not handed to a lambda)
         for (int dz = -1; dz <= 1; ++dz)
             for (int dy = -1; dy <= 1; ++dy) {
-                const uint32_t r = (uint32_t)(cx + 1) + (uint32_t)a.g.DX * ((uint32_t)(cy + dy + 2) + (uint32_t)a.g.DY * (uint32_t)(cz + dz + 2));
+                const uint32_t r = (uint32_t)(cx + 1) + row_base(a.g, cy + dy, cz + dz);
                 const uint32_t j1 = a.g.row_start[r + 3];
                 for (uint32_t j = a.g.row_start[r]; j < j1; ++j) {
                     const float4 p = a.g.sorted[j];
@@ -123,7 +77,7 @@ __global__ __launch_bounds__(GRID_TPB) void k_outliers_grid(const StatArgs a) {
         u64 kth = EMPTY;
 #pragma unroll
         for (int b = 0; b < K; ++b) if (b == a.m - 1) kth = best[b];
-        if (kth != EMPTY && inside_reach(key_d(kth), block_reach(a, q, cx, cy, cz, 1))) {
+        if (kth != EMPTY && inside_reach(key_d(kth), block_reach(a.g, q, cx, cy, cz, 1, a.margin))) {
             double sum = 0.0;
 #pragma unroll
             for (int b = 0; b < K; ++b) if (b < a.m) sum += sqrt((double)key_d(best[b]));
@@ -131,48 +85,13 @@ __global__ __launch_bounds__(GRID_TPB) void k_outliers_grid(const StatArgs a) {
         } else
             fail = true;
     }
-    // wave-aggregated append to the list of the ring pass
-    const u64 mask = __ballot(fail);
-    if (mask) {
-        const uint32_t lane = threadIdx.x & 63u, leader = (uint32_t)__ffsll((long long)mask) - 1u;
-        uint32_t base = 0;
-        if (lane == leader) base = atomicAdd(a.fail_count, (uint32_t)__popcll(mask));
-        base = __shfl(base, (int)leader, 64);
-        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-        if (fail) a.fail[base + rank] = s;
-    }
+    fail_append(fail, s, a.fail, a.fail_count);   // to the list of the ring pass
 }
 
-// The wave's 64 smallest keys: lane r holds the r-th.  Merged with one key per lane (EMPTY: none): the new keys are sorted across
-// the wave (bitonic, 21 steps), reversed and merged with the list (the element-wise minimum of an ascending and a descending
-// sequence is a bitonic sequence that holds the 64 smallest of both, 6 more steps).
-__device__ __forceinline__ u64 wave_merge(u64 list, u64 key, int lane) {
-    u64 v = key;
-#pragma unroll
-    for (int size = 2; size <= 64; size <<= 1)
-#pragma unroll
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            const u64 o = __shfl_xor(v, stride, 64);
-            const bool keep_min = ((lane & stride) == 0) == ((lane & size) == 0);
-            v = keep_min ? (o < v ? o : v) : (o < v ? v : o);
-        }
-    const u64 r = __shfl(v, 63 - lane, 64);
-    u64 t = list < r ? list : r;
-#pragma unroll
-    for (int stride = 32; stride > 0; stride >>= 1) {
-        const u64 o = __shfl_xor(t, stride, 64);
-        t = (lane & stride) == 0 ? (o < t ? o : t) : (o < t ? t : o);
-    }
-    return t;
-}
-
-// One wavefront per point the grid kernel could not finish (persistent workgroups; the list's length stays on the device).  The
-// block [c - rout, c + rout]^3 grows by half its radius per step; a step reads whole x runs of the rows outside the old block's
-// y-z square and the two x runs left and right of it in the rows inside (one or two row look-ups per row: O(R^2) per step).  The
-// candidates of all lanes' runs are handed out 64 at a time (a wave prefix sum over the run lengths, each lane finding its run by
-// a binary search over the lanes); a batch is merged only when one of its keys is below the current k-th.  The point is finished
-// when the k-th key is closer than the outside of the block, or the block covers the grid (then all n - 1 >= k_eff other points
-// have been scanned).
+// One wavefront per point the grid kernel could not finish (persistent workgroups; the list's length stays on the device): the
+// growing blocks of ring_step, the point itself left out.  A batch is merged only when one of its keys is below the current k-th.
+// The point is finished when the k-th key is closer than the outside of the block, or the block covers the grid (then all
+// n - 1 >= k_eff other points have been scanned).
 __global__ __launch_bounds__(64 * RING_WAVES) void k_outliers_ring(const StatArgs a) {
     const int lane = (int)(threadIdx.x & 63u), wv = (int)(threadIdx.x >> 6);
     const uint32_t total = *a.fail_count, stride_w = gridDim.x * RING_WAVES;
@@ -185,52 +104,13 @@ __global__ __launch_bounds__(64 * RING_WAVES) void k_outliers_ring(const StatArg
         cell_of(a.g, q, cx, cy, cz);
         u64 list = EMPTY;
         for (int rin = -1, rout = 1;; rin = rout, rout += max(1, rout / 2)) {
-            const int y0 = max(cy - rout, 0), y1 = min(cy + rout, a.g.dy - 1), z0 = max(cz - rout, 0), z1 = min(cz + rout, a.g.dz - 1);
-            const int ny = y1 - y0 + 1, rows = ny * (z1 - z0 + 1);
-            const int xo0 = max(cx - rout, 0), xo1 = min(cx + rout, a.g.dx - 1);   // x range of the new block
-            for (int t0 = 0; t0 < rows; t0 += 64) {                                // (wave-uniform)
-                const int t = t0 + lane;
-                uint32_t a0 = 0, la = 0, b0 = 0, lb = 0;                           // up to two runs of this lane's row
-                if (t < rows) {
-                    const int y = y0 + t % ny, z = z0 + t / ny;
-                    const uint32_t row = (uint32_t)a.g.DX * ((uint32_t)(y + 2) + (uint32_t)a.g.DY * (uint32_t)(z + 2)) + 2u;
-                    if (abs(y - cy) > rin || abs(z - cz) > rin) {                  // outside the old block's y-z square: the whole run
-                        a0 = a.g.row_start[row + (uint32_t)xo0];
-                        la = a.g.row_start[row + (uint32_t)xo1 + 1u] - a0;
-                    } else {                                                       // inside: left and right of the old block
-                        if (cx - rin - 1 >= xo0) {
-                            a0 = a.g.row_start[row + (uint32_t)xo0];
-                            la = a.g.row_start[row + (uint32_t)(cx - rin)] - a0;
-                        }
-                        if (cx + rin + 1 <= xo1) {
-                            b0 = a.g.row_start[row + (uint32_t)(cx + rin + 1)];
-                            lb = a.g.row_start[row + (uint32_t)xo1 + 1u] - b0;
-                        }
-                    }
-                }
-                const uint32_t len = la + lb;
-                uint32_t incl = len;
-#pragma unroll
-                for (int d = 1; d < 64; d <<= 1) { const uint32_t o = __shfl_up(incl, d, 64); if (lane >= d) incl += o; }
-                const uint32_t pre = incl - len, cand_total = __shfl(incl, 63, 64);
-                for (uint32_t c0 = 0; c0 < cand_total; c0 += 64) {                 // (wave-uniform)
-                    const uint32_t idx = c0 + (uint32_t)lane;
-                    int o = 0;                                                     // the last lane whose run starts at or before idx
-#pragma unroll
-                    for (int st = 32; st >= 1; st >>= 1) if (__shfl(pre, o + st, 64) <= idx) o += st;
-                    const uint32_t off = idx - __shfl(pre, o, 64), la_o = __shfl(la, o, 64);
-                    const uint32_t a0_o = __shfl(a0, o, 64), b0_o = __shfl(b0, o, 64);
-                    u64 key = EMPTY;
-                    if (idx < cand_total) {
-                        const float4 p = a.g.sorted[off < la_o ? a0_o + off : b0_o + (off - la_o)];
-                        const uint32_t orig = __float_as_uint(p.w);
-                        if (orig != self) key = make_key(flann_d2(q, f3(p.x, p.y, p.z)), orig);
-                    }
-                    const u64 kth = __shfl(list, a.m - 1, 64);
-                    if (__ballot(key < kth)) list = wave_merge(list, key, lane);
-                }
-            }
-            const double reach = block_reach(a, q, cx, cy, cz, rout);
+            ring_step(a.g, cx, cy, cz, rin, rout, lane, [&](bool valid, float4 p) {
+                const uint32_t orig = __float_as_uint(p.w);
+                const u64 key = valid && orig != self ? make_key(flann_d2(q, f3(p.x, p.y, p.z)), orig) : EMPTY;
+                const u64 kth = __shfl(list, a.m - 1, 64);
+                if (__ballot(key < kth)) list = wave_merge(list, key, lane);
+            });
+            const double reach = block_reach(a.g, q, cx, cy, cz, rout, a.margin);
             if (reach == INFINITY) break;
             if (inside_reach(key_d(__shfl(list, a.m - 1, 64)), reach)) break;   // (EMPTY: NaN, not inside)
         }
@@ -244,7 +124,7 @@ __global__ __launch_bounds__(64 * RING_WAVES) void k_outliers_ring(const StatArg
 
 __global__ __launch_bounds__(RAD_TPB) void k_outliers_radius(const RadArgs a) {
     const uint32_t s = blockIdx.x * RAD_TPB + threadIdx.x;
-    if (s >= a.g.n) return;
+    if (s >= a.n) return;
     const float4 q4 = a.g.sorted[s];
     const f3 q(q4.x, q4.y, q4.z);
     const uint32_t self = __float_as_uint(q4.w);
@@ -253,7 +133,7 @@ __global__ __launch_bounds__(RAD_TPB) void k_outliers_radius(const RadArgs a) {
     uint32_t c = 0;
     for (int t = 0; t < 9 && c < a.stop; ++t) {
         const int dy = t % 3 - 1, dz = t / 3 - 1;
-        const uint32_t r = (uint32_t)(cx + 1) + (uint32_t)a.g.DX * ((uint32_t)(cy + dy + 2) + (uint32_t)a.g.DY * (uint32_t)(cz + dz + 2));
+        const uint32_t r = (uint32_t)(cx + 1) + row_base(a.g, cy + dy, cz + dz);   // for_block27's runs, with an early end
         const uint32_t j1 = a.g.row_start[r + 3];
         for (uint32_t j = a.g.row_start[r]; j < j1; ++j) {
             const float4 p = a.g.sorted[j];
@@ -322,27 +202,10 @@ __global__ __launch_bounds__(ROW_TPB) void k_outliers_gather(const uint32_t *__r
     out[w] = in[(size_t)kept[o] * stride + c];
 }
 
-// occ[0] += occupied cells (distinct sorted keys)
-__global__ __launch_bounds__(256) void k_outliers_cells(const uint32_t *__restrict__ keys, uint32_t n, uint32_t *__restrict__ occ) {
-    uint32_t c = 0;
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
-        c += (i == 0 || keys[i] != keys[i - 1]) ? 1u : 0u;
-    for (int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d, 64);
-    if ((threadIdx.x & 63) == 0 && c) atomicAdd(occ, c);
-}
-
 template <int K>
 void launch_search(plade_ctx *ctx, const StatArgs &a) {
-    hipLaunchKernelGGL(k_outliers_grid<K>, dim3(cdiv(a.g.n, GRID_TPB)), dim3(GRID_TPB), 0, ctx->stream, a);
-    hipLaunchKernelGGL(k_outliers_ring, dim3(std::min(cdiv(a.g.n, RING_WAVES), 2048u)), dim3(64 * RING_WAVES), 0, ctx->stream, a);
-}
-
-GridView view_of(const TargetGrid &G, uint32_t n) {
-    GridView g;
-    g.sorted = G.sorted.p; g.row_start = G.row_start.p; g.n = n;
-    g.mnx = G.gp.mnx; g.mny = G.gp.mny; g.mnz = G.gp.mnz; g.inv = G.gp.inv;
-    g.dx = G.gp.dx; g.dy = G.gp.dy; g.dz = G.gp.dz; g.DX = G.DX; g.DY = G.DY;
-    return g;
+    hipLaunchKernelGGL(k_outliers_grid<K>, dim3(cdiv(a.n, GRID_TPB)), dim3(GRID_TPB), 0, ctx->stream, a);
+    hipLaunchKernelGGL(k_outliers_ring, dim3(std::min(cdiv(a.n, RING_WAVES), 2048u)), dim3(64 * RING_WAVES), 0, ctx->stream, a);
 }
 
 }  // namespace
@@ -389,10 +252,6 @@ uint32_t filter_dev(plade_ctx *ctx, OutlierWork &W, const float *d_rows, uint32_
     HIP_TRY(hipEventRecord(W.ev[0], ctx->stream));
     TargetGrid &G = W.grid;
     const bool stat = p.mode == PLADE_OUTLIER_STATISTICAL;
-    const double ex = std::max(1e-9, (double)bbmax[0] - bbmin[0]), ey = std::max(1e-9, (double)bbmax[1] - bbmin[1]),
-                 ez = std::max(1e-9, (double)bbmax[2] - bbmin[2]);
-    double amax = 0.0;
-    for (int t = 0; t < 3; ++t) amax = std::max(amax, std::max(std::fabs((double)bbmin[t]), std::fabs((double)bbmax[t])));
     uint32_t *d_cnt = W.count.ensure(4);   // [0]: the ring list's length, [1]: occupied cells
     uint8_t *d_keep = W.keep.ensure((size_t)n + 4);
     uint32_t *d_flags = W.flags.ensure((size_t)n + 1);
@@ -408,36 +267,13 @@ uint32_t filter_dev(plade_ctx *ctx, OutlierWork &W, const float *d_rows, uint32_
             ctx->fill_async(d_mean, 0, 8);
             HIP_TRY(hipEventRecord(W.ev[1], ctx->stream));
         } else {
-            // cell: k_normals' -- a surface-like cloud spread over the faces of its box has r_k = sqrt(k A / (pi n)); the cell is
-            // 1.5 r_k (an occupied cell holds ~0.7 k points), then adapted to the measured mean occupancy
-            const double area = 2 * (ex * ey + ey * ez + ex * ez), target = 0.7 * k;
-            float cell = (float)(1.5 * std::sqrt((double)k * area / (M_PI * (double)n)));
-            if (!(cell > 0.f) || !std::isfinite(cell)) cell = 1.f;
-            for (int attempt = 0;; ++attempt) {
-                G.build(ctx, d_rows, n, stride, cell, bbmin, bbmax, true);
-                ++W.builds;
-                PLADE_REQUIRE(G.dense, PLADE_EINVAL, "filter_outliers: needs the dense row index (unset PLADE_OVERLAP_INDEX_COMPACT)");
-                if (attempt == 3 || n <= (uint32_t)(4 * k)) break;
-                ctx->fill_async(d_cnt + 1, 0, 4);
-                hipLaunchKernelGGL(k_outliers_cells, dim3(std::min(cdiv(n, 1024), 512u)), dim3(256), 0, ctx->stream, G.keys2.p, n, d_cnt + 1);
-                HIP_TRY(hipGetLastError());
-                uint32_t occ = 0;
-                ctx->d2h(&occ, d_cnt + 1, 4);
-                ctx->sync();
-                const double mean = (double)n / std::max(occ, 1u);
-                const float built = 1.f / G.gp.inv;          // build() enlarges the cell when the cell budget is hit
-                if (mean > 2.0 * target && built <= cell * 1.01f) cell = built * (float)std::max(0.25, std::sqrt(target / mean));   // too coarse
-                else if (mean < 0.5 * target && occ < n) cell = built * (float)std::min(4.0, std::sqrt(target / mean));          // too fine
-                else break;
-            }
+            W.builds = build_knn_grid(ctx, G, d_rows, n, stride, bbmin, bbmax, k, d_cnt + 1, "filter_outliers");
             HIP_TRY(hipEventRecord(W.ev[1], ctx->stream));
             StatArgs a;
             memset(&a, 0, sizeof(a));
-            a.g = view_of(G, n);
-            a.m = m;
-            a.mn[0] = G.gp.mnx; a.mn[1] = G.gp.mny; a.mn[2] = G.gp.mnz;
-            a.cell = 1.0 / (double)G.gp.inv;
-            a.margin = 0.01 * a.cell + 1e-6 * amax;   // fp32 cell assignment: a few ulps of the coordinates, 1 % of a cell on top
+            a.g = view_of(G, "filter_outliers");
+            a.n = n; a.m = m;
+            a.margin = grid_margin(a.g, bbmin, bbmax);
             a.mean = d_mean;
             a.fail = W.fail.ensure(n); a.fail_count = d_cnt;
             if (k <= 8) launch_search<8>(ctx, a);
@@ -459,14 +295,15 @@ uint32_t filter_dev(plade_ctx *ctx, OutlierWork &W, const float *d_rows, uint32_
         HIP_TRY(hipMemcpyAsync(&W.h_count, d_cnt, 4, hipMemcpyDeviceToHost, ctx->stream));
     } else {
         const float r = (float)p.radius;
+        double amax = 0.0;
+        for (int t = 0; t < 3; ++t) amax = std::max(amax, std::max(std::fabs((double)bbmin[t]), std::fabs((double)bbmax[t])));
         G.build(ctx, d_rows, n, stride, (float)(1.03 * (double)r + 4e-6 * amax), bbmin, bbmax, true);
         ++W.builds;
-        PLADE_REQUIRE(G.dense, PLADE_EINVAL, "filter_outliers: needs the dense row index (unset PLADE_OVERLAP_INDEX_COMPACT)");
         HIP_TRY(hipEventRecord(W.ev[1], ctx->stream));
         RadArgs a;
         memset(&a, 0, sizeof(a));
-        a.g = view_of(G, n);
-        a.r2 = r * r;
+        a.g = view_of(G, "filter_outliers");
+        a.n = n; a.r2 = r * r;
         a.min_nb = (uint32_t)p.min_neighbours;
         a.stop = want_values ? 0xffffffffu : a.min_nb;
         a.count = want_values ? W.nbr_count.ensure(n) : nullptr;
@@ -536,10 +373,8 @@ extern "C" int plade_filter_outliers(plade_ctx *ctx, const float *rows, uint32_t
         if (params) p = *params; else plade_outlier_default_params(&p);
         check_params(n, stride, p);
         OutlierWork &W = work_of(ctx);
-        W.in.ensure((size_t)n * stride + 4);
-        HIP_TRY(hipMemcpyAsync(W.in.p, rows, (size_t)n * stride * 4, hipMemcpyHostToDevice, ctx->stream));
         float mn[3], mx[3];
-        bbox_host(ctx, W.in.p, n, stride, mn, mx);   // (waits; refuses non-finite coordinates)
+        upload_rows(ctx, W.in, rows, n, stride, mn, mx);
         const bool stat = p.mode == PLADE_OUTLIER_STATISTICAL;
         const bool want_values = stat ? mean_dist_out != nullptr : count_out != nullptr;
         const uint32_t total = filter_dev(ctx, W, W.in.p, n, stride, mn, mx, p, want_values,

@@ -785,6 +785,12 @@ void bbox_host(plade_ctx *ctx, const float *d_xyz, uint32_t n, uint32_t stride, 
     ctx->sync();
     bbox_decode(out, mn, mx);
 }
+
+void upload_rows(plade_ctx *ctx, DBuf<float> &buf, const float *h, uint32_t n, uint32_t stride, float mn[3], float mx[3]) {
+    buf.ensure((size_t)n * stride + 4);
+    HIP_TRY(hipMemcpyAsync(buf.p, h, (size_t)n * stride * 4, hipMemcpyHostToDevice, ctx->stream));
+    bbox_host(ctx, buf.p, n, stride, mn, mx);
+}
 }  // namespace plade
 
 using namespace plade;

@@ -12,6 +12,7 @@ from plade_amd.plyio import write_ply
 from plade_amd.synth import make_pair
 import distance_restate as R
 import icp_restate as IR
+import ring_scene
 
 pytestmark = pytest.mark.gpu
 
@@ -174,6 +175,15 @@ def test_ring_pass_is_exercised_and_exact(dctx):
     for d in (0.1 * D, 2 * D):
         _check(dctx, tg, src, d, T=T)
         assert dctx.stats()["distances_ring_queries"] > 0
+
+
+@pytest.mark.parametrize("d", ring_scene.RADII)
+def test_the_ring_walk_does_everything(dctx, d):
+    """ring_scene.py: the isolated probes' blocks span more than 64 rows, grow at least three times, have whole-row and side runs
+    and are clipped by the grid's edge (test_ring_scene_host.py).  The bounds lie below and above the probes' distance."""
+    idx = _check(dctx, ring_scene.target(), ring_scene.probes(), d)[0]
+    assert dctx.stats()["distances_ring_queries"] >= len(ring_scene.PROBES)
+    assert (idx[256:] >= 0).all() == (d > ring_scene.GAP) and (idx[:256] >= 0).all()
 
 
 def test_plane_term_with_nan_normals(dctx):

@@ -9,6 +9,7 @@ import pytest
 
 import plade_amd
 import icp_restate as IR
+import ring_scene
 from plade_amd.synth import make_pair, sample_scene
 from conftest import GT_TOL, ORIENTED
 from test_normals_host import PARENT_RESULT, PARENT_STDERR, PARENT_STDOUT
@@ -153,6 +154,16 @@ def test_far_outliers_take_the_ring_path(nctx):
     assert nctx.stats()["normals_ring_queries"] >= len(far)
     q = np.concatenate([np.arange(7000, 7005), gen_queries(len(P), 2000, seed=9)])
     check_against_ref(P, out, curv, nbr, np.unique(q), 16)
+
+
+@pytest.mark.parametrize("k", [8, 64])
+def test_the_ring_walk_does_everything(nctx, k):
+    """ring_scene.py: the isolated points' blocks span more than 64 rows, grow at least three times, have whole-row and side runs
+    and are clipped by the grid's edge (test_ring_scene_host.py)."""
+    P = ring_scene.scene()
+    out, curv, nbr = nctx.estimate_normals(P, k=k, curvature=True, neighbours=True)
+    assert nctx.stats()["normals_ring_queries"] >= ring_scene.N_FAR
+    check_against_ref(P, out, curv, nbr, np.arange(len(P)), k)
 
 
 # ---- normals, orientation, invariance -----------------------------------------------------------------------------------------

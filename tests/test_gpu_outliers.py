@@ -16,6 +16,7 @@ import pytest
 import plade_amd
 import icp_restate as IR
 import outlier_restate as R
+import ring_scene
 from plade_amd.synth import make_pair, sample_scene
 from conftest import GT_TOL, ORIENTED
 from test_normals_host import PARENT_RESULT, PARENT_STDERR, PARENT_STDOUT
@@ -177,6 +178,22 @@ def test_far_outliers_take_the_ring_pass(octx):
     info, _ = check_statistical(octx, P, 16, 1.0, keys, "far")
     assert octx.stats()["outliers_ring_queries"] >= len(far)
     assert not info["keep"][7000:7005].any()
+
+
+@pytest.fixture(scope="module")
+def ring_keys():
+    return R.neighbours(ring_scene.scene(), kmax=64)[0]
+
+
+@pytest.mark.parametrize("k", [1, 16, 64])
+def test_the_ring_walk_does_everything(octx, ring_keys, k):
+    """ring_scene.py: the isolated points' blocks span more than 64 rows, grow at least three times, have whole-row and side runs
+    and are clipped by the grid's edge (test_ring_scene_host.py)."""
+    P = ring_scene.scene()
+    ref = R.statistical(P, k, 1.0, keys=ring_keys)
+    assert R.nearest_gap(ref["m"], ref["threshold"]) > GAP
+    check_statistical(octx, P, k, 1.0, ring_keys, "ring scene")
+    assert octx.stats()["outliers_ring_queries"] >= ring_scene.N_FAR
 
 
 def test_tiny_clouds(octx):

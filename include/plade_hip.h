@@ -479,6 +479,53 @@ int plade_filter_outliers(plade_ctx *ctx, const float *rows, uint32_t n, uint32_
 int plade_cloud_filter_outliers_dev(plade_ctx *ctx, plade_cloud *cloud, const plade_outlier_params *params, plade_cloud **out,
                                     uint8_t *keep_out, uint32_t *kept_index_out, plade_outlier_summary *summary);
 
+/* ---- connected components: dropping dense blobs that do not belong to the structure (no reference counterpart; PCL ships it as
+ * EuclideanClusterExtraction, Open3D as cluster_dbscan) ----------------------------------------------------------------------------
+ * Semantics (plade_amd/csrc/components.h).  Input: n >= 1 points, rows of `stride` >= 3 floats, x y z first,
+ * all coordinates finite.  d(i, j) = the fp32 FLANN L2 of (p_i, p_j), ((dx*dx + dy*dy) + dz*dz).
+ *   edge         i ~ j when i != j and d(i, j) < (float)radius * (float)radius (the strict `<` of the radius filter): duplicates are
+ *                connected, a pair at exactly radius^2 is not.
+ *   components   the connected components of that graph, an exact set; ids 0 .. C - 1 in ascending order of the component's smallest
+ *                original index.
+ *   selection    component c passes when min_size <= size[c] and (max_size = 0 or size[c] <= max_size).  keep_largest = m > 0: only
+ *                the m passing components that come first in the order (size descending, id ascending) are kept; 0: all passing
+ *                ones.  A point is kept when its component is.
+ *   output       each array may be NULL.  label_out: n int32, the id of each point's component; size_out: the C sizes (room for
+ *                n); keep_out: n bytes 0 / 1; kept_index_out: the kept original indices, ascending (room for n); rows_out: the kept
+ *                rows in that order, every float copied bit for bit (room for n rows; may be `rows` itself); summary: n,
+ *                components = C, kept_components, kept, largest = the largest size.  The result depends on the point set and the
+ *                parameters only, and is the same bits on every run.
+ * Errors: PLADE_EINVAL for n = 0, stride < 3, a NULL cloud, a non-finite coordinate, radius <= 0 or not finite (or its fp32 square
+ * not finite), min_size < 1, max_size in (0, min_size), keep_largest < 0; the context stays usable.  A
+ * selection that keeps nothing is PLADE_OK with kept = 0.  A radius that is tiny against the cloud's extent (one far point is
+ * enough) is not refused: the grid's cell grows until 48e6 cells hold the cloud, and every call then fills a row table of up to
+ * 192 MB -- crop such a cloud first.  plade_stats_get then reports components_grid_s,
+ * components_link_s (the union-find over the edges), components_label_s (roots, ids, sizes, selection), components_compact_s (scan,
+ * kept list and row gather; HIP events on the context's stream), components_count and components_kept. */
+typedef struct plade_component_params {
+    double radius;               /* must be set (> 0): there is no automatic value */
+    int32_t min_size;            /* >= 1 */
+    int32_t max_size;            /* 0: no upper bound, else >= min_size */
+    int32_t keep_largest;        /* 0: every passing component, m > 0: the m largest passing ones */
+    int32_t reserved;            /* 0 */
+} plade_component_params;
+typedef struct plade_component_summary {
+    uint64_t n, components, kept_components, kept;
+    uint32_t largest;
+    uint32_t reserved;           /* 0 */
+} plade_component_summary;
+/* The defaults: radius = 0 (unset), min_size = 1, max_size = 0, keep_largest = 0.  Needs no GPU. */
+void plade_component_default_params(plade_component_params *p);
+int plade_label_components(plade_ctx *ctx, const float *rows, uint32_t n, uint32_t stride, const plade_component_params *params,
+                           int32_t *label_out, uint32_t *size_out, uint8_t *keep_out, uint32_t *kept_index_out, float *rows_out,
+                           plade_component_summary *summary);
+/* The same on a resident cloud (plade_cloud_upload / plade_cloud_upload_xyz; rows x y z nx ny nz) into a NEW resident cloud of the
+ * kept points, a resident cloud like any other: the point data makes no host round trip.  The same label, kept_index and summary
+ * bits as plade_label_components on the cloud's rows.  PLADE_EFAIL (summary filled, *out NULL) when nothing is kept: a resident
+ * cloud has no empty form.  Free both clouds with plade_cloud_free. */
+int plade_cloud_filter_components_dev(plade_ctx *ctx, plade_cloud *cloud, const plade_component_params *params, plade_cloud **out,
+                                      int32_t *label_out, uint32_t *kept_index_out, plade_component_summary *summary);
+
 /* ---- merging registered clouds: the step a scan-to-scan chain ends with (no reference counterpart) -----------------------------
  * Semantics (plade_amd/csrc/merge.h).  k clouds, 1 <= k <= 16; cloud c: n_c >= 1 rows x y z nx ny nz with
  * finite coordinates (the normals may be NaN); T: k row-major fp32 4 x 4 matrices, cloud c -> the output frame (NULL: identities,

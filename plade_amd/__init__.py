@@ -31,6 +31,7 @@ ABI_SYMBOLS = [
     "plade_cloud_distances", "plade_cloud_distances_dev",
     "plade_outlier_default_params", "plade_filter_outliers", "plade_cloud_filter_outliers_dev",
     "plade_merge_clouds", "plade_merge_clouds_dev", "plade_cloud_download",
+    "plade_component_default_params", "plade_label_components", "plade_cloud_filter_components_dev",
 ]
 
 
@@ -84,6 +85,19 @@ class MergeSummary(C.Structure):
     """plade_merge_summary: points in, rows out, rows seen by two or more clouds, the largest per-voxel count."""
     _fields_ = [("n_in", C.c_uint64), ("n_out", C.c_uint64), ("n_shared", C.c_uint64), ("max_count", C.c_uint32),
                 ("reserved", C.c_uint32)]
+
+
+class ComponentParams(C.Structure):
+    """plade_component_params: radius of the edges, min_size / max_size (0: no bound) of a passing component, keep_largest (0: every
+    passing component)."""
+    _fields_ = [("radius", C.c_double), ("min_size", C.c_int32), ("max_size", C.c_int32), ("keep_largest", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class ComponentSummary(C.Structure):
+    """plade_component_summary: n, components, kept_components, kept (points), largest (size)."""
+    _fields_ = [("n", C.c_uint64), ("components", C.c_uint64), ("kept_components", C.c_uint64), ("kept", C.c_uint64),
+                ("largest", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 PLADE_OUTLIER_STATISTICAL, PLADE_OUTLIER_RADIUS = 0, 1
@@ -162,6 +176,9 @@ def load_library(path=LIB_PATH):
     sig("plade_merge_clouds", argtypes=[p, u32, p, p, p, f, p, p, p, C.POINTER(MergeSummary)])
     sig("plade_merge_clouds_dev", argtypes=[p, u32, p, p, f, C.POINTER(p), p, p, C.POINTER(MergeSummary)])
     sig("plade_cloud_download", argtypes=[p, p, p, u32, C.POINTER(u32)])
+    sig("plade_component_default_params", argtypes=[C.POINTER(ComponentParams)], restype=None)
+    sig("plade_label_components", argtypes=[p, p, u32, u32, C.POINTER(ComponentParams), p, p, p, p, p, C.POINTER(ComponentSummary)])
+    sig("plade_cloud_filter_components_dev", argtypes=[p, p, C.POINTER(ComponentParams), C.POINTER(p), p, p, C.POINTER(ComponentSummary)])
     sig("plade_sort_segments", argtypes=[p, p, p, p, u32, C.c_int, p, p])
     sig("plade_set_candidate_shard", argtypes=[p, u32, u32, u32, EXCHANGE_FN, p])
     sig("plade_registration_minsupport", argtypes=[p, p, u32, p, u32, i32, i32, p])
@@ -261,6 +278,31 @@ def _outlier_params(mode, k, alpha, radius, min_neighbours):
 def _outlier_info(summ, keep):
     info = {k: getattr(summ, k) for k, _ in OutlierSummary._fields_}
     info["keep"] = keep.view(np.bool_)
+    return info
+
+
+def component_default_params():
+    """plade_component_default_params (pure: needs no GPU) as a dict of the plade_component_params fields."""
+    prm = ComponentParams()
+    load_library().plade_component_default_params(C.byref(prm))
+    return {k: getattr(prm, k) for k, _ in ComponentParams._fields_ if k != "reserved"}
+
+
+def _component_params(radius, min_size, max_size, keep_largest):
+    prm = ComponentParams()
+    load_library().plade_component_default_params(C.byref(prm))
+    prm.radius = float(radius)
+    prm.min_size, prm.max_size, prm.keep_largest = int(min_size), int(max_size), int(keep_largest)
+    return prm
+
+
+def _component_info(summ, label, size, keep):
+    info = {k: getattr(summ, k) for k, _ in ComponentSummary._fields_ if k != "reserved"}
+    info["label"] = label
+    if size is not None:
+        info["size"] = size[:summ.components].copy()
+    if keep is not None:
+        info["keep"] = keep.view(np.bool_)
     return info
 
 
@@ -843,6 +885,41 @@ class Context:
         self._check(self.L.plade_cloud_filter_outliers_dev(self.h, cloud.h, C.byref(prm), C.byref(h), _ptr(keep), _ptr(kept), C.byref(summ)))
         out = Cloud(self, None, handle=(int(summ.kept), h))
         return (out, kept[:summ.kept].copy(), _outlier_info(summ, keep)) if info else out
+
+    # ---- connected components --------------------------------------------------------------------
+    def connected_components(self, points, radius, min_size=1, max_size=0, keep_largest=0):
+        """plade_label_components: the connected components of the graph "closer than radius" (fp32 squared distance, strict <)
+        of an (N, >= 3) float32 array whose first three columns are x y z, and the points of the components that pass min_size <=
+        size <= max_size (0: no upper bound), with keep_largest = m > 0 only of the m largest passing ones (ties: the smaller id).
+        Returns (filtered, kept_index, info): the kept rows in their original order with every column copied bit for bit, their
+        original indices (uint32, ascending), and a dict with n, components, kept_components, kept, largest, label (N int32: ids
+        in ascending order of a component's smallest index), size (components uint32) and keep (N bools)."""
+        a, n, stride = _xyz_view(points)
+        prm = _component_params(radius, min_size, max_size, keep_largest)
+        label = np.empty(n, np.int32)
+        size = np.empty(n, np.uint32)
+        keep = np.zeros(n, np.uint8)
+        kept = np.empty(n, np.uint32)
+        rows = np.empty((n, stride), np.float32)
+        summ = ComponentSummary()
+        self._check(self.L.plade_label_components(self.h, _ptr(a), n, stride, C.byref(prm), _ptr(label), _ptr(size), _ptr(keep),
+                                                  _ptr(kept), _ptr(rows), C.byref(summ)))
+        return rows[:summ.kept].copy(), kept[:summ.kept].copy(), _component_info(summ, label, size, keep)
+
+    def filter_components_dev(self, cloud, radius, min_size=1, max_size=0, keep_largest=0, info=False):
+        """plade_cloud_filter_components_dev: connected_components on a resident cloud (upload, upload_xyz) into a new resident
+        Cloud of the kept points; the point data makes no host round trip.  With info also (kept_index, info dict): the same
+        bits as connected_components gives (label, no size and keep arrays).  Raises PladeError (PLADE_EFAIL) when nothing is
+        kept."""
+        prm = _component_params(radius, min_size, max_size, keep_largest)
+        label = np.empty(cloud.n, np.int32) if info else None
+        kept = np.empty(cloud.n, np.uint32) if info else None
+        summ = ComponentSummary()
+        h = C.c_void_p()
+        self._check(self.L.plade_cloud_filter_components_dev(self.h, cloud.h, C.byref(prm), C.byref(h), _ptr(label), _ptr(kept),
+                                                             C.byref(summ)))
+        out = Cloud(self, None, handle=(int(summ.kept), h))
+        return (out, kept[:summ.kept].copy(), _component_info(summ, label, None, None)) if info else out
 
     # ---- merging registered clouds ---------------------------------------------------------------
     @staticmethod

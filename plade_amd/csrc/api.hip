@@ -1,5 +1,6 @@
 // plade_amd/csrc/api.hip -- context management and instrumentation entry points of the C ABI.
 #include "ctx.h"
+#include "components.h"
 #include "distances.h"
 #include "exact_sort.h"
 #include "icp.h"
@@ -141,6 +142,7 @@ extern "C" void plade_ctx_destroy(plade_ctx *ctx) {
     if (ctx->dist_work) plade::dist_work_destroy(ctx->dist_work);
     if (ctx->outlier_work) plade::outlier_work_destroy(ctx->outlier_work);
     if (ctx->merge_work) plade::merge_work_destroy(ctx->merge_work);
+    if (ctx->component_work) plade::component_work_destroy(ctx->component_work);
     (void)hipStreamDestroy(ctx->stream);
     if (ctx->pf.stream) { (void)hipStreamSynchronize(ctx->pf.stream); (void)hipStreamDestroy(ctx->pf.stream); }
     delete ctx;

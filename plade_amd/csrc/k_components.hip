@@ -1,0 +1,349 @@
+// plade_amd/csrc/k_components.hip -- connected components of the radius graph on gfx950 (semantics: components.h).
+//
+// Layout
+//   grid     the dense row index of TargetGrid with the radius filter's cell, 1.03 r + 4e-6 max|coordinate| (the rule of DESIGN.md
+//            section 10): the 27-cell block around a point holds everything closer than r.
+//   link     k_cc_link: one lane per point in the grid's sorted order walks the nine runs of its block and tests only the
+//            candidates at a smaller sorted position, so every undirected edge is tested once.  An edge unites the two original
+//            indices in parent[] (uint32 by original index, parent[i] = i at the start) by lock-free min-hooking: find both roots,
+//            atomicMin(&parent[hi], lo) at agent scope with hi > lo; a returned value other than hi means somebody hooked hi first,
+//            and the union goes on with (that value, lo).  Parents only ever decrease: every loop ends, no lane waits for another,
+//            and at the end every root is the smallest original index of its component -- whatever the order of the unions.
+//            parent[] is read with relaxed agent-scope atomic loads; a stale value costs a round, never a link, because the
+//            atomicMin's return value decides.
+//   flatten  k_cc_flatten (next launch): root[i] by walking up, flags[i] = (root[i] == i).  compact_flags over the flags gives C and,
+//            by its exclusive positions, the id of every root: ascending root = ascending smallest index.
+//   label    k_cc_label_size: label[i] = id[root[i]]; the sizes by integer atomics, one per distinct id of a wavefront.
+//   select   k_cc_pass; with keep_largest the keys ~size << 32 | id (all ones in the high word: does not pass) through the stable
+//            sort_pairs_u64 and k_cc_mark_first; k_cc_summary (largest, kept components); k_cc_keep, compact_flags, k_cc_gather.
+#include "components.h"
+#include "grid_walk.h"
+#include "prims.h"
+#include "stages.h"
+#include "voxel.h"
+#include <functional>
+
+namespace plade {
+
+namespace {
+
+constexpr int LINK_TPB = 256, ROW_TPB = 256;
+constexpr uint32_t NO_PASS = 0xffffffffu;   // high word of a sort key: the component does not pass
+
+struct LinkArgs {
+    GridView g;
+    uint32_t n;
+    float r2;                        // (float)r * (float)r
+    uint32_t *parent;                // by original index
+};
+
+__device__ __forceinline__ uint32_t parent_of(const uint32_t *parent, uint32_t x) {
+    return __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// a, b: any two ancestors (or the points themselves) of the two ends
+__device__ __forceinline__ void unite(uint32_t *parent, uint32_t a, uint32_t b) {
+    for (;;) {
+        for (uint32_t p = parent_of(parent, a); p != a; p = parent_of(parent, a)) a = p;
+        for (uint32_t p = parent_of(parent, b); p != b; p = parent_of(parent, b)) b = p;
+        if (a == b) return;
+        const uint32_t hi = max(a, b), lo = min(a, b);
+        const uint32_t old = __hip_atomic_fetch_min(parent + hi, lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (old == hi) return;
+        a = old; b = lo;             // hi had been hooked to `old` already (parent[hi] is now min(old, lo)): old and lo remain to be united
+    }
+}
+
+__global__ __launch_bounds__(ROW_TPB) void k_cc_init(uint32_t *__restrict__ parent, uint32_t n) {
+    const uint32_t i = blockIdx.x * ROW_TPB + threadIdx.x;
+    if (i < n) parent[i] = i;
+}
+
+__global__ __launch_bounds__(LINK_TPB) void k_cc_link(const LinkArgs a) {
+    const uint32_t s = blockIdx.x * LINK_TPB + threadIdx.x;
+    if (s >= a.n) return;
+    const float4 q4 = a.g.sorted[s];
+    const f3 q(q4.x, q4.y, q4.z);
+    const uint32_t self = __float_as_uint(q4.w);
+    int cx, cy, cz;
+    cell_of(a.g, q, cx, cy, cz);
+    for_block27(a.g, cx, cy, cz, [&](uint32_t j0, uint32_t j1) {
+        j1 = min(j1, s);             // the sorted positions below this lane's own (runs of later rows are empty)
+        for (uint32_t j = j0; j < j1; ++j) {
+            const float4 p = a.g.sorted[j];
+            if (flann_d2(q, f3(p.x, p.y, p.z)) < a.r2) {
+                const uint32_t other = __float_as_uint(p.w);
+                const uint32_t pa = parent_of(a.parent, self), pb = parent_of(a.parent, other);
+                if (pa != pb) unite(a.parent, pa, pb);   // (the same parent: already in one tree)
+            }
+        }
+    });
+}
+
+__global__ __launch_bounds__(ROW_TPB) void k_cc_flatten(const uint32_t *__restrict__ parent, uint32_t n, uint32_t *__restrict__ root,
+                                                        uint32_t *__restrict__ flags) {
+    const uint32_t i = blockIdx.x * ROW_TPB + threadIdx.x;
+    if (i >= n) return;
+    uint32_t x = i;
+    for (uint32_t p = parent[x]; p != x; p = parent[x]) x = p;
+    root[i] = x;
+    flags[i] = x == i ? 1u : 0u;
+}
+
+// label[i] = id[root[i]]; size[id] += 1, one atomic per distinct id of the wavefront (a room-sized component would otherwise put
+// every point's atomic on one address).  Integer sums: the same in any order
+__global__ __launch_bounds__(ROW_TPB) void k_cc_label_size(const uint32_t *__restrict__ root, const uint32_t *__restrict__ id, uint32_t n,
+                                                           int32_t *__restrict__ label, uint32_t *__restrict__ size) {
+    const uint32_t i = blockIdx.x * ROW_TPB + threadIdx.x, lane = threadIdx.x & 63u;
+    const bool valid = i < n;
+    uint32_t c = 0;
+    if (valid) {
+        c = id[root[i]];
+        label[i] = (int32_t)c;
+    }
+    u64 todo = __ballot(valid);
+    while (todo) {                   // (wave-uniform)
+        const uint32_t leader = (uint32_t)__ffsll((long long)todo) - 1u;
+        const uint32_t lc = (uint32_t)__builtin_amdgcn_readlane((int)c, (int)leader);
+        const u64 same = __ballot(valid && c == lc);
+        if (lane == leader) atomicAdd(size + lc, (uint32_t)__popcll(same));
+        todo &= ~same;
+    }
+}
+
+// kept[c] = passes (keep_largest = 0), or the sort key of c: ~size << 32 | c when it passes, NO_PASS << 32 | c when not
+__global__ __launch_bounds__(ROW_TPB) void k_cc_pass(const uint32_t *__restrict__ size, uint32_t C, uint32_t min_size, uint32_t max_size,
+                                                     uint8_t *__restrict__ kept, u64 *__restrict__ key, uint32_t *__restrict__ val) {
+    const uint32_t c = blockIdx.x * ROW_TPB + threadIdx.x;
+    if (c >= C) return;
+    const uint32_t sz = size[c];
+    const bool pass = sz >= min_size && (max_size == 0u || sz <= max_size);
+    if (key) {
+        key[c] = ((u64)(pass ? ~sz : NO_PASS) << 32) | (u64)c;   // (sz >= 1: ~sz < NO_PASS)
+        val[c] = c;
+        kept[c] = 0;
+    } else
+        kept[c] = pass ? 1 : 0;
+}
+
+// the first m entries of the sorted keys that pass
+__global__ __launch_bounds__(ROW_TPB) void k_cc_mark_first(const u64 *__restrict__ key, const uint32_t *__restrict__ val, uint32_t C, uint32_t m,
+                                                           uint8_t *__restrict__ kept) {
+    const uint32_t t = blockIdx.x * ROW_TPB + threadIdx.x;
+    if (t >= C || t >= m) return;
+    if ((uint32_t)(key[t] >> 32) != NO_PASS) kept[val[t]] = 1;
+}
+
+// out[0] = the largest size, out[1] = the number of kept components (integer atomics, one pair per wavefront)
+__global__ __launch_bounds__(ROW_TPB) void k_cc_summary(const uint32_t *__restrict__ size, const uint8_t *__restrict__ kept, uint32_t C,
+                                                        uint32_t *__restrict__ out) {
+    const uint32_t c = blockIdx.x * ROW_TPB + threadIdx.x;
+    uint32_t big = c < C ? size[c] : 0u;
+    const u64 k = __ballot(c < C && kept[c]);
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) big = max(big, (uint32_t)__shfl_xor((int)big, o, 64));
+    if ((threadIdx.x & 63u) == 0) {
+        atomicMax(out, big);
+        if (k) atomicAdd(out + 1, (uint32_t)__popcll(k));
+    }
+}
+
+__global__ __launch_bounds__(ROW_TPB) void k_cc_keep(const int32_t *__restrict__ label, const uint8_t *__restrict__ kept, uint32_t n,
+                                                     uint8_t *__restrict__ keep, uint32_t *__restrict__ flags) {
+    const uint32_t i = blockIdx.x * ROW_TPB + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t k = kept[label[i]] ? 1u : 0u;
+    keep[i] = (uint8_t)k;
+    flags[i] = k;
+}
+
+// out row o = in row kept[o], word by word (the gather of k_outliers.hip: whatever the floats hold keeps its bits)
+__global__ __launch_bounds__(ROW_TPB) void k_cc_gather(const uint32_t *__restrict__ in, uint32_t stride, const uint32_t *__restrict__ kept,
+                                                       uint32_t total, uint32_t *__restrict__ out) {
+    const size_t w = (size_t)blockIdx.x * ROW_TPB + threadIdx.x;
+    if (w >= (size_t)total * stride) return;
+    const uint32_t o = (uint32_t)(w / stride), c = (uint32_t)(w - (size_t)o * stride);
+    out[w] = in[(size_t)kept[o] * stride + c];
+}
+
+}  // namespace
+
+struct ComponentWork {
+    TargetGrid grid;
+    DBuf<uint32_t> parent, root, flags, root_pos, root_list, pos, kept, size, count, sort_val, sort_val2;
+    DBuf<unsigned long long> sort_key, sort_key2;
+    DBuf<int32_t> label;
+    DBuf<uint8_t> keep, comp_kept;
+    DBuf<float> in, out;             // the host-pointer entry point's device copies (grow-only)
+    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    uint32_t h_count[2] = {0, 0};    // the largest size, the kept components
+    uint32_t components = 0;
+    ~ComponentWork() { for (hipEvent_t &e : ev) if (e) (void)hipEventDestroy(e); }
+};
+ComponentWork *component_work_create() { return new ComponentWork; }
+void component_work_destroy(ComponentWork *w) { delete w; }
+
+namespace {
+
+void check_params(uint32_t n, uint32_t stride, const plade_component_params &p) {
+    PLADE_REQUIRE(n >= 1, PLADE_EINVAL, "label_components: the cloud is empty (n = 0)");
+    PLADE_REQUIRE(stride >= 3, PLADE_EINVAL, "label_components: stride must be >= 3 floats");
+    const float r = (float)p.radius;
+    PLADE_REQUIRE(std::isfinite(p.radius) && std::isfinite(r) && r > 0.f && std::isfinite(r * r), PLADE_EINVAL,
+                  "label_components: radius must be finite and > 0");
+    PLADE_REQUIRE(p.min_size >= 1, PLADE_EINVAL, "label_components: min_size must be >= 1");
+    PLADE_REQUIRE(p.max_size == 0 || p.max_size >= p.min_size, PLADE_EINVAL, "label_components: max_size must be 0 (no bound) or >= min_size");
+    PLADE_REQUIRE(p.keep_largest >= 0, PLADE_EINVAL, "label_components: keep_largest must be >= 0");
+}
+
+// The components of a device cloud of `stride` floats per point with a known bounding box.  Leaves label, size, keep and the kept
+// list in W, gathers the kept rows into dst(kept) -- not called when nothing is kept --, waits, fills the summary and the stats.
+// Returns the number of kept points.
+uint32_t components_dev(plade_ctx *ctx, ComponentWork &W, const float *d_rows, uint32_t n, uint32_t stride, const float bbmin[3],
+                        const float bbmax[3], const plade_component_params &p, const std::function<float *(uint32_t)> &dst,
+                        plade_component_summary *summary) {
+    for (hipEvent_t &e : W.ev) if (!e) HIP_TRY(hipEventCreate(&e));
+    HIP_TRY(hipEventRecord(W.ev[0], ctx->stream));
+    TargetGrid &G = W.grid;
+    const float r = (float)p.radius;
+    double amax = 0.0;
+    for (int t = 0; t < 3; ++t) amax = std::max(amax, std::max(std::fabs((double)bbmin[t]), std::fabs((double)bbmax[t])));
+    G.build(ctx, d_rows, n, stride, (float)(1.03 * (double)r + 4e-6 * amax), bbmin, bbmax, true);
+    HIP_TRY(hipEventRecord(W.ev[1], ctx->stream));
+
+    LinkArgs a;
+    memset(&a, 0, sizeof(a));
+    a.g = view_of(G, "label_components");
+    a.n = n; a.r2 = r * r;
+    a.parent = W.parent.ensure(n);
+    hipLaunchKernelGGL(k_cc_init, dim3(cdiv(n, ROW_TPB)), dim3(ROW_TPB), 0, ctx->stream, a.parent, n);
+    hipLaunchKernelGGL(k_cc_link, dim3(cdiv(n, LINK_TPB)), dim3(LINK_TPB), 0, ctx->stream, a);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(W.ev[2], ctx->stream));
+
+    uint32_t *d_root = W.root.ensure(n), *d_flags = W.flags.ensure((size_t)n + 1), *d_size = W.size.ensure(n), *d_cnt = W.count.ensure(4);
+    int32_t *d_label = W.label.ensure(n);
+    uint8_t *d_keep = W.keep.ensure((size_t)n + 4), *d_ckept = W.comp_kept.ensure((size_t)n + 4);
+    ctx->fill_async(d_flags + n, 0, 4);    // compact_flags scans n + 1 entries
+    ctx->fill_async(d_size, 0, (size_t)n * 4);
+    ctx->fill_async(d_cnt, 0, 16);
+    hipLaunchKernelGGL(k_cc_flatten, dim3(cdiv(n, ROW_TPB)), dim3(ROW_TPB), 0, ctx->stream, a.parent, n, d_root, d_flags);
+    HIP_TRY(hipGetLastError());
+    const uint32_t C = compact_flags(ctx, d_flags, n, W.root_pos, W.root_list);   // (waits for the count)
+    W.components = C;
+    hipLaunchKernelGGL(k_cc_label_size, dim3(cdiv(n, ROW_TPB)), dim3(ROW_TPB), 0, ctx->stream, d_root, W.root_pos.p, n, d_label, d_size);
+    const dim3 cgrid(cdiv(C, ROW_TPB));
+    if (p.keep_largest > 0) {
+        unsigned long long *d_key = W.sort_key.ensure(C), *d_key2 = W.sort_key2.ensure(C);
+        uint32_t *d_val = W.sort_val.ensure(C), *d_val2 = W.sort_val2.ensure(C);
+        hipLaunchKernelGGL(k_cc_pass, cgrid, dim3(ROW_TPB), 0, ctx->stream, d_size, C, (uint32_t)p.min_size, (uint32_t)p.max_size, d_ckept,
+                           d_key, d_val);
+        HIP_TRY(hipGetLastError());
+        sort_pairs_u64(ctx, reinterpret_cast<const uint64_t *>(d_key), reinterpret_cast<uint64_t *>(d_key2), d_val, d_val2, C, 64);
+        hipLaunchKernelGGL(k_cc_mark_first, cgrid, dim3(ROW_TPB), 0, ctx->stream, d_key2, d_val2, C, (uint32_t)p.keep_largest, d_ckept);
+    } else
+        hipLaunchKernelGGL(k_cc_pass, cgrid, dim3(ROW_TPB), 0, ctx->stream, d_size, C, (uint32_t)p.min_size, (uint32_t)p.max_size, d_ckept,
+                           (u64 *)nullptr, (uint32_t *)nullptr);
+    hipLaunchKernelGGL(k_cc_summary, cgrid, dim3(ROW_TPB), 0, ctx->stream, d_size, d_ckept, C, d_cnt);
+    hipLaunchKernelGGL(k_cc_keep, dim3(cdiv(n, ROW_TPB)), dim3(ROW_TPB), 0, ctx->stream, d_label, d_ckept, n, d_keep, d_flags);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(W.h_count, d_cnt, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipEventRecord(W.ev[3], ctx->stream));
+
+    const uint32_t total = compact_flags(ctx, d_flags, n, W.pos, W.kept);   // (waits for the count)
+    if (total) {
+        float *d_out = dst(total);
+        const size_t words = (size_t)total * stride;
+        hipLaunchKernelGGL(k_cc_gather, dim3(cdiv(words, ROW_TPB)), dim3(ROW_TPB), 0, ctx->stream, reinterpret_cast<const uint32_t *>(d_rows),
+                           stride, W.kept.p, total, reinterpret_cast<uint32_t *>(d_out));
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(W.ev[4], ctx->stream));
+    ctx->sync();
+    if (summary) {
+        summary->n = n;
+        summary->components = C;
+        summary->kept_components = W.h_count[1];
+        summary->kept = total;
+        summary->largest = W.h_count[0];
+        summary->reserved = 0;
+    }
+    float ms[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int k = 0; k < 4; ++k) HIP_TRY(hipEventElapsedTime(&ms[k], W.ev[k], W.ev[k + 1]));
+    ctx->stats.clear();
+    ctx->stats.add("components_grid_s", 1e-3 * ms[0]);
+    ctx->stats.add("components_link_s", 1e-3 * ms[1]);
+    ctx->stats.add("components_label_s", 1e-3 * ms[2]);
+    ctx->stats.add("components_compact_s", 1e-3 * ms[3]);
+    ctx->stats.add("components_count", C);
+    ctx->stats.add("components_kept", total);
+    return total;
+}
+
+ComponentWork &work_of(plade_ctx *ctx) {
+    if (!ctx->component_work) ctx->component_work = component_work_create();
+    return *ctx->component_work;
+}
+
+}  // namespace
+}  // namespace plade
+
+using namespace plade;
+
+// ---- C ABI (include/plade_hip.h) ---------------------------------------------------------------------------------------------
+extern "C" void plade_component_default_params(plade_component_params *p) {
+    if (!p) return;
+    memset(p, 0, sizeof(*p));
+    p->radius = 0.0;
+    p->min_size = 1;
+    p->max_size = 0;
+    p->keep_largest = 0;
+}
+
+extern "C" int plade_label_components(plade_ctx *ctx, const float *rows, uint32_t n, uint32_t stride, const plade_component_params *params,
+                                      int32_t *label_out, uint32_t *size_out, uint8_t *keep_out, uint32_t *kept_index_out,
+                                      float *rows_out, plade_component_summary *summary) {
+    return guarded(ctx, [&]() -> int {
+        PLADE_REQUIRE(rows, PLADE_EINVAL, "plade_label_components: NULL cloud");
+        plade_component_params p;
+        if (params) p = *params; else plade_component_default_params(&p);
+        check_params(n, stride, p);
+        ComponentWork &W = work_of(ctx);
+        float mn[3], mx[3];
+        upload_rows(ctx, W.in, rows, n, stride, mn, mx);
+        const uint32_t total = components_dev(ctx, W, W.in.p, n, stride, mn, mx, p,
+                                              [&](uint32_t kept) { return W.out.ensure((size_t)kept * stride + 4); }, summary);
+        if (label_out) HIP_TRY(hipMemcpyAsync(label_out, W.label.p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+        if (size_out) HIP_TRY(hipMemcpyAsync(size_out, W.size.p, (size_t)W.components * 4, hipMemcpyDeviceToHost, ctx->stream));
+        if (keep_out) HIP_TRY(hipMemcpyAsync(keep_out, W.keep.p, n, hipMemcpyDeviceToHost, ctx->stream));
+        if (kept_index_out && total) HIP_TRY(hipMemcpyAsync(kept_index_out, W.kept.p, (size_t)total * 4, hipMemcpyDeviceToHost, ctx->stream));
+        if (rows_out && total) HIP_TRY(hipMemcpyAsync(rows_out, W.out.p, (size_t)total * stride * 4, hipMemcpyDeviceToHost, ctx->stream));
+        ctx->sync();
+        return PLADE_OK;
+    });
+}
+
+extern "C" int plade_cloud_filter_components_dev(plade_ctx *ctx, plade_cloud *cloud, const plade_component_params *params, plade_cloud **out,
+                                                 int32_t *label_out, uint32_t *kept_index_out, plade_component_summary *summary) {
+    return guarded(ctx, [&]() -> int {
+        PLADE_REQUIRE(cloud && out, PLADE_EINVAL, "plade_cloud_filter_components_dev: NULL cloud");
+        *out = nullptr;
+        plade_component_params p;
+        if (params) p = *params; else plade_component_default_params(&p);
+        const CloudDev &in = cloud->dev;
+        check_params(in.n, 6, p);
+        ComponentWork &W = work_of(ctx);
+        plade_cloud *c = new plade_cloud;
+        try {
+            const uint32_t total = components_dev(ctx, W, in.aos.p, in.n, 6, in.bbmin, in.bbmax, p,
+                                                  [&](uint32_t kept) { cloud_shape(c->dev, kept); return c->dev.aos.p; }, summary);
+            if (label_out) HIP_TRY(hipMemcpyAsync(label_out, W.label.p, (size_t)in.n * 4, hipMemcpyDeviceToHost, ctx->stream));
+            if (kept_index_out && total) HIP_TRY(hipMemcpyAsync(kept_index_out, W.kept.p, (size_t)total * 4, hipMemcpyDeviceToHost, ctx->stream));
+            ctx->sync();
+            PLADE_REQUIRE(total >= 1, PLADE_EFAIL, "plade_cloud_filter_components_dev: the selection keeps no point (a resident cloud cannot be empty)");
+            cloud_finish_device(ctx, c->dev);   // SoA planes + bounding box of the resident cloud, as plade_cloud_upload
+        } catch (...) { delete c; throw; }
+        *out = c;
+        return PLADE_OK;
+    });
+}

@@ -83,6 +83,21 @@ struct OutlierRemoval {
 bool remove_outliers(pcl::PointCloud<pcl::PointNormal>::Ptr cloud, pcl::PointCloud<pcl::PointNormal> &filtered, int k = 16,
                      double alpha = 1.0, OutlierRemoval *info = nullptr);
 
+/** Connected components (no counterpart in the reference): the fields of plade_component_summary (include/plade_hip.h). */
+struct ComponentFilter {
+    uint64_t n = 0, components = 0, kept_components = 0, kept = 0;   // points in, components found, components and points kept
+    uint32_t largest = 0;                                            // the size of the largest component
+};
+/** Keeps the connected components of the graph "closer than radius" (absolute, in the cloud's units; fp32 squared distance, strict
+ *  <) that hold at least min_size and, when max_size > 0, at most max_size points -- with keep_largest = m > 0 only the m largest of
+ *  them -- on the GPU (plade_label_components): dense blobs that do not belong to the structure, which no neighbour-count filter
+ *  removes.  `filtered` receives the kept points in their original order, coordinates and normals copied bit for bit (it may be
+ *  *cloud).  false: invalid input or no GPU; a message is printed and `filtered` is unchanged.  The CLI and the file overload of
+ *  registration() filter both clouds of a pair after PLADE_REMOVE_OUTLIERS and before PLADE_ESTIMATE_NORMALS when
+ *  PLADE_KEEP_COMPONENTS=<radius>[,<min_size>[,<keep_largest>]] is set, and print one line per cloud. */
+bool keep_components(pcl::PointCloud<pcl::PointNormal>::Ptr cloud, pcl::PointCloud<pcl::PointNormal> &filtered, double radius,
+                     int min_size = 1, int max_size = 0, int keep_largest = 0, ComponentFilter *info = nullptr);
+
 /** Merging registered clouds (no counterpart in the reference): the fields of plade_merge_summary (include/plade_hip.h). */
 struct CloudMerge {
     uint64_t n_in = 0, n_out = 0, n_shared = 0;   // points in, rows out, rows to which two or more clouds contributed

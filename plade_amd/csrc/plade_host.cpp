@@ -259,6 +259,75 @@ bool remove_outliers_in_place(std::vector<float> &buf) {
     return true;
 }
 
+// PLADE_KEEP_COMPONENTS=<radius>[,<min_size>[,<keep_largest>]] (opt-in, 0 / unset = off; the radius absolute, in the clouds' units):
+// both clouds of a pair keep only the connected components of the graph "closer than radius" with at least min_size points
+// (1 when not given), with keep_largest = m > 0 only the m largest of them (plade_label_components), after PLADE_REMOVE_OUTLIERS and
+// before PLADE_ESTIMATE_NORMALS; one console line per cloud.  A value that does not parse (radius negative or not finite, min_size
+// not an integer >= 1, keep_largest not an integer >= 0, anything behind them) prints one warning and filters nothing; unset,
+// nothing changes.
+struct ComponentSwitch { double radius = 0.0; int min_size = 1, keep_largest = 0; };
+const ComponentSwitch &keep_components_switch() {
+    static const ComponentSwitch sw = [] {
+        ComponentSwitch v, off;
+        const char *w = getenv("PLADE_KEEP_COMPONENTS");
+        if (!w) return off;
+        char *end = nullptr;
+        v.radius = strtod(w, &end);
+        bool ok = end != w && std::isfinite(v.radius) && v.radius >= 0.0 && std::isfinite((float)v.radius * (float)v.radius);
+        if (ok && *end == ',') {
+            const char *a = end + 1;
+            const long m = strtol(a, &end, 10);
+            ok = end != a && m >= 1 && m <= INT32_MAX;
+            v.min_size = (int)m;
+            if (ok && *end == ',') {
+                a = end + 1;
+                const long g = strtol(a, &end, 10);
+                ok = end != a && g >= 0 && g <= INT32_MAX;
+                v.keep_largest = (int)g;
+            }
+        }
+        if (!ok || *end != '\0') {
+            std::cerr << "warning: PLADE_KEEP_COMPONENTS=" << w
+                      << " is not <radius>[,<min_size>[,<keep_largest>]] with radius >= 0, min_size >= 1 and keep_largest >= 0; no component filter"
+                      << std::endl;
+            return off;
+        }
+        return v;
+    }();
+    return sw;
+}
+// the rows of an x y z nx ny nz array whose component is kept, in place (the normal columns, NaN included, keep their bits)
+bool components_packed(plade_ctx *ctx, std::vector<float> &buf, double radius, int min_size, int max_size, int keep_largest,
+                       plade_component_summary &s) {
+    plade_component_params prm;
+    plade_component_default_params(&prm);
+    prm.radius = radius; prm.min_size = min_size; prm.max_size = max_size; prm.keep_largest = keep_largest;
+    const size_t n = buf.size() / 6;
+    trace("components: labelling");
+    // (in place: the upload of the rows precedes the read-back of the kept ones on the context's stream)
+    const int rc = plade_label_components(ctx, buf.data(), (uint32_t)n, 6, &prm, nullptr, nullptr, nullptr, nullptr, buf.data(), &s);
+    trace("components: done");
+    if (rc != PLADE_OK) {
+        con_err() << "component filter failed: " << plade_last_error(ctx) << std::endl;
+        return false;
+    }
+    buf.resize((size_t)s.kept * 6);
+    return true;
+}
+bool keep_components_in_place(std::vector<float> &buf) {
+    const ComponentSwitch &sw = keep_components_switch();
+    if (!(sw.radius > 0.0) || buf.empty()) return true;
+    plade_ctx *ctx = context();
+    if (!ctx) return false;
+    plade_component_summary s;
+    if (!components_packed(ctx, buf, sw.radius, sw.min_size, 0, sw.keep_largest, s)) return false;
+    char b[240];
+    snprintf(b, sizeof(b), "component filter: kept %llu of %llu points in %llu of %llu components (largest %u)", (unsigned long long)s.kept,
+             (unsigned long long)s.n, (unsigned long long)s.kept_components, (unsigned long long)s.components, s.largest);
+    con_out() << b << std::endl;
+    return true;
+}
+
 // PLADE_MERGE=<leaf> (opt-in, absolute, in the clouds' units; 0 = plain concatenation): every pair that registered is merged on
 // the GPU (plade_merge_clouds: the target as it is, the source under the pair's final transformation -- after ICP when that is
 // on) into <result file>.merged.ply (one pair) or <result file>.<pair index>.merged.ply (a list), in the target file's frame; one
@@ -466,7 +535,7 @@ bool load_packed(const std::string &file_name, std::vector<float> &buf) {
         return false;
     }
     for (auto &w : warnings) con_out() << w << std::endl;
-    if (!remove_outliers_in_place(buf)) return false;
+    if (!remove_outliers_in_place(buf) || !keep_components_in_place(buf)) return false;
     if (estimate && !buf.empty() && !estimate_in_place(file_name, buf)) return false;
     return !buf.empty();
 }
@@ -565,7 +634,7 @@ void registration_group(size_t count, Eigen::Matrix<float, 4, 4> *transformation
     auto report = [&](const Loaded &l, const std::string &file, std::vector<float> &buf) {   // load_packed's messages
         if (!l.ok && !l.err.empty()) con_err() << l.err << std::endl;
         if (l.ok || l.err.empty()) for (auto &w : l.warnings) con_out() << w << std::endl;
-        if (l.ok && !remove_outliers_in_place(buf)) return false;
+        if (l.ok && (!remove_outliers_in_place(buf) || !keep_components_in_place(buf))) return false;
         if (l.ok && buf.empty()) return false;
         if (l.ok && l.estimate) return estimate_in_place(file, buf);
         return l.ok;
@@ -673,6 +742,23 @@ bool remove_outliers(pcl::PointCloud<pcl::PointNormal>::Ptr cloud, pcl::PointClo
     return true;
 }
 
+// connected components: see plade.h
+bool keep_components(pcl::PointCloud<pcl::PointNormal>::Ptr cloud, pcl::PointCloud<pcl::PointNormal> &filtered, double radius, int min_size,
+                     int max_size, int keep_largest, ComponentFilter *info) {
+    plade_ctx *ctx = context();
+    if (!ctx) return false;
+    std::vector<float> buf = flatten(*cloud);
+    plade_component_summary s;
+    if (!components_packed(ctx, buf, radius, min_size, max_size, keep_largest, s)) return false;
+    filtered.resize((size_t)s.kept);
+    for (size_t i = 0; i < (size_t)s.kept; ++i) {
+        const float *p = &buf[6 * i];
+        filtered.at(i) = pcl::PointNormal(p[0], p[1], p[2], p[3], p[4], p[5]);
+    }
+    if (info) { info->n = s.n; info->components = s.components; info->kept_components = s.kept_components; info->kept = s.kept; info->largest = s.largest; }
+    return true;
+}
+
 // merging registered clouds: see plade.h
 bool merge_clouds(const std::vector<pcl::PointCloud<pcl::PointNormal>::Ptr> &clouds, const std::vector<Eigen::Matrix4f> &transformations,
                   float leaf, pcl::PointCloud<pcl::PointNormal> &merged, CloudMerge *info) {
@@ -716,7 +802,7 @@ bool load_ply_cloud(const std::string &file_name, pcl::PointCloud<pcl::PointNorm
         return false;
     }
     for (auto &w : warnings) con_out() << w << std::endl;
-    if (!remove_outliers_in_place(pos_nrm)) return false;
+    if (!remove_outliers_in_place(pos_nrm) || !keep_components_in_place(pos_nrm)) return false;
     if (estimate && !pos_nrm.empty() && !estimate_in_place(file_name, pos_nrm)) return false;
     const size_t n = pos_nrm.size() / 6;
     cloud.resize(n);

@@ -526,6 +526,55 @@ int plade_label_components(plade_ctx *ctx, const float *rows, uint32_t n, uint32
 int plade_cloud_filter_components_dev(plade_ctx *ctx, plade_cloud *cloud, const plade_component_params *params, plade_cloud **out,
                                       int32_t *label_out, uint32_t *kept_index_out, plade_component_summary *summary);
 
+/* ---- smoothing: moving-least-squares plane projection, the step between outlier removal and normals (no reference counterpart;
+ * PCL ships it as MovingLeastSquares, Open3D users expect it) -----------------------------------------------------------------------
+ * Semantics (plade_amd/csrc/smooth.h).  Input: n >= 1 points, rows of `stride` >= 3 floats, x y z first, all
+ * coordinates finite.  r2 = (float)radius * (float)radius; d(i, j) = the fp32 FLANN L2 of (p_i, p_j), ((dx*dx + dy*dy) + dz*dz).
+ *   neighbours   N_i = the j with d(i, j) < r2 (strict, as the radius filter); the point itself is one of them.  c_i = |N_i|.
+ *   moments      u = (double)d / (double)r2, w = (1 - u) * (1 - u); q_j = double(p_j) - double(p_i); W = sum w, S = sum w q,
+ *                M = sum (w q_a) q_b (xx xy xz yy yz zz), fp64, added in the order of the grid walk (no atomics).
+ *                mu = S / W, C = M / W - mu mu^T.
+ *   fit          n = the unit eigenvector of C's smallest eigenvalue l0 (the closed-form fp64 solve of plade_estimate_normals),
+ *                flipped when (viewpoint - p_i) . n < 0; curvature = max(l0, 0) / trace.
+ *   projection   delta_i = n . mu (fp64), the signed distance from p_i to the fitted plane along n;
+ *                p_i' = fp32(double(p_i) + delta_i * n) per coordinate.
+ *   unfitted     c_i < min_neighbours or C exactly zero: the position is copied bit for bit, normal and curvature are NaN,
+ *                delta = 0, fitted = 0.
+ *   output       by original index; every array after out_xyz may be NULL.  out_xyz: n x 3 floats; out_normal: n x 3 floats;
+ *                curvature_out: n floats; displacement_out: n doubles (delta); count_out: n uint32 (c_i); fitted_out: n bytes
+ *                0 / 1; moments_out: n x 10 doubles W, S (3), M (6) -- a test seam; summary: n, fitted, the rms and the max of
+ *                |delta| over the fitted points (0 when there is none; a fixed-order fp64 reduction) and the largest c_i.
+ * The same input gives the same bits on every run, on every context and from plade_cloud_smooth_dev.  c_i and fitted depend on the
+ * point set and the radius only; the fp64 sums follow the grid's order: under a permutation of the input their last bits may
+ * differ.
+ * Errors: PLADE_EINVAL for n = 0, stride < 3, a NULL cloud or out_xyz, a non-finite coordinate or viewpoint, radius <= 0 or not
+ * finite (or its fp32 square r2 not finite or below FLT_MIN: the point itself must satisfy 0 < r2), min_neighbours < 3; the context stays usable.  plade_stats_get then reports
+ * smooth_grid_s, smooth_fit_s, smooth_reduce_s (HIP events on the context's stream) and smooth_fitted. */
+typedef struct plade_smooth_params {
+    double radius;               /* must be set (> 0), absolute, in the cloud's units: there is no automatic value */
+    int32_t min_neighbours;      /* >= 3; a point with fewer neighbours (itself included) is left where it is */
+    float viewpoint[3];          /* the fit's normals point toward it */
+    int32_t reserved;            /* 0 */
+} plade_smooth_params;
+typedef struct plade_smooth_summary {
+    uint64_t n, fitted;
+    double rms, max;             /* of |delta| over the fitted points */
+    uint32_t max_count;          /* the largest c_i */
+    uint32_t reserved;           /* 0 */
+} plade_smooth_summary;
+/* The defaults: radius = 0 (unset), min_neighbours = 6, viewpoint = 0 0 0.  Needs no GPU. */
+void plade_smooth_default_params(plade_smooth_params *p);
+int plade_smooth_cloud(plade_ctx *ctx, const float *rows, uint32_t n, uint32_t stride, const plade_smooth_params *params,
+                       float *out_xyz, float *out_normal, float *curvature_out, double *displacement_out, uint32_t *count_out,
+                       uint8_t *fitted_out, double *moments_out, plade_smooth_summary *summary);
+/* The same on a resident cloud (plade_cloud_upload / plade_cloud_upload_xyz; rows x y z nx ny nz) into a NEW resident cloud of the
+ * same n points with the smoothed positions: the point data makes no host round trip, the positions and the summary are the bits
+ * of plade_smooth_cloud on the cloud's rows.  use_fit_normals = 1: columns 3..5 are the fit's normals (NaN where unfitted, which the
+ * registration skips like the NaN normals of plade_estimate_normals); 0: the input cloud's normal columns bit for bit.  Free both
+ * clouds with plade_cloud_free. */
+int plade_cloud_smooth_dev(plade_ctx *ctx, plade_cloud *cloud, const plade_smooth_params *params, int32_t use_fit_normals,
+                           plade_cloud **out, plade_smooth_summary *summary);
+
 /* ---- merging registered clouds: the step a scan-to-scan chain ends with (no reference counterpart) -----------------------------
  * Semantics (plade_amd/csrc/merge.h).  k clouds, 1 <= k <= 16; cloud c: n_c >= 1 rows x y z nx ny nz with
  * finite coordinates (the normals may be NaN); T: k row-major fp32 4 x 4 matrices, cloud c -> the output frame (NULL: identities,

@@ -32,6 +32,7 @@ ABI_SYMBOLS = [
     "plade_outlier_default_params", "plade_filter_outliers", "plade_cloud_filter_outliers_dev",
     "plade_merge_clouds", "plade_merge_clouds_dev", "plade_cloud_download",
     "plade_component_default_params", "plade_label_components", "plade_cloud_filter_components_dev",
+    "plade_smooth_default_params", "plade_smooth_cloud", "plade_cloud_smooth_dev",
 ]
 
 
@@ -98,6 +99,18 @@ class ComponentSummary(C.Structure):
     """plade_component_summary: n, components, kept_components, kept (points), largest (size)."""
     _fields_ = [("n", C.c_uint64), ("components", C.c_uint64), ("kept_components", C.c_uint64), ("kept", C.c_uint64),
                 ("largest", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class SmoothParams(C.Structure):
+    """plade_smooth_params: radius of the neighbourhood (absolute, no default), min_neighbours of a fitted point (the point itself
+    included), the viewpoint the fit's normals point toward."""
+    _fields_ = [("radius", C.c_double), ("min_neighbours", C.c_int32), ("viewpoint", C.c_float * 3), ("reserved", C.c_int32)]
+
+
+class SmoothSummary(C.Structure):
+    """plade_smooth_summary: n, fitted, rms and max of |displacement| over the fitted points, max_count (the largest neighbourhood)."""
+    _fields_ = [("n", C.c_uint64), ("fitted", C.c_uint64), ("rms", C.c_double), ("max", C.c_double), ("max_count", C.c_uint32),
+                ("reserved", C.c_uint32)]
 
 
 PLADE_OUTLIER_STATISTICAL, PLADE_OUTLIER_RADIUS = 0, 1
@@ -179,6 +192,9 @@ def load_library(path=LIB_PATH):
     sig("plade_component_default_params", argtypes=[C.POINTER(ComponentParams)], restype=None)
     sig("plade_label_components", argtypes=[p, p, u32, u32, C.POINTER(ComponentParams), p, p, p, p, p, C.POINTER(ComponentSummary)])
     sig("plade_cloud_filter_components_dev", argtypes=[p, p, C.POINTER(ComponentParams), C.POINTER(p), p, p, C.POINTER(ComponentSummary)])
+    sig("plade_smooth_default_params", argtypes=[C.POINTER(SmoothParams)], restype=None)
+    sig("plade_smooth_cloud", argtypes=[p, p, u32, u32, C.POINTER(SmoothParams), p, p, p, p, p, p, p, C.POINTER(SmoothSummary)])
+    sig("plade_cloud_smooth_dev", argtypes=[p, p, C.POINTER(SmoothParams), i32, C.POINTER(p), C.POINTER(SmoothSummary)])
     sig("plade_sort_segments", argtypes=[p, p, p, p, u32, C.c_int, p, p])
     sig("plade_set_candidate_shard", argtypes=[p, u32, u32, u32, EXCHANGE_FN, p])
     sig("plade_registration_minsupport", argtypes=[p, p, u32, p, u32, i32, i32, p])
@@ -304,6 +320,27 @@ def _component_info(summ, label, size, keep):
     if keep is not None:
         info["keep"] = keep.view(np.bool_)
     return info
+
+
+def smooth_default_params():
+    """plade_smooth_default_params (pure: needs no GPU) as a dict of the plade_smooth_params fields."""
+    prm = SmoothParams()
+    load_library().plade_smooth_default_params(C.byref(prm))
+    return {"radius": prm.radius, "min_neighbours": prm.min_neighbours, "viewpoint": tuple(prm.viewpoint)}
+
+
+def _smooth_params(radius, min_neighbours, viewpoint):
+    prm = SmoothParams()
+    load_library().plade_smooth_default_params(C.byref(prm))
+    prm.radius = float(radius)
+    if min_neighbours is not None:
+        prm.min_neighbours = int(min_neighbours)
+    prm.viewpoint[:] = [float(x) for x in _viewpoint(viewpoint)]
+    return prm
+
+
+def _smooth_info(summ):
+    return {k: getattr(summ, k) for k, _ in SmoothSummary._fields_ if k != "reserved"}
 
 
 def _icp_params(kw):
@@ -920,6 +957,49 @@ class Context:
                                                              C.byref(summ)))
         out = Cloud(self, None, handle=(int(summ.kept), h))
         return (out, kept[:summ.kept].copy(), _component_info(summ, label, None, None)) if info else out
+
+    # ---- smoothing ---------------------------------------------------------------------------------
+    def smooth_cloud(self, points, radius, min_neighbours=None, viewpoint=(0.0, 0.0, 0.0), normals=True, per_point=True, moments=False):
+        """plade_smooth_cloud: the moving-least-squares plane projection of an (N, >= 3) float32 array whose first three columns
+        are x y z -- every point with at least min_neighbours (default 6, itself included) points closer than radius goes to the
+        weighted plane fit of that neighbourhood (weights (1 - d^2 / r^2)^2).  Returns (rows, info): rows (N, 6) float32, the
+        smoothed x y z and -- with normals -- the fit's normals toward `viewpoint` (NaN where unfitted; NaN everywhere without
+        normals); info: a dict with n, fitted, rms and max (of |displacement| over the fitted points), max_count and -- with
+        per_point -- curvature (N float32, NaN where unfitted), displacement (N float64), count (N uint32: the neighbourhood, the
+        point itself included), fitted_mask (N bools), and with moments the (N, 10) float64 sums W, S, M of the fit."""
+        a, n, stride = _xyz_view(points)
+        prm = _smooth_params(radius, min_neighbours, viewpoint)
+        xyz = np.empty((n, 3), np.float32)
+        nrm = np.empty((n, 3), np.float32) if normals else None
+        curv = np.empty(n, np.float32) if per_point else None
+        disp = np.empty(n, np.float64) if per_point else None
+        count = np.empty(n, np.uint32) if per_point else None
+        fitted = np.zeros(n, np.uint8) if per_point else None
+        mom = np.empty((n, 10), np.float64) if moments else None
+        summ = SmoothSummary()
+        self._check(self.L.plade_smooth_cloud(self.h, _ptr(a), n, stride, C.byref(prm), _ptr(xyz), _ptr(nrm), _ptr(curv), _ptr(disp),
+                                              _ptr(count), _ptr(fitted), _ptr(mom), C.byref(summ)))
+        rows = np.full((n, 6), np.nan, np.float32)
+        rows[:, :3] = xyz
+        if normals:
+            rows[:, 3:] = nrm
+        info = _smooth_info(summ)
+        if per_point:
+            info.update(curvature=curv, displacement=disp, count=count, fitted_mask=fitted.view(np.bool_))
+        if moments:
+            info["moments"] = mom
+        return rows, info
+
+    def smooth_cloud_dev(self, cloud, radius, min_neighbours=None, viewpoint=(0.0, 0.0, 0.0), fit_normals=True, info=False):
+        """plade_cloud_smooth_dev: smooth_cloud on a resident cloud (upload, upload_xyz) into a new resident Cloud of the same
+        points; the point data makes no host round trip, the positions are the bits of smooth_cloud.  fit_normals: the normal
+        columns are the fit's (NaN where unfitted); without, the input cloud's bit for bit.  With info also the summary dict."""
+        prm = _smooth_params(radius, min_neighbours, viewpoint)
+        summ = SmoothSummary()
+        h = C.c_void_p()
+        self._check(self.L.plade_cloud_smooth_dev(self.h, cloud.h, C.byref(prm), 1 if fit_normals else 0, C.byref(h), C.byref(summ)))
+        out = Cloud(self, None, handle=(int(summ.n), h))
+        return (out, _smooth_info(summ)) if info else out
 
     # ---- merging registered clouds ---------------------------------------------------------------
     @staticmethod

@@ -9,6 +9,7 @@
 #include "outliers.h"
 #include "pipeline.h"
 #include "ransac.h"
+#include "smooth.h"
 
 using namespace plade;
 
@@ -143,6 +144,7 @@ extern "C" void plade_ctx_destroy(plade_ctx *ctx) {
     if (ctx->outlier_work) plade::outlier_work_destroy(ctx->outlier_work);
     if (ctx->merge_work) plade::merge_work_destroy(ctx->merge_work);
     if (ctx->component_work) plade::component_work_destroy(ctx->component_work);
+    if (ctx->smooth_work) plade::smooth_work_destroy(ctx->smooth_work);
     (void)hipStreamDestroy(ctx->stream);
     if (ctx->pf.stream) { (void)hipStreamSynchronize(ctx->pf.stream); (void)hipStreamDestroy(ctx->pf.stream); }
     delete ctx;

@@ -14,10 +14,12 @@
 //           ends when the k-th key is closer than the outside of the block or the block covers the grid.  Sparse regions and
 //           isolated outliers come out exact.
 //   PCA     in the same kernels, by the one function pca_store (identical fp64 arithmetic on both paths): two passes over the
-//           neighbour list (staged in LDS) in its order, closed-form eigenvalues of the 3 x 3 symmetric covariance, the eigenvector of the
-//           smallest from the cross products of the rows of C - l0 I, orientation toward the viewpoint.
+//           neighbour list (staged in LDS) in its order, then pca_eig (pca_eig.h, shared with k_smooth.hip): closed-form eigenvalues
+//           of the 3 x 3 symmetric covariance, the eigenvector of the smallest from the cross products of the rows of C - l0 I;
+//           orientation toward the viewpoint.
 #include "normals.h"
 #include "grid_walk.h"
+#include "pca_eig.h"
 #include "voxel.h"
 
 namespace plade {
@@ -59,11 +61,6 @@ __device__ __forceinline__ void scan_run(const NrmArgs &a, u64 (&best)[K], f3 q,
     }
 }
 
-// fp64 3-vector helpers of the eigen-solve
-struct d3 { double x, y, z; };
-__device__ __forceinline__ d3 dcross(d3 u, d3 v) { return {u.y * v.z - u.z * v.y, u.z * v.x - u.x * v.z, u.x * v.y - u.y * v.x}; }
-__device__ __forceinline__ double ddot(d3 u, d3 v) { return u.x * v.x + u.y * v.y + u.z * v.z; }
-
 // neighbour list -> outputs of point `orig` (p: its coordinates).  The list is staged in LDS: original index of neighbour b
 // = list[b * ld], b < a.m (plain loops: unrolled over K, the gathers of all neighbours would be hoisted into registers)
 __device__ void pca_store(const NrmArgs &a, const uint32_t *list, int ld, f3 p, uint32_t orig) {
@@ -89,46 +86,10 @@ __device__ void pca_store(const NrmArgs &a, const uint32_t *list, int ld, f3 p, 
             c11 += ey * ey; c12 += ey * ez; c22 += ez * ez;
         }
         c00 /= m; c01 /= m; c02 /= m; c11 /= m; c12 /= m; c22 /= m;
-        if (!(c00 == 0.0 && c01 == 0.0 && c02 == 0.0 && c11 == 0.0 && c12 == 0.0 && c22 == 0.0)) {
-            // eigenvalues: trigonometric solution of det(C - l I) = 0 on the shifted, scaled matrix
-            const double tr = c00 + c11 + c22, q = tr / 3.0;
-            const double b00 = c00 - q, b11 = c11 - q, b22 = c22 - q;
-            const double p2 = b00 * b00 + b11 * b11 + b22 * b22 + 2.0 * (c01 * c01 + c02 * c02 + c12 * c12);
-            double l0 = q;
-            if (p2 > 0.0) {
-                const double pp = sqrt(p2 / 6.0);
-                const double i00 = b00 / pp, i11 = b11 / pp, i22 = b22 / pp, i01 = c01 / pp, i02 = c02 / pp, i12 = c12 / pp;
-                double r = 0.5 * (i00 * (i11 * i22 - i12 * i12) - i01 * (i01 * i22 - i12 * i02) + i02 * (i01 * i12 - i11 * i02));
-                r = fmin(1.0, fmax(-1.0, r));
-                const double phi = acos(r) / 3.0;
-                l0 = q + 2.0 * pp * cos(phi + 2.0943951023931954923);   // the smallest root (2 pi / 3)
-            }
-            // eigenvector of l0: the largest cross product of two rows of C - l0 I; when all of them vanish (a line: the
-            // eigenspace of l0 is a plane) any vector orthogonal to the largest row
-            const d3 r0 = {c00 - l0, c01, c02}, r1 = {c01, c11 - l0, c12}, r2 = {c02, c12, c22 - l0};
-            const d3 x01 = dcross(r0, r1), x02 = dcross(r0, r2), x12 = dcross(r1, r2);
-            const double n01 = ddot(x01, x01), n02 = ddot(x02, x02), n12 = ddot(x12, x12);
-            d3 v = x01;
-            double vn = n01;
-            if (n02 > vn) { v = x02; vn = n02; }
-            if (n12 > vn) { v = x12; vn = n12; }
-            const double q0 = ddot(r0, r0), q1 = ddot(r1, r1), q2 = ddot(r2, r2);
-            double rmax = q0;
-            d3 rr = r0;
-            if (q1 > rmax) { rr = r1; rmax = q1; }
-            if (q2 > rmax) { rr = r2; rmax = q2; }
-            if (!(vn > 1e-20 * rmax * rmax)) {
-                if (rmax > 0.0) {
-                    const double ax = fabs(rr.x), ay = fabs(rr.y), az = fabs(rr.z);
-                    const d3 e = ax <= ay && ax <= az ? d3{1.0, 0.0, 0.0} : ay <= az ? d3{0.0, 1.0, 0.0} : d3{0.0, 0.0, 1.0};
-                    v = dcross(rr, e);
-                } else {
-                    v = {0.0, 0.0, 1.0};   // isotropic: every direction is an eigenvector
-                }
-                vn = ddot(v, v);
-            }
-            const double s = 1.0 / sqrt(vn);
-            nx = v.x * s; ny = v.y * s; nz = v.z * s;
+        d3 nv;
+        double l0, tr;
+        if (pca_eig(c00, c01, c02, c11, c12, c22, nv, l0, tr)) {   // closed-form eigen-solve (pca_eig.h)
+            nx = nv.x; ny = nv.y; nz = nv.z;
             if ((a.view[0] - px) * nx + (a.view[1] - py) * ny + (a.view[2] - pz) * nz < 0.0) { nx = -nx; ny = -ny; nz = -nz; }
             curvature = fmax(l0, 0.0) / tr;
         }

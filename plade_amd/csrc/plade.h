@@ -98,6 +98,22 @@ struct ComponentFilter {
 bool keep_components(pcl::PointCloud<pcl::PointNormal>::Ptr cloud, pcl::PointCloud<pcl::PointNormal> &filtered, double radius,
                      int min_size = 1, int max_size = 0, int keep_largest = 0, ComponentFilter *info = nullptr);
 
+/** Smoothing (no counterpart in the reference): the fields of plade_smooth_summary (include/plade_hip.h). */
+struct CloudSmoothing {
+    uint64_t n = 0, fitted = 0;   // points in, points that were fitted and projected
+    double rms = 0, max = 0;      // of the displacements of the fitted points
+    uint32_t max_count = 0;       // the largest neighbourhood
+};
+/** Moving-least-squares plane projection on the GPU (plade_smooth_cloud): every point with at least min_neighbours points (itself
+ *  included) closer than radius (absolute, in the cloud's units) is projected onto the plane fitted to that neighbourhood with the
+ *  weights (1 - d^2 / radius^2)^2; the others stay where they are.  `smoothed` receives the points in their original order (it may
+ *  be *cloud) with their own normals bit for bit or, with use_fit_normals, the fits' normals oriented toward the origin (NaN where
+ *  unfitted).  false: invalid input or no GPU; a message is printed and `smoothed` is unchanged.  The CLI and the file overload of
+ *  registration() smooth both clouds of a pair after PLADE_REMOVE_OUTLIERS and PLADE_KEEP_COMPONENTS and before
+ *  PLADE_ESTIMATE_NORMALS when PLADE_SMOOTH=<radius>[,<min_neighbours>] is set, and print one line per cloud. */
+bool smooth_cloud(pcl::PointCloud<pcl::PointNormal>::Ptr cloud, pcl::PointCloud<pcl::PointNormal> &smoothed, double radius,
+                  int min_neighbours = 6, bool use_fit_normals = false, CloudSmoothing *info = nullptr);
+
 /** Merging registered clouds (no counterpart in the reference): the fields of plade_merge_summary (include/plade_hip.h). */
 struct CloudMerge {
     uint64_t n_in = 0, n_out = 0, n_shared = 0;   // points in, rows out, rows to which two or more clouds contributed

@@ -5,6 +5,7 @@
 #include "plade_hip.h"
 #include "ply_reader.h"
 
+#include <cfloat>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -328,6 +329,70 @@ bool keep_components_in_place(std::vector<float> &buf) {
     return true;
 }
 
+// PLADE_SMOOTH=<radius>[,<min_neighbours>] (opt-in, 0 / unset = off; the radius absolute, in the clouds' units): both clouds of a
+// pair are smoothed by the moving-least-squares plane projection on the GPU (plade_smooth_cloud; min_neighbours 6 when not given)
+// after PLADE_REMOVE_OUTLIERS and PLADE_KEEP_COMPONENTS and before PLADE_ESTIMATE_NORMALS: the positions move, the normal columns
+// keep their bits (a file without normals gets the k-NN normals of the smoothed positions); one console line per cloud.  A value
+// that does not parse (radius negative, not finite or so small that its fp32 square is below FLT_MIN, min_neighbours not an
+// integer >= 3, anything behind them) prints one warning and smooths nothing; unset, nothing changes.
+struct SmoothSwitch { double radius = 0.0; int min_neighbours = 6; };
+const SmoothSwitch &smooth_switch() {
+    static const SmoothSwitch sw = [] {
+        SmoothSwitch v, off;
+        const char *w = getenv("PLADE_SMOOTH");
+        if (!w) return off;
+        char *end = nullptr;
+        v.radius = strtod(w, &end);
+        const float r2 = (float)v.radius * (float)v.radius;   // 0 = off; otherwise what plade_smooth_cloud accepts
+        bool ok = end != w && std::isfinite(v.radius) && v.radius >= 0.0 && std::isfinite(r2) && (v.radius == 0.0 || r2 >= FLT_MIN);
+        if (ok && *end == ',') {
+            const char *a = end + 1;
+            const long m = strtol(a, &end, 10);
+            ok = end != a && m >= 3 && m <= INT32_MAX;
+            v.min_neighbours = (int)m;
+        }
+        if (!ok || *end != '\0') {
+            std::cerr << "warning: PLADE_SMOOTH=" << w << " is not <radius>[,<min_neighbours>] with radius >= 0 (its square not below FLT_MIN) and min_neighbours >= 3; no smoothing"
+                      << std::endl;
+            return off;
+        }
+        return v;
+    }();
+    return sw;
+}
+// the x y z columns of an x y z nx ny nz array smoothed in place; nrm: the fit's normals (n x 3) when wanted
+bool smooth_packed(plade_ctx *ctx, std::vector<float> &buf, double radius, int min_neighbours, std::vector<float> *nrm, plade_smooth_summary &s) {
+    plade_smooth_params prm;
+    plade_smooth_default_params(&prm);
+    prm.radius = radius; prm.min_neighbours = min_neighbours;
+    const size_t n = buf.size() / 6;
+    std::vector<float> xyz(n * 3);
+    if (nrm) nrm->resize(n * 3);
+    trace("smooth: fitting");
+    const int rc = plade_smooth_cloud(ctx, buf.data(), (uint32_t)n, 6, &prm, xyz.data(), nrm ? nrm->data() : nullptr, nullptr, nullptr, nullptr,
+                                      nullptr, nullptr, &s);
+    trace("smooth: done");
+    if (rc != PLADE_OK) {
+        con_err() << "smoothing failed: " << plade_last_error(ctx) << std::endl;
+        return false;
+    }
+    for (size_t i = 0; i < n; ++i) memcpy(&buf[6 * i], &xyz[3 * i], 12);
+    return true;
+}
+bool smooth_in_place(std::vector<float> &buf) {
+    const SmoothSwitch &sw = smooth_switch();
+    if (!(sw.radius > 0.0) || buf.empty()) return true;
+    plade_ctx *ctx = context();
+    if (!ctx) return false;
+    plade_smooth_summary s;
+    if (!smooth_packed(ctx, buf, sw.radius, sw.min_neighbours, nullptr, s)) return false;
+    char b[240];
+    snprintf(b, sizeof(b), "smoothing: fitted %llu of %llu points (rms displacement %.6g, max %.6g)", (unsigned long long)s.fitted,
+             (unsigned long long)s.n, s.rms, s.max);
+    con_out() << b << std::endl;
+    return true;
+}
+
 // PLADE_MERGE=<leaf> (opt-in, absolute, in the clouds' units; 0 = plain concatenation): every pair that registered is merged on
 // the GPU (plade_merge_clouds: the target as it is, the source under the pair's final transformation -- after ICP when that is
 // on) into <result file>.merged.ply (one pair) or <result file>.<pair index>.merged.ply (a list), in the target file's frame; one
@@ -535,7 +600,7 @@ bool load_packed(const std::string &file_name, std::vector<float> &buf) {
         return false;
     }
     for (auto &w : warnings) con_out() << w << std::endl;
-    if (!remove_outliers_in_place(buf) || !keep_components_in_place(buf)) return false;
+    if (!remove_outliers_in_place(buf) || !keep_components_in_place(buf) || !smooth_in_place(buf)) return false;
     if (estimate && !buf.empty() && !estimate_in_place(file_name, buf)) return false;
     return !buf.empty();
 }
@@ -634,7 +699,7 @@ void registration_group(size_t count, Eigen::Matrix<float, 4, 4> *transformation
     auto report = [&](const Loaded &l, const std::string &file, std::vector<float> &buf) {   // load_packed's messages
         if (!l.ok && !l.err.empty()) con_err() << l.err << std::endl;
         if (l.ok || l.err.empty()) for (auto &w : l.warnings) con_out() << w << std::endl;
-        if (l.ok && (!remove_outliers_in_place(buf) || !keep_components_in_place(buf))) return false;
+        if (l.ok && (!remove_outliers_in_place(buf) || !keep_components_in_place(buf) || !smooth_in_place(buf))) return false;
         if (l.ok && buf.empty()) return false;
         if (l.ok && l.estimate) return estimate_in_place(file, buf);
         return l.ok;
@@ -759,6 +824,24 @@ bool keep_components(pcl::PointCloud<pcl::PointNormal>::Ptr cloud, pcl::PointClo
     return true;
 }
 
+// smoothing: see plade.h
+bool smooth_cloud(pcl::PointCloud<pcl::PointNormal>::Ptr cloud, pcl::PointCloud<pcl::PointNormal> &smoothed, double radius, int min_neighbours,
+                  bool use_fit_normals, CloudSmoothing *info) {
+    plade_ctx *ctx = context();
+    if (!ctx) return false;
+    std::vector<float> buf = flatten(*cloud), nrm;
+    plade_smooth_summary s;
+    if (!smooth_packed(ctx, buf, radius, min_neighbours, use_fit_normals ? &nrm : nullptr, s)) return false;
+    const size_t n = buf.size() / 6;
+    smoothed.resize(n);
+    for (size_t i = 0; i < n; ++i) {
+        const float *p = &buf[6 * i], *q = use_fit_normals ? &nrm[3 * i] : p + 3;
+        smoothed.at(i) = pcl::PointNormal(p[0], p[1], p[2], q[0], q[1], q[2]);
+    }
+    if (info) { info->n = s.n; info->fitted = s.fitted; info->rms = s.rms; info->max = s.max; info->max_count = s.max_count; }
+    return true;
+}
+
 // merging registered clouds: see plade.h
 bool merge_clouds(const std::vector<pcl::PointCloud<pcl::PointNormal>::Ptr> &clouds, const std::vector<Eigen::Matrix4f> &transformations,
                   float leaf, pcl::PointCloud<pcl::PointNormal> &merged, CloudMerge *info) {
@@ -802,7 +885,7 @@ bool load_ply_cloud(const std::string &file_name, pcl::PointCloud<pcl::PointNorm
         return false;
     }
     for (auto &w : warnings) con_out() << w << std::endl;
-    if (!remove_outliers_in_place(pos_nrm) || !keep_components_in_place(pos_nrm)) return false;
+    if (!remove_outliers_in_place(pos_nrm) || !keep_components_in_place(pos_nrm) || !smooth_in_place(pos_nrm)) return false;
     if (estimate && !pos_nrm.empty() && !estimate_in_place(file_name, pos_nrm)) return false;
     const size_t n = pos_nrm.size() / 6;
     cloud.resize(n);

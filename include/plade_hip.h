@@ -400,6 +400,71 @@ int plade_refine_icp_dev(plade_ctx *ctx, plade_cloud *tgt, plade_cloud *src, con
 int plade_icp_linearize(plade_ctx *ctx, const float *tgt_pos_nrm, uint32_t n_t, const float *src_xyz, uint32_t n_s, uint32_t stride,
                         const double *T16, const double *center, float dist, int32_t *corr_out, double *moments_out);
 
+/* ---- fine alignment: plane-to-plane (generalized) ICP (no reference counterpart) ------------------------------------------------
+ * Semantics (plade_amd/csrc/gicp.h).  Segal's Generalized ICP with the covariances built from the normals,
+ * C = I - (1 - epsilon) n n^T: every correspondence is weighted by M = (C_t + R C_s R^T)^-1.  Where the two normals agree the term
+ * is point-to-plane with weight ~ 1 / (2 epsilon); where they disagree (a wall against the clutter in front of it, corners, the
+ * other side of a thin wall) the weight falls to order 1; the two clouds play symmetric roles.  epsilon = 1 makes M = I / 2
+ * exactly: point-to-point ICP.  Target: n_t points x y z nx ny nz; source: n_s points x y z nx ny nz (BOTH normals are read);
+ * T_in, D, A, the automatic values, the stage distances, the tolerances with their fp32 floors and the limit of 16 stages are those
+ * of plade_refine_icp above, word for word.
+ *   sample       S = the source alone, voxel-fused under plade_merge_clouds' rules at leaf source_leaf [0.005 D]
+ *                (plade_merge_clouds_dev of one cloud under the identity): fp64 mean position, normalised fp64 sum of the finite
+ *                normals, ascending voxel order; every sample point carries a normal m or three NaNs.  Not the xyz-only sample
+ *                of plade_refine_icp: the two are not expected to have the same bits
+ *   centre       s-bar = the fp64 mean of S (summed once in a fixed order), c_k = T_k s-bar in fp64
+ *   match        p' and j as plade_refine_icp.  s has a correspondence when the distance < (float)d * (float)d, n_j is finite
+ *                with (n0 n0 + n1 n1) + n2 n2 > 0 in fp64, and m is finite with non-zero length in the same way.  No second choice
+ *                is looked for when the nearest point fails the normal test
+ *   linearise    fp64 per correspondence, p = T_k double(s): e = p - q_j, u = p - c_k, nh = n_j / |n_j|, ah = R m / |R m|,
+ *                k = 1 - epsilon, Sigma = 2 I - k nh nh^T - k ah ah^T, M = adj(Sigma) / det Sigma in closed form,
+ *                J = [-[u]x | I]; the 21 values of J^T M J (row-major upper triangle), the 6 of J^T M e, sum e^T M e, sum e . e and
+ *                the count: 30 moments, every term in the written operation order of gicp.h, summed in the fixed order of
+ *                plade_refine_icp (bit-identical from run to run).  The eigenvalues of Sigma lie in [2 epsilon, 2]
+ *   solve, update, tolerances, schedule   those of plade_refine_icp on the 21 + 6 moments
+ *   failure      PLADE_EFAIL and T_out = T_in with failure = PLADE_ICP_TOO_FEW or PLADE_ICP_DEGENERATE.  The isotropic part of M
+ *                makes a single plane or a crease NON-degenerate here (an in-plane pull at relative weight epsilon is inherent
+ *                to GICP); degenerate remains for the truly singular cases, e.g. a sample on one straight line through c_k
+ *   output       T_out: fp32 of the fp64 iterate; rmse = sqrt(sum e . e / count) (point-to-point), cost = sum e^T M e / count,
+ *                fitness = count / |S|, all of the last linearisation
+ * Errors: PLADE_EINVAL with a message for every case of plade_refine_icp and for epsilon < 0, epsilon > 1 or not finite (and what
+ * plade_merge_clouds refuses for the sample: PLADE_ELIMIT for more than 2^18 leaves along an axis); the context stays usable.
+ * plade_stats_get then reports gicp_sample_s, gicp_grid_s, gicp_loop_s, gicp_iterations and gicp_stages. */
+typedef struct plade_gicp_params {
+    double source_leaf;          /* 0: 0.005 D */
+    double max_dist;             /* 0: 0.025 D */
+    double min_dist;             /* 0: 0.0025 D (capped at max_dist when max_dist is given and min_dist is not) */
+    double eps_rotation;         /* radians, 0: 1e-6 */
+    double eps_translation;      /* 0: 1e-6 D */
+    int32_t max_iterations;      /* 0: 60 */
+    int32_t min_correspondences; /* 0: 100 */
+    double epsilon;              /* variance along the normal relative to 1 in the tangent plane; 0: 1e-3; valid: 0 < epsilon <= 1 */
+} plade_gicp_params;
+typedef struct plade_gicp_result {
+    int32_t iterations;          /* updates applied */
+    int32_t stages;              /* stage distances used (1 + the index of the last) */
+    int32_t converged;           /* 1: the stage at min_dist converged */
+    int32_t failure;             /* 0, PLADE_ICP_TOO_FEW or PLADE_ICP_DEGENERATE */
+    uint32_t correspondences;    /* of the last linearisation */
+    uint32_t samples;            /* |S| */
+    double rmse, fitness;        /* of the last linearisation; rmse is point-to-point */
+    double final_dist;           /* the stage distance d of the last linearisation */
+    double cost;                 /* sum e^T M e / count of the last linearisation */
+} plade_gicp_result;
+/* The defaults of plade_icp_default_params and epsilon = 1e-3.  Pure: needs no GPU. */
+void plade_gicp_default_params(plade_gicp_params *p);
+/* params NULL: the defaults.  T_out16 may be T_in16. */
+int plade_refine_gicp(plade_ctx *ctx, const float *tgt_pos_nrm, uint32_t n_t, const float *src_pos_nrm, uint32_t n_s,
+                      const float *T_in16, const plade_gicp_params *params, float *T_out16, plade_gicp_result *result);
+/* The same on resident clouds (plade_cloud_upload, plade_cloud_upload_xyz): bit-identical results. */
+int plade_refine_gicp_dev(plade_ctx *ctx, plade_cloud *tgt, plade_cloud *src, const float *T_in16, const plade_gicp_params *params,
+                          float *T_out16, plade_gicp_result *result);
+/* Test seam: one match + linearise pass at stage distance `dist` on the given source rows (x y z nx ny nz, no sample), about the
+ * fp64 point center[3]; epsilon as in the parameters (0: 1e-3).  corr_out[i] = j or -1 (n_s int32, may be NULL); moments_out =
+ * J^T M J (21 values, row-major upper triangle), J^T M e (6), sum e^T M e, sum e . e, count. */
+int plade_gicp_linearize(plade_ctx *ctx, const float *tgt_pos_nrm, uint32_t n_t, const float *src_pos_nrm, uint32_t n_s,
+                         const double *T16, const double *center, float dist, double epsilon, int32_t *corr_out, double *moments_out);
+
 /* ---- cloud-to-cloud distances and registration quality (no reference counterpart) ------------------------------------------
  * Semantics (plade_amd/csrc/distances.h).  Target: n_t points x y z nx ny nz (the normals may be NaN, as
  * plade_ply_read_points gives for xyz-only files); source: n_s points x y z, `stride` floats apart; T16: the row-major 4 x 4

@@ -33,6 +33,7 @@ ABI_SYMBOLS = [
     "plade_merge_clouds", "plade_merge_clouds_dev", "plade_cloud_download",
     "plade_component_default_params", "plade_label_components", "plade_cloud_filter_components_dev",
     "plade_smooth_default_params", "plade_smooth_cloud", "plade_cloud_smooth_dev",
+    "plade_gicp_default_params", "plade_refine_gicp", "plade_refine_gicp_dev", "plade_gicp_linearize",
 ]
 
 
@@ -61,6 +62,17 @@ class IcpResult(C.Structure):
     _fields_ = [("iterations", C.c_int32), ("stages", C.c_int32), ("converged", C.c_int32), ("failure", C.c_int32),
                 ("correspondences", C.c_uint32), ("samples", C.c_uint32), ("rmse", C.c_double), ("fitness", C.c_double),
                 ("final_dist", C.c_double)]
+
+
+class GicpParams(C.Structure):
+    """plade_gicp_params: the seven fields of plade_icp_params with the same meaning and automatic values, and epsilon = the variance
+    along the normal relative to 1 in the tangent plane (0: 1e-3; valid 0 < epsilon <= 1; 1 = point-to-point ICP)."""
+    _fields_ = IcpParams._fields_ + [("epsilon", C.c_double)]
+
+
+class GicpResult(C.Structure):
+    """plade_gicp_result: the fields of plade_icp_result (rmse is point-to-point) and cost = sum e^T M e / count."""
+    _fields_ = IcpResult._fields_ + [("cost", C.c_double)]
 
 
 class DistanceSummary(C.Structure):
@@ -181,6 +193,10 @@ def load_library(path=LIB_PATH):
     sig("plade_refine_icp", argtypes=[p, p, u32, p, u32, p, C.POINTER(IcpParams), p, C.POINTER(IcpResult)])
     sig("plade_refine_icp_dev", argtypes=[p, p, p, p, C.POINTER(IcpParams), p, C.POINTER(IcpResult)])
     sig("plade_icp_linearize", argtypes=[p, p, u32, p, u32, u32, p, p, f, p, p])
+    sig("plade_gicp_default_params", argtypes=[C.POINTER(GicpParams)], restype=None)
+    sig("plade_refine_gicp", argtypes=[p, p, u32, p, u32, p, C.POINTER(GicpParams), p, C.POINTER(GicpResult)])
+    sig("plade_refine_gicp_dev", argtypes=[p, p, p, p, C.POINTER(GicpParams), p, C.POINTER(GicpResult)])
+    sig("plade_gicp_linearize", argtypes=[p, p, u32, p, u32, p, p, f, C.c_double, p, p])
     sig("plade_cloud_distances", argtypes=[p, p, u32, p, u32, u32, p, f, p, p, p, C.POINTER(DistanceSummary)])
     sig("plade_cloud_distances_dev", argtypes=[p, p, p, p, f, p, p, p, C.POINTER(DistanceSummary)])
     sig("plade_outlier_default_params", argtypes=[C.POINTER(OutlierParams)], restype=None)
@@ -341,6 +357,30 @@ def _smooth_params(radius, min_neighbours, viewpoint):
 
 def _smooth_info(summ):
     return {k: getattr(summ, k) for k, _ in SmoothSummary._fields_ if k != "reserved"}
+
+
+def gicp_default_params():
+    """plade_gicp_default_params (pure: needs no GPU) as a dict of the plade_gicp_params fields."""
+    prm = GicpParams()
+    load_library().plade_gicp_default_params(C.byref(prm))
+    return {k: getattr(prm, k) for k, _ in GicpParams._fields_}
+
+
+def _gicp_params(kw):
+    prm = GicpParams()
+    load_library().plade_gicp_default_params(C.byref(prm))
+    for k, v in kw.items():
+        if k not in dict(GicpParams._fields_):
+            raise TypeError(f"unknown GICP parameter {k!r}")
+        setattr(prm, k, v)
+    return prm
+
+
+def _gicp_info(res):
+    info = {k: getattr(res, k) for k, _ in GicpResult._fields_}
+    info["converged"] = bool(info["converged"])
+    info["reason"] = ICP_FAILURES.get(info["failure"], "unknown")
+    return info
 
 
 def _icp_params(kw):
@@ -851,6 +891,49 @@ class Context:
         mom = np.zeros(29, np.float64)
         self._check(self.L.plade_icp_linearize(self.h, _ptr(tgt), len(tgt), _ptr(a), n, stride, _ptr(T64), _ptr(c64), float(dist),
                                                _ptr(corr), _ptr(mom)))
+        return corr, mom
+
+    def _refine_gicp(self, call, T, gicp_params):
+        T_in = _f32(T).reshape(4, 4).copy()
+        prm = _gicp_params(gicp_params)
+        T_out = np.zeros((4, 4), np.float32)
+        res = GicpResult()
+        rc = call(T_in, prm, T_out, res)
+        info = _gicp_info(res)
+        if rc != 0:
+            err = PladeError(rc, self.L.plade_last_error(self.h).decode(errors="replace"))
+            err.info, err.T = info, T_out
+            raise err
+        return T_out, info
+
+    def refine_gicp(self, tgt, src, T, **gicp_params):
+        """plade_refine_gicp: plane-to-plane (generalized) ICP of the (N, 6) source onto the (M, 6) target from the 4 x 4 source ->
+        target T; both clouds' normals are read.  Parameters: those of refine_icp and epsilon (1: point-to-point ICP).  Returns
+        (T_out, info), info = the plade_gicp_result fields as a dict plus `reason` (None, "too few correspondences", "degenerate").
+        A failed refinement raises PladeError (code PLADE_EFAIL, with .info and .T = T_in)."""
+        tgt, src = _f32(tgt), _f32(src)
+        self._check_cloud(tgt, "refine_gicp"); self._check_cloud(src, "refine_gicp")
+        return self._refine_gicp(lambda T_in, prm, T_out, res: self.L.plade_refine_gicp(
+            self.h, _ptr(tgt), len(tgt), _ptr(src), len(src), _ptr(T_in), C.byref(prm), _ptr(T_out), C.byref(res)), T, gicp_params)
+
+    def refine_gicp_dev(self, tgt_cloud, src_cloud, T, **gicp_params):
+        """plade_refine_gicp_dev: refine_gicp on resident clouds (upload, upload_xyz); bit-identical to refine_gicp."""
+        return self._refine_gicp(lambda T_in, prm, T_out, res: self.L.plade_refine_gicp_dev(
+            self.h, tgt_cloud.h, src_cloud.h, _ptr(T_in), C.byref(prm), _ptr(T_out), C.byref(res)), T, gicp_params)
+
+    def gicp_linearize(self, tgt, src, T, dist, epsilon=0.0, center=None):
+        """plade_gicp_linearize (test seam): one match + linearise pass of the plane-to-plane ICP at stage distance `dist` with the
+        fp64 4 x 4 T on every row of the (N, 6) source (no sample), J about the fp64 point `center` (None: the origin); epsilon 0 =
+        1e-3.  Returns (corr, moments): corr (N,) int32 = the target index or -1, moments (30,) float64 = J^T M J (upper triangle,
+        row-major), J^T M e, sum e^T M e, sum e . e, count."""
+        tgt, src = _f32(tgt), _f32(src)
+        self._check_cloud(tgt, "gicp_linearize"); self._check_cloud(src, "gicp_linearize")
+        T64 = np.ascontiguousarray(T, dtype=np.float64).reshape(4, 4)
+        c64 = np.ascontiguousarray((0.0, 0.0, 0.0) if center is None else center, dtype=np.float64).reshape(3)
+        corr = np.empty(len(src), np.int32)
+        mom = np.zeros(30, np.float64)
+        self._check(self.L.plade_gicp_linearize(self.h, _ptr(tgt), len(tgt), _ptr(src), len(src), _ptr(T64), _ptr(c64), float(dist),
+                                                float(epsilon), _ptr(corr), _ptr(mom)))
         return corr, mom
 
     # ---- cloud-to-cloud distances ------------------------------------------------------------

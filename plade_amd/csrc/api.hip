@@ -10,6 +10,7 @@
 #include "pipeline.h"
 #include "ransac.h"
 #include "smooth.h"
+#include "gicp.h"
 
 using namespace plade;
 
@@ -145,6 +146,7 @@ extern "C" void plade_ctx_destroy(plade_ctx *ctx) {
     if (ctx->merge_work) plade::merge_work_destroy(ctx->merge_work);
     if (ctx->component_work) plade::component_work_destroy(ctx->component_work);
     if (ctx->smooth_work) plade::smooth_work_destroy(ctx->smooth_work);
+    if (ctx->gicp_work) plade::gicp_work_destroy(ctx->gicp_work);
     (void)hipStreamDestroy(ctx->stream);
     if (ctx->pf.stream) { (void)hipStreamSynchronize(ctx->pf.stream); (void)hipStreamDestroy(ctx->pf.stream); }
     delete ctx;

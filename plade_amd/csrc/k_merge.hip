@@ -389,6 +389,26 @@ void fill_unfused(uint32_t k, const uint32_t n[], uint32_t *out_count, uint32_t 
 }
 
 }  // namespace
+
+uint32_t merge_fuse_one(plade_ctx *ctx, const float *d_rows, uint32_t n, float leaf, const float **d_out, const char *who) {
+    const void *const clouds[1] = {d_rows};
+    const uint32_t ns[1] = {n};
+    const float *const rows[1] = {d_rows};
+    try {
+        // (a leaf that rounds to 0 in fp32 would select the concatenation: there would be no fused rows to hand out)
+        PLADE_REQUIRE(leaf > 0.f, PLADE_EINVAL, "merge_clouds: the leaf is 0 in fp32");
+        const uint32_t total = check_args(1, clouds, ns, nullptr, leaf);
+        MergeWork &W = work_of(ctx);
+        const uint32_t m = merge_dev(ctx, W, 1, rows, ns, nullptr, leaf, total, W.cat.ensure(6 * (size_t)total + 8), nullptr);
+        *d_out = W.out_rows.p;
+        return m;
+    } catch (Err &e) {   // the merge's refusals, under the caller's name
+        const std::string own = "merge_clouds: ";
+        e.msg = std::string(who) + ": the sample: " + (e.msg.compare(0, own.size(), own) == 0 ? e.msg.substr(own.size()) : e.msg);
+        throw;
+    }
+}
+
 }  // namespace plade
 
 using namespace plade;

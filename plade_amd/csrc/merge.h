@@ -32,4 +32,10 @@ struct MergeWork;
 MergeWork *merge_work_create();
 void merge_work_destroy(MergeWork *w);
 
+// The voxel fuse of ONE device cloud (n x 6 rows) under the identity at leaf > 0 -- plade_merge_clouds_dev of one cloud -- for the
+// stages that sample a cloud with its normals (gicp.h): returns the number of fused rows and leaves them, n_out x 6, behind *d_out in
+// the context's MergeWork, where they stay until the next merge on the context.  Waits for the stream.  What the merge refuses (a
+// non-finite coordinate, more than 2^18 leaves along an axis, a leaf that is 0 in fp32) is reported under the name `who`.
+uint32_t merge_fuse_one(plade_ctx *ctx, const float *d_rows, uint32_t n, float leaf, const float **d_out, const char *who);
+
 }  // namespace plade

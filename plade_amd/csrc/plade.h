@@ -58,6 +58,17 @@ bool refine_registration(Eigen::Matrix<float, 4, 4> &transformation,
                          pcl::PointCloud<pcl::PointNormal>::Ptr target_cloud,
                          pcl::PointCloud<pcl::PointNormal>::Ptr source_cloud);
 
+/** Fine alignment by plane-to-plane (generalized) ICP on the GPU (plade_refine_gicp, default parameters and the given epsilon --
+ *  0: 1e-3; 1: point-to-point ICP): like refine_registration, but BOTH clouds' normals are read and every correspondence is
+ *  weighted by how well the two normals agree, so the roles of the two clouds are symmetric and clutter in front of a wall counts
+ *  little.  Prints one line on success.  false: the refinement failed (too few correspondences, a degenerate geometry, an invalid
+ *  epsilon, no GPU) and `transformation` is unchanged; a warning is printed.  The CLI and the file / cloud overloads of
+ *  registration(T, target, source) call it for every registered pair when PLADE_REFINE_GICP=1[,<epsilon>] is set (it then takes
+ *  the place of PLADE_REFINE_ICP's refinement). */
+bool refine_registration_gicp(Eigen::Matrix<float, 4, 4> &transformation,
+                              pcl::PointCloud<pcl::PointNormal>::Ptr target_cloud,
+                              pcl::PointCloud<pcl::PointNormal>::Ptr source_cloud, double epsilon = 0.0);
+
 /** Registration quality (no counterpart in the reference): the fields of plade_distance_summary (include/plade_hip.h). */
 struct RegistrationQuality {
     uint64_t n = 0, count = 0, plane_count = 0;   // source points, those within max_dist, those of them with a finite target normal

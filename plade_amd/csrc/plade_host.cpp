@@ -160,6 +160,67 @@ bool refine_packed(plade_ctx *ctx, float *T16, const float *tg, size_t n_t, cons
     return true;
 }
 
+// PLADE_REFINE_GICP=1[,<epsilon>] (opt-in, 0 / unset = off): every pair that registered is refined by plane-to-plane ICP on the GPU
+// (plade_refine_gicp with the default parameters and the given epsilon, 0 < epsilon <= 1, default 1e-3; 1 = point-to-point) before
+// evaluation and merge; one console line per refined pair.  A refinement that fails keeps PLADE's transformation and prints a
+// warning.  A value that does not parse prints one warning and refines nothing.  With PLADE_REFINE_ICP also set, this is the
+// refinement that runs, and one warning says so.  Unset, nothing changes.  The variable is read when the first pair has registered
+// (like PLADE_EVALUATE): the warnings appear there, once per process.
+struct GicpSwitch { bool on = false; double epsilon = 0.0; };
+const GicpSwitch &refine_gicp_switch() {
+    static const GicpSwitch sw = [] {
+        GicpSwitch g;
+        const char *w = getenv("PLADE_REFINE_GICP");
+        if (!w) return g;
+        char *end = nullptr;
+        const long on = strtol(w, &end, 10);
+        double eps = 0.0;
+        bool ok = end != w && (on == 0 || on == 1);
+        if (ok && *end == ',') {
+            const char *v = end + 1;
+            eps = strtod(v, &end);
+            ok = end != v && std::isfinite(eps) && eps > 0.0 && eps <= 1.0;
+        }
+        if (!ok || *end != '\0') {
+            std::cerr << "warning: PLADE_REFINE_GICP=" << w << " is not 0, 1 or 1,<epsilon> with 0 < epsilon <= 1; no refinement" << std::endl;
+            return g;
+        }
+        g.on = on == 1;
+        g.epsilon = eps;
+        if (g.on && refine_icp_on())
+            std::cerr << "warning: PLADE_REFINE_ICP and PLADE_REFINE_GICP are both set; the plane-to-plane refinement runs" << std::endl;
+        return g;
+    }();
+    return sw;
+}
+// T16 (source -> target of the packed arrays) refined in place; false (T16 unchanged, a warning printed) when the refinement fails
+bool refine_gicp_packed(plade_ctx *ctx, float *T16, const float *tg, size_t n_t, const float *sr, size_t n_s, double epsilon) {
+    plade_gicp_params prm;
+    plade_gicp_default_params(&prm);
+    if (epsilon != 0.0) prm.epsilon = epsilon;
+    plade_gicp_result res;
+    float out[16];
+    trace("gicp: refining");
+    const int rc = plade_refine_gicp(ctx, tg, (uint32_t)n_t, sr, (uint32_t)n_s, T16, &prm, out, &res);
+    trace("gicp: done");
+    if (rc != PLADE_OK) {
+        con_err() << "warning: GICP refinement failed (" << plade_last_error(ctx) << "); PLADE's transformation is kept" << std::endl;
+        return false;
+    }
+    memcpy(T16, out, sizeof(out));
+    char b[240];
+    snprintf(b, sizeof(b), "GICP refinement: %d iterations, %s, rmse %.6g, cost %.6g, fitness %.4f", res.iterations,
+             res.converged ? "converged" : "not converged", res.rmse, res.cost, res.fitness);
+    con_out() << b << std::endl;
+    return true;
+}
+// the refinement the environment selects, if any
+void refine_selected(plade_ctx *ctx, float *T16, const float *tg, size_t n_t, const float *sr, size_t n_s) {
+    const GicpSwitch &g = refine_gicp_switch();
+    if (g.on) refine_gicp_packed(ctx, T16, tg, n_t, sr, n_s, g.epsilon);
+    else if (refine_icp_on()) refine_packed(ctx, T16, tg, n_t, sr, n_s);
+}
+
 // PLADE_EVALUATE=<d> (opt-in, absolute, in the clouds' units): every pair that registered -- after the ICP refinement when that
 // is on -- is evaluated at max_dist d (plade_cloud_distances, no per-point outputs) and one console line reports its fitness.
 // The pair is evaluated as it was registered (after the target / source switch).  A value that is not a positive finite number
@@ -583,7 +644,7 @@ bool register_packed(Eigen::Matrix<float, 4, 4> &transformation, const float *tg
         return false;
     }
     con_out() << "done. time: " << w.str() << std::endl;
-    if (refine_icp_on()) refine_packed(ctx, T16, tg, n_t, sr, n_s);
+    refine_selected(ctx, T16, tg, n_t, sr, n_s);
     if (evaluate_dist() > 0.f) evaluate_line(ctx, T16, tg, n_t, sr, n_s);
     to_matrix(T16, transformation);
     return true;
@@ -750,7 +811,7 @@ void registration_group(size_t count, Eigen::Matrix<float, 4, 4> *transformation
             continue;
         }
         con_out() << "done. time: " << w.str() << std::endl;
-        if (refine_icp_on()) refine_packed(ctx, T16 + 16 * q, it.tg, it.n_t, it.sr, it.n_s);
+        refine_selected(ctx, T16 + 16 * q, it.tg, it.n_t, it.sr, it.n_s);
         if (evaluate_dist() > 0.f) evaluate_line(ctx, T16 + 16 * q, it.tg, it.n_t, it.sr, it.n_s);
         to_matrix(T16 + 16 * q, transformations[it.pair]);
         if (it.switched) transformations[it.pair] = transformations[it.pair].inverse();
@@ -771,6 +832,19 @@ bool refine_registration(Eigen::Matrix<float, 4, 4> &transformation, pcl::PointC
     float T16[16];
     for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) T16[4 * r + c] = transformation(r, c);
     if (!refine_packed(ctx, T16, tg.data(), target_cloud->size(), sr.data(), source_cloud->size())) return false;
+    to_matrix(T16, transformation);
+    return true;
+}
+
+// fine alignment by plane-to-plane ICP: see plade.h
+bool refine_registration_gicp(Eigen::Matrix<float, 4, 4> &transformation, pcl::PointCloud<pcl::PointNormal>::Ptr target_cloud,
+                              pcl::PointCloud<pcl::PointNormal>::Ptr source_cloud, double epsilon) {
+    plade_ctx *ctx = context();
+    if (!ctx) return false;
+    std::vector<float> tg = flatten(*target_cloud), sr = flatten(*source_cloud);
+    float T16[16];
+    for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) T16[4 * r + c] = transformation(r, c);
+    if (!refine_gicp_packed(ctx, T16, tg.data(), target_cloud->size(), sr.data(), source_cloud->size(), epsilon)) return false;
     to_matrix(T16, transformation);
     return true;
 }

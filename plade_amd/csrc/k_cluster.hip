@@ -11,7 +11,10 @@
 //        edge(a,b) <=> |T_a-T_b|^2 < float(r*r)  &&  |euler_a-euler_b|^2 < gate ,
 //     clusters come out ordered by their smallest member and that member is the representative
 //     (util.cpp:355-357).  GPU: lock-free union-find (smaller index wins, so the root IS the seed)
-//     over a sorted-cell spatial hash of the translations.
+//     over a sorted-cell spatial hash of the translations.  The hash finds every pair within r at every extent
+//     the doubling loop of cluster_transforms admits (fp64 cell coordinates, see HashGrid); the seam
+//     plade_cluster_transforms rejects non-finite translations.  tests/test_gpu_cluster.py compares the stage
+//     with a brute-force restatement (tests/cluster_restate.py), exactly.
 // K7: plane-consistency count per cluster seed (util.cpp:359-401), one lane per cluster, plane
 //     tables in LDS.
 #include "stages.h"
@@ -78,8 +81,17 @@ void build_transforms(plade_ctx *ctx, const PairTableDev &src, const PairTableDe
 // ------------------------------------------------------------------------------------------------
 // cells of edge >= the cluster radius over the translations' bounding box; keys packed to the bits the
 // extents need (x lowest, so the three x-neighbours of a cell row are one contiguous key range)
+//
+// k_cell_spans probes +-1 cell, so every pair with fp32 d^2 < r2 must get cell coordinates at most 1 apart on every axis.
+// Such a pair is less than r (1 + 2^-22) apart on each axis (the roundings of the difference, its square and the sum), the
+// cell edge is at least float(r * 1.001f) >= 1.0009999 r, so it is less than 0.99901 cells apart: each of the two cell
+// coordinates (t - mn) / cell may be off by 0.0004 cells before the floors can come out 2 apart.  They are computed in fp64: t - mn
+// rounds once (2^-53 relative), 1.0 / cell and the product once each, at most 5e-10 cells at the 2^21 cells per axis that the
+// doubling loop of cluster_transforms admits.  (An fp32 coordinate is good to about 2^-23 of itself, 0.0004 cells at a few thousand
+// cells per axis already: at r = 0.06 and an extent of 60 000 it put 23 of 3000 pairs 0.99995 r apart two cells apart and split
+// their clusters, tests/test_cluster_host.py.  A doubled cell only widens the margin.)
 struct HashGrid {
-    float mnx, mny, mnz, inv;
+    double mnx, mny, mnz, inv;
     int bx, bxy;   // shifts of the y and z fields
 };
 
@@ -92,9 +104,9 @@ __device__ void k_t_keys(const VB &vb, const float4 *__restrict__ rt, uint32_t m
                          uint32_t *__restrict__ vals, uint32_t *__restrict__ parent, uint32_t *__restrict__ sizes) {
     const uint32_t i = vb.bx * blockDim.x + threadIdx.x;
     if (i >= m) return;
-    const int cx = (int)floorf((rt[4 * (size_t)i].w - g.mnx) * g.inv) + 1;
-    const int cy = (int)floorf((rt[4 * (size_t)i + 1].w - g.mny) * g.inv) + 1;
-    const int cz = (int)floorf((rt[4 * (size_t)i + 2].w - g.mnz) * g.inv) + 1;
+    const int cx = (int)floor(((double)rt[4 * (size_t)i].w - g.mnx) * g.inv) + 1;
+    const int cy = (int)floor(((double)rt[4 * (size_t)i + 1].w - g.mny) * g.inv) + 1;
+    const int cz = (int)floor(((double)rt[4 * (size_t)i + 2].w - g.mnz) * g.inv) + 1;
     keys[i] = cell_key(g, cx, cy, cz);
     vals[i] = i;
     parent[i] = i;
@@ -247,7 +259,7 @@ void cluster_transforms(plade_ctx *ctx, CandidateSet &cs, float dist_threshold, 
     }
     const int bx = bits_for(((double)mx[0] - mn[0]) / cell + 4), by = bits_for(((double)mx[1] - mn[1]) / cell + 4),
               bz = bits_for(((double)mx[2] - mn[2]) / cell + 4);
-    HashGrid g{mn[0], mn[1], mn[2], 1.f / cell, bx, bx + by};
+    HashGrid g{(double)mn[0], (double)mn[1], (double)mn[2], 1.0 / (double)cell, bx, bx + by};
     cs.ckeys.ensure(m); cs.ckeys2.ensure(m); cs.cvals.ensure(m); cs.cvals2.ensure(m);
     cs.parent.ensure(m); cs.sizes_all.ensure(m); cs.flags.ensure((size_t)m + 1);
     cs.st.ensure(m); cs.se.ensure(m); cs.spans.ensure((size_t)m * 9);
@@ -372,6 +384,8 @@ extern "C" int plade_cluster_transforms(plade_ctx *ctx, const float *t_xyz, cons
             rt[4 * (size_t)i + 2] = make_float4(0.f, 0.f, 1.f, t[2]);
             rt[4 * (size_t)i + 3] = make_float4(e[0], e[1], e[2], 0.f);
             for (int k = 0; k < 3; ++k) {
+                // std::min / std::max keep a NaN out of the box, where cluster_transforms looks for it
+                PLADE_REQUIRE(std::isfinite(t[k]), PLADE_EFAIL, "candidate transforms are not finite");
                 part[6 * (size_t)(i / 256) + k] = std::min(part[6 * (size_t)(i / 256) + k], t[k]);
                 part[6 * (size_t)(i / 256) + 3 + k] = std::max(part[6 * (size_t)(i / 256) + 3 + k], t[k]);
             }

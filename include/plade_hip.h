@@ -640,6 +640,62 @@ int plade_smooth_cloud(plade_ctx *ctx, const float *rows, uint32_t n, uint32_t s
 int plade_cloud_smooth_dev(plade_ctx *ctx, plade_cloud *cloud, const plade_smooth_params *params, int32_t use_fit_normals,
                            plade_cloud **out, plade_smooth_summary *summary);
 
+/* ---- change detection between two registered clouds: M3C2 distances (Lague, Brodu, Leroux 2013; no reference counterpart) -------
+ * Semantics (plade_amd/csrc/m3c2.h).  Per core point a cylinder of radius R and half-length L along the core
+ * point's normal; the mean position of each cloud inside it, measured along the normal; the difference of the two means and its
+ * 95 % level of detection.  Input: m >= 1 core points, rows x y z nx ny nz with finite coordinates (the normals need not be unit
+ * and may be non-finite); the reference cloud A and the compared cloud B: n >= 1 points each, rows of `stride` >= 3 floats, x y z
+ * first, finite; T16: row-major fp32 4 x 4, B -> the frame of A and the core points (NULL: the identity, which goes through the
+ * same arithmetic).
+ *   transform    B' = ((r0 x + r1 y) + r2 z) + t per row in fp32 (the rule of plade_cloud_distances).
+ *   axis         len2 = (nx nx + ny ny) + nz nz in fp64, n^ = double(n) / sqrt(len2).  A core point whose len2 is not finite or is 0
+ *                has no axis: both counts 0, the moments 0, distance, lod and sigma NaN, significant 0.  Not an error.
+ *   membership   in fp64 from the fp32 inputs, without contraction: q = double(p) - double(c); t = (q_x n^_x + q_y n^_y) + q_z n^_z;
+ *                e = q - t n^ per coordinate; rho2 = (e_x e_x + e_y e_y) + e_z e_z.  p is in the cylinder iff
+ *                fabs(t) <= L && rho2 < R * R: the radius test is strict, the ends are closed.
+ *   moments      per core point and cloud X in {A, B}: the exact count c_X, S1_X = sum t, S2_X = sum t t: fp64 sums in the fixed
+ *                order of the grid walk.  No atomics.
+ *   result       a core point is valid iff it has an axis and c_A, c_B >= min_points.  Then mean_X = S1_X / c_X,
+ *                var_X = max(S2_X - S1_X mean_X, 0) / (c_X - 1), sigma_X = sqrt(var_X), distance = mean_B - mean_A,
+ *                lod = 1.96 (sqrt(var_A / c_A + var_B / c_B) + reg_error), significant = |distance| > lod.  Not valid: distance,
+ *                lod and sigma are NaN and significant is 0; the counts and moments are still reported when there is an axis.
+ *   output       by core index; each array may be NULL.  distance_out, lod_out: m doubles; significant_out: m bytes 0 / 1;
+ *                count_out: m x 2 uint32 (c_A, c_B); sigma_out: m x 2 doubles; moments_out: m x 4 doubles S1_A S2_A S1_B S2_B -- a
+ *                test seam.  summary: m, valid, significant, the mean of distance, the rms of distance and the max of |distance|
+ *                over the valid core points (NaN when there is none; a fixed-order fp64 reduction over the core index) and the
+ *                largest count of either cloud.
+ * The same input gives the same bits on every run, on every context and from plade_cloud_m3c2_dev.  The counts depend on the point
+ * sets, the axes, R and L only; the last bits of the sums follow the grid (another bounding box, a permutation of the input).
+ * Errors: PLADE_EINVAL for a NULL cloud, params or summary, m = 0 or n = 0, stride < 3, a non-finite coordinate or T, radius or
+ * depth <= 0 or not finite (or radius * radius not finite), reg_error < 0 or not finite, min_points < 2; the context stays usable.
+ * plade_stats_get then reports m3c2_grid_s (transform + both grids), m3c2_walk_s, m3c2_reduce_s (HIP events on the context's
+ * stream) and m3c2_valid. */
+typedef struct plade_m3c2_params {
+    double radius;               /* R: must be set (> 0), absolute, in the clouds' units */
+    double depth;                /* L, the cylinder's half-length: must be set (> 0) */
+    double reg_error;            /* >= 0: the registration error added to the level of detection (e.g. plade_distance_summary.rmse) */
+    int32_t min_points;          /* >= 2: the smallest count per cloud of a valid core point */
+    int32_t reserved;            /* 0 */
+} plade_m3c2_params;
+typedef struct plade_m3c2_summary {
+    uint64_t m, valid, significant;
+    double mean, rms, max;       /* of distance, of distance, of |distance| over the valid core points */
+    uint32_t max_count;          /* the largest c_A or c_B */
+    uint32_t reserved;           /* 0 */
+} plade_m3c2_summary;
+/* The defaults: radius = depth = 0 (unset), reg_error = 0, min_points = 4.  Needs no GPU. */
+void plade_m3c2_default_params(plade_m3c2_params *p);
+int plade_cloud_m3c2(plade_ctx *ctx, const float *core_pos_nrm, uint32_t m, const float *ref_rows, uint32_t n_a, uint32_t stride_a,
+                     const float *cmp_rows, uint32_t n_b, uint32_t stride_b, const float *T16, const plade_m3c2_params *params,
+                     double *distance_out, double *lod_out, uint8_t *significant_out, uint32_t *count_out, double *sigma_out,
+                     double *moments_out, plade_m3c2_summary *summary);
+/* The same on resident clouds (rows x y z nx ny nz; `core` supplies the core points and their normals and may be the same handle
+ * as `ref`): the point data makes no host round trip, the outputs (host arrays) are the bits of plade_cloud_m3c2 on the clouds'
+ * rows. */
+int plade_cloud_m3c2_dev(plade_ctx *ctx, plade_cloud *core, plade_cloud *ref, plade_cloud *cmp, const float *T16,
+                         const plade_m3c2_params *params, double *distance_out, double *lod_out, uint8_t *significant_out,
+                         uint32_t *count_out, double *sigma_out, double *moments_out, plade_m3c2_summary *summary);
+
 /* ---- merging registered clouds: the step a scan-to-scan chain ends with (no reference counterpart) -----------------------------
  * Semantics (plade_amd/csrc/merge.h).  k clouds, 1 <= k <= 16; cloud c: n_c >= 1 rows x y z nx ny nz with
  * finite coordinates (the normals may be NaN); T: k row-major fp32 4 x 4 matrices, cloud c -> the output frame (NULL: identities,

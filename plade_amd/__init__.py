@@ -34,6 +34,7 @@ ABI_SYMBOLS = [
     "plade_component_default_params", "plade_label_components", "plade_cloud_filter_components_dev",
     "plade_smooth_default_params", "plade_smooth_cloud", "plade_cloud_smooth_dev",
     "plade_gicp_default_params", "plade_refine_gicp", "plade_refine_gicp_dev", "plade_gicp_linearize",
+    "plade_m3c2_default_params", "plade_cloud_m3c2", "plade_cloud_m3c2_dev",
 ]
 
 
@@ -125,6 +126,20 @@ class SmoothSummary(C.Structure):
                 ("reserved", C.c_uint32)]
 
 
+class M3c2Params(C.Structure):
+    """plade_m3c2_params: radius and depth (half-length) of the cylinder (absolute, no defaults), reg_error added to the level of
+    detection, min_points per cloud of a valid core point."""
+    _fields_ = [("radius", C.c_double), ("depth", C.c_double), ("reg_error", C.c_double), ("min_points", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class M3c2Summary(C.Structure):
+    """plade_m3c2_summary: m, valid, significant, the mean and rms of distance and the max of |distance| over the valid core points
+    (NaN when there is none), max_count (the largest count of either cloud)."""
+    _fields_ = [("m", C.c_uint64), ("valid", C.c_uint64), ("significant", C.c_uint64), ("mean", C.c_double), ("rms", C.c_double),
+                ("max", C.c_double), ("max_count", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 PLADE_OUTLIER_STATISTICAL, PLADE_OUTLIER_RADIUS = 0, 1
 OUTLIER_MODES = {"statistical": PLADE_OUTLIER_STATISTICAL, "radius": PLADE_OUTLIER_RADIUS}
 
@@ -211,6 +226,10 @@ def load_library(path=LIB_PATH):
     sig("plade_smooth_default_params", argtypes=[C.POINTER(SmoothParams)], restype=None)
     sig("plade_smooth_cloud", argtypes=[p, p, u32, u32, C.POINTER(SmoothParams), p, p, p, p, p, p, p, C.POINTER(SmoothSummary)])
     sig("plade_cloud_smooth_dev", argtypes=[p, p, C.POINTER(SmoothParams), i32, C.POINTER(p), C.POINTER(SmoothSummary)])
+    sig("plade_m3c2_default_params", argtypes=[C.POINTER(M3c2Params)], restype=None)
+    sig("plade_cloud_m3c2", argtypes=[p, p, u32, p, u32, u32, p, u32, u32, p, C.POINTER(M3c2Params), p, p, p, p, p, p,
+                                      C.POINTER(M3c2Summary)])
+    sig("plade_cloud_m3c2_dev", argtypes=[p, p, p, p, p, C.POINTER(M3c2Params), p, p, p, p, p, p, C.POINTER(M3c2Summary)])
     sig("plade_sort_segments", argtypes=[p, p, p, p, u32, C.c_int, p, p])
     sig("plade_set_candidate_shard", argtypes=[p, u32, u32, u32, EXCHANGE_FN, p])
     sig("plade_registration_minsupport", argtypes=[p, p, u32, p, u32, i32, i32, p])
@@ -357,6 +376,22 @@ def _smooth_params(radius, min_neighbours, viewpoint):
 
 def _smooth_info(summ):
     return {k: getattr(summ, k) for k, _ in SmoothSummary._fields_ if k != "reserved"}
+
+
+def m3c2_default_params():
+    """plade_m3c2_default_params (pure: needs no GPU) as a dict of the plade_m3c2_params fields."""
+    prm = M3c2Params()
+    load_library().plade_m3c2_default_params(C.byref(prm))
+    return {k: getattr(prm, k) for k, _ in M3c2Params._fields_ if k != "reserved"}
+
+
+def _m3c2_params(radius, depth, min_points, reg_error):
+    prm = M3c2Params()
+    load_library().plade_m3c2_default_params(C.byref(prm))
+    prm.radius, prm.depth, prm.reg_error = float(radius), float(depth), float(reg_error)
+    if min_points is not None:
+        prm.min_points = int(min_points)
+    return prm
 
 
 def gicp_default_params():
@@ -1083,6 +1118,49 @@ class Context:
         self._check(self.L.plade_cloud_smooth_dev(self.h, cloud.h, C.byref(prm), 1 if fit_normals else 0, C.byref(h), C.byref(summ)))
         out = Cloud(self, None, handle=(int(summ.n), h))
         return (out, _smooth_info(summ)) if info else out
+
+    # ---- change detection: M3C2 distances -------------------------------------------------------------
+    def _m3c2(self, call, m, radius, depth, T, min_points, reg_error, per_point, moments):
+        T_in = None if T is None else _f32(T).reshape(4, 4).copy()
+        prm = _m3c2_params(radius, depth, min_points, reg_error)
+        dist = np.empty(m, np.float64)
+        lod = np.empty(m, np.float64) if per_point else None
+        sig = np.zeros(m, np.uint8) if per_point else None
+        count = np.empty((m, 2), np.uint32) if per_point else None
+        sigma = np.empty((m, 2), np.float64) if per_point else None
+        mom = np.empty((m, 4), np.float64) if moments else None
+        summ = M3c2Summary()
+        self._check(call(_ptr(T_in), C.byref(prm), _ptr(dist), _ptr(lod), _ptr(sig), _ptr(count), _ptr(sigma), _ptr(mom), C.byref(summ)))
+        info = {k: getattr(summ, k) for k, _ in M3c2Summary._fields_ if k != "reserved"}
+        if per_point:
+            info.update(lod=lod, significant_mask=sig.view(np.bool_), count=count, sigma=sigma)
+        if moments:
+            info["moments"] = mom
+        return dist, info
+
+    def m3c2(self, core, ref, cmp, radius, depth, T=None, min_points=None, reg_error=0.0, per_point=True, moments=False):
+        """plade_cloud_m3c2: M3C2 distances of the compared cloud `cmp` against the reference cloud `ref` (both (N, >= 3) float32,
+        x y z first) at the (M, 6) core points x y z nx ny nz: per core point a cylinder of `radius` and half-length `depth` along
+        its normal, the mean position of each cloud inside it along the normal, distance = mean_cmp - mean_ref and the 95 % level
+        of detection.  T: 4 x 4, cmp -> the frame of ref and core (None: the identity).  Returns (distance, info): distance (M,)
+        float64 (NaN where a cloud has fewer than min_points (default 4) points in the cylinder or the normal is zero / not
+        finite); info: a dict with m, valid, significant, mean, rms, max, max_count and -- with per_point -- lod (M float64),
+        significant_mask (M bools), count (M, 2 uint32: ref, cmp), sigma (M, 2 float64), and with moments the (M, 4) float64
+        sums S1_ref S2_ref S1_cmp S2_cmp."""
+        c = _f32(core)
+        self._check_cloud(c, "m3c2")
+        a, n_a, stride_a = _xyz_view(ref)
+        b, n_b, stride_b = _xyz_view(cmp)
+        return self._m3c2(lambda T_in, prm, *out: self.L.plade_cloud_m3c2(
+            self.h, _ptr(c), len(c), _ptr(a), n_a, stride_a, _ptr(b), n_b, stride_b, T_in, prm, *out), len(c), radius, depth, T,
+            min_points, reg_error, per_point, moments)
+
+    def m3c2_dev(self, core_cloud, ref_cloud, cmp_cloud, radius, depth, T=None, min_points=None, reg_error=0.0, per_point=True,
+                 moments=False):
+        """plade_cloud_m3c2_dev: m3c2 on resident clouds (upload, upload_xyz; core_cloud may be ref_cloud); bit-identical results."""
+        return self._m3c2(lambda T_in, prm, *out: self.L.plade_cloud_m3c2_dev(
+            self.h, core_cloud.h, ref_cloud.h, cmp_cloud.h, T_in, prm, *out), core_cloud.n, radius, depth, T, min_points, reg_error,
+            per_point, moments)
 
     # ---- merging registered clouds ---------------------------------------------------------------
     @staticmethod

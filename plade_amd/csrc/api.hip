@@ -11,6 +11,7 @@
 #include "ransac.h"
 #include "smooth.h"
 #include "gicp.h"
+#include "m3c2.h"
 
 using namespace plade;
 
@@ -147,6 +148,7 @@ extern "C" void plade_ctx_destroy(plade_ctx *ctx) {
     if (ctx->component_work) plade::component_work_destroy(ctx->component_work);
     if (ctx->smooth_work) plade::smooth_work_destroy(ctx->smooth_work);
     if (ctx->gicp_work) plade::gicp_work_destroy(ctx->gicp_work);
+    if (ctx->m3c2_work) plade::m3c2_work_destroy(ctx->m3c2_work);
     (void)hipStreamDestroy(ctx->stream);
     if (ctx->pf.stream) { (void)hipStreamSynchronize(ctx->pf.stream); (void)hipStreamDestroy(ctx->pf.stream); }
     delete ctx;

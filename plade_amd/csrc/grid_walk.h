@@ -195,6 +195,29 @@ __device__ __forceinline__ void ring_step(const GridView &g, int cx, int cy, int
     }
 }
 
+// The hand-out of ring_step on its own, for a walk that is no growing block (k_m3c2_walk): lane l offers one run of `sorted`,
+// [a0, a0 + len) (len = 0: none).  The candidates of all lanes' runs are handed out 64 at a time in lane order, ascending sorted
+// position within a run (the same prefix sum over the run lengths and binary search over the lanes): on_batch(valid, p) is
+// called by all lanes, p = this lane's candidate when valid.  Wave-uniform control flow; no LDS.
+template <class F>
+__device__ __forceinline__ void hand_out_runs(const GridView &g, uint32_t a0, uint32_t len, int lane, F &&on_batch) {
+    uint32_t incl = len;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) { const uint32_t o = __shfl_up(incl, d, 64); if (lane >= d) incl += o; }
+    const uint32_t pre = incl - len, cand_total = __shfl(incl, 63, 64);
+    for (uint32_t c0 = 0; c0 < cand_total; c0 += 64) {                   // (wave-uniform)
+        const uint32_t idx = c0 + (uint32_t)lane;
+        int o = 0;                                                       // the last lane whose run starts at or before idx
+#pragma unroll
+        for (int st = 32; st >= 1; st >>= 1) if (__shfl(pre, o + st, 64) <= idx) o += st;
+        const uint32_t off = idx - __shfl(pre, o, 64), a0_o = __shfl(a0, o, 64);
+        const bool valid = idx < cand_total;
+        float4 p = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (valid) p = g.sorted[a0_o + off];
+        on_batch(valid, p);
+    }
+}
+
 // wave-aggregated append of the failing lanes' values to a list (a lane kernel's hand-over to its ring kernel): one atomic per
 // wavefront.  Called by all lanes
 __device__ __forceinline__ void fail_append(bool fail, uint32_t value, uint32_t *list, uint32_t *count) {

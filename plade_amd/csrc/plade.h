@@ -125,6 +125,24 @@ struct CloudSmoothing {
 bool smooth_cloud(pcl::PointCloud<pcl::PointNormal>::Ptr cloud, pcl::PointCloud<pcl::PointNormal> &smoothed, double radius,
                   int min_neighbours = 6, bool use_fit_normals = false, CloudSmoothing *info = nullptr);
 
+/** Change detection (no counterpart in the reference): the fields of plade_m3c2_summary (include/plade_hip.h). */
+struct CloudComparison {
+    uint64_t m = 0, valid = 0, significant = 0;   // core points, those with enough points of both clouds, those beyond the level of detection
+    double mean = 0, rms = 0, max = 0;            // of the distances (max: of their absolute values) over the valid core points
+    uint32_t max_count = 0;                       // the largest number of points of one cloud in a cylinder
+};
+/** M3C2 distances on the GPU (plade_cloud_m3c2): the core points are the points of reference_cloud with their normals; per core
+ *  point a cylinder of `radius` and half-length `depth` (absolute, in the clouds' units) along the normal, the mean position of
+ *  each cloud inside it along the normal -- compared_cloud under `transformation` (compared -> reference) -- and the difference of
+ *  the two means.  `distances` receives one value per point of reference_cloud (NaN where a cloud has fewer than min_points points
+ *  in the cylinder or the normal is zero or not finite); info->significant counts the core points with |distance| above the 95 %
+ *  level of detection, to which reg_error (e.g. RegistrationQuality::rmse) is added.  false: invalid input or no GPU; a message is
+ *  printed, `distances` and `info` are unchanged.  The CLI prints one summary line per registered pair (reference = the target)
+ *  when PLADE_M3C2=<radius>,<depth>[,<min_points>[,<reg_error>]] is set. */
+bool compare_clouds(const Eigen::Matrix4f &transformation, pcl::PointCloud<pcl::PointNormal>::Ptr reference_cloud,
+                    pcl::PointCloud<pcl::PointNormal>::Ptr compared_cloud, double radius, double depth, std::vector<double> &distances,
+                    CloudComparison *info = nullptr, int min_points = 4, double reg_error = 0.0);
+
 /** Merging registered clouds (no counterpart in the reference): the fields of plade_merge_summary (include/plade_hip.h). */
 struct CloudMerge {
     uint64_t n_in = 0, n_out = 0, n_shared = 0;   // points in, rows out, rows to which two or more clouds contributed

@@ -261,6 +261,75 @@ void evaluate_line(plade_ctx *ctx, const float *T16, const float *tg, size_t n_t
     con_out() << b << std::endl;
 }
 
+// PLADE_M3C2=<radius>,<depth>[,<min_points>[,<reg_error>]] (opt-in, absolute, in the clouds' units): every pair that registered -- after
+// the ICP / GICP refinement when that is on -- is compared by M3C2 distances on the GPU (plade_cloud_m3c2: core points = reference
+// = the target with its normals, compared = the source under the final transformation; min_points 4 and reg_error 0 when not
+// given) and one console line reports the library's summary.  The pair is compared as it was registered (after the target / source
+// switch).  A value that does not parse (radius or depth not positive and finite, min_points not an integer >= 2, reg_error negative
+// or not finite, anything behind them) prints one warning and compares nothing; unset, nothing changes.
+struct M3c2Switch { bool on = false; double radius = 0.0, depth = 0.0, reg_error = 0.0; int min_points = 4; };
+const M3c2Switch &m3c2_switch() {
+    static const M3c2Switch sw = [] {
+        M3c2Switch v, off;
+        const char *w = getenv("PLADE_M3C2");
+        if (!w) return off;
+        char *end = nullptr;
+        v.radius = strtod(w, &end);
+        bool ok = end != w && std::isfinite(v.radius) && v.radius > 0.0 && std::isfinite(v.radius * v.radius) && *end == ',';
+        if (ok) {
+            const char *a = end + 1;
+            v.depth = strtod(a, &end);
+            ok = end != a && std::isfinite(v.depth) && v.depth > 0.0;
+        }
+        if (ok && *end == ',') {
+            const char *a = end + 1;
+            const long m = strtol(a, &end, 10);
+            ok = end != a && m >= 2 && m <= INT32_MAX;
+            v.min_points = (int)m;
+            if (ok && *end == ',') {
+                a = end + 1;
+                v.reg_error = strtod(a, &end);
+                ok = end != a && std::isfinite(v.reg_error) && v.reg_error >= 0.0;
+            }
+        }
+        if (!ok || *end != '\0') {
+            std::cerr << "warning: PLADE_M3C2=" << w
+                      << " is not <radius>,<depth>[,<min_points>[,<reg_error>]] with radius > 0, depth > 0, min_points >= 2 and reg_error >= 0; no comparison"
+                      << std::endl;
+            return off;
+        }
+        v.on = true;
+        return v;
+    }();
+    return sw;
+}
+// M3C2 of the packed source under T16 against the packed reference at the given core points (all x y z nx ny nz rows); dist: one
+// double per core point when wanted.  false: a message has been printed
+bool m3c2_packed(plade_ctx *ctx, const float *T16, const float *core, size_t m, const float *ref, size_t n_a, const float *cmp, size_t n_b,
+                 double radius, double depth, int min_points, double reg_error, double *dist, plade_m3c2_summary &s) {
+    plade_m3c2_params prm;
+    plade_m3c2_default_params(&prm);
+    prm.radius = radius; prm.depth = depth; prm.min_points = min_points; prm.reg_error = reg_error;
+    trace("m3c2: comparing");
+    const int rc = plade_cloud_m3c2(ctx, core, (uint32_t)m, ref, (uint32_t)n_a, 6, cmp, (uint32_t)n_b, 6, T16, &prm, dist, nullptr, nullptr,
+                                    nullptr, nullptr, nullptr, &s);
+    trace("m3c2: done");
+    if (rc != PLADE_OK) {
+        con_err() << "cloud comparison failed: " << plade_last_error(ctx) << std::endl;
+        return false;
+    }
+    return true;
+}
+void m3c2_line(plade_ctx *ctx, const float *T16, const float *tg, size_t n_t, const float *sr, size_t n_s) {
+    const M3c2Switch &sw = m3c2_switch();
+    plade_m3c2_summary s;
+    if (!sw.on || !m3c2_packed(ctx, T16, tg, n_t, tg, n_t, sr, n_s, sw.radius, sw.depth, sw.min_points, sw.reg_error, nullptr, s)) return;
+    char b[280];
+    snprintf(b, sizeof(b), "m3c2: %llu of %llu core points valid, %llu significant (mean %.6g, rms %.6g, max %.6g)", (unsigned long long)s.valid,
+             (unsigned long long)s.m, (unsigned long long)s.significant, s.mean, s.rms, s.max);
+    con_out() << b << std::endl;
+}
+
 // PLADE_REMOVE_OUTLIERS=<k>[,<alpha>] (opt-in, 0 / unset = off): both clouds of a pair pass the statistical outlier filter on the
 // GPU (plade_filter_outliers: k nearest neighbours, threshold mu + alpha sigma, alpha 1 when not given) after they are read and
 // before PLADE_ESTIMATE_NORMALS; one console line per cloud.  A value that does not parse (k not an integer in [1, 64], alpha
@@ -646,6 +715,7 @@ bool register_packed(Eigen::Matrix<float, 4, 4> &transformation, const float *tg
     con_out() << "done. time: " << w.str() << std::endl;
     refine_selected(ctx, T16, tg, n_t, sr, n_s);
     if (evaluate_dist() > 0.f) evaluate_line(ctx, T16, tg, n_t, sr, n_s);
+    m3c2_line(ctx, T16, tg, n_t, sr, n_s);
     to_matrix(T16, transformation);
     return true;
 }
@@ -813,6 +883,7 @@ void registration_group(size_t count, Eigen::Matrix<float, 4, 4> *transformation
         con_out() << "done. time: " << w.str() << std::endl;
         refine_selected(ctx, T16 + 16 * q, it.tg, it.n_t, it.sr, it.n_s);
         if (evaluate_dist() > 0.f) evaluate_line(ctx, T16 + 16 * q, it.tg, it.n_t, it.sr, it.n_s);
+        m3c2_line(ctx, T16 + 16 * q, it.tg, it.n_t, it.sr, it.n_s);
         to_matrix(T16 + 16 * q, transformations[it.pair]);
         if (it.switched) transformations[it.pair] = transformations[it.pair].inverse();
         if (merge_leaf() >= 0.f)
@@ -913,6 +984,29 @@ bool smooth_cloud(pcl::PointCloud<pcl::PointNormal>::Ptr cloud, pcl::PointCloud<
         smoothed.at(i) = pcl::PointNormal(p[0], p[1], p[2], q[0], q[1], q[2]);
     }
     if (info) { info->n = s.n; info->fitted = s.fitted; info->rms = s.rms; info->max = s.max; info->max_count = s.max_count; }
+    return true;
+}
+
+// change detection: see plade.h
+bool compare_clouds(const Eigen::Matrix4f &transformation, pcl::PointCloud<pcl::PointNormal>::Ptr reference_cloud,
+                    pcl::PointCloud<pcl::PointNormal>::Ptr compared_cloud, double radius, double depth, std::vector<double> &distances,
+                    CloudComparison *info, int min_points, double reg_error) {
+    plade_ctx *ctx = context();
+    if (!ctx) return false;
+    if (!reference_cloud || !compared_cloud) { con_err() << "compare_clouds: null cloud" << std::endl; return false; }
+    std::vector<float> ref = flatten(*reference_cloud), cmp = flatten(*compared_cloud);
+    float T16[16];
+    for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) T16[4 * r + c] = transformation(r, c);
+    std::vector<double> dist(reference_cloud->size());
+    plade_m3c2_summary s;
+    if (!m3c2_packed(ctx, T16, ref.data(), reference_cloud->size(), ref.data(), reference_cloud->size(), cmp.data(), compared_cloud->size(),
+                     radius, depth, min_points, reg_error, dist.data(), s))
+        return false;
+    distances.swap(dist);
+    if (info) {
+        info->m = s.m; info->valid = s.valid; info->significant = s.significant;
+        info->mean = s.mean; info->rms = s.rms; info->max = s.max; info->max_count = s.max_count;
+    }
     return true;
 }
 

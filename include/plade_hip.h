@@ -734,7 +734,9 @@ int plade_cloud_download(plade_ctx *ctx, const plade_cloud *cloud, float *rows, 
 
 /* ---- instrumentation ---------------------------------------------------------------------- */
 /* Named intermediates of the last registration (when params.dump != 0). Returns 0 if found;
- * the pointer stays valid until the next call on this ctx. */
+ * the pointer stays valid until the next call on this ctx.
+ * Among them the acceptance chains of every cloud's last detect call: [tgt_ | src_]extract_trace_{call_u, call_f, entry,
+ * cand, slot_f, slot_u, slot_w} (no tag after plade_extract_planes; layout: ExtractTrace in plade_amd/csrc/ransac.h). */
 int plade_dump_get(plade_ctx *ctx, const char *name, const void **ptr, int64_t *nbytes);
 /* Per-stage GPU/host seconds and byte counts of the last registration:
  * names is a ';'-separated list, values has one double per name. */

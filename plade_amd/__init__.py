@@ -279,6 +279,13 @@ DUMP_FIELDS = {
     "tgt_planes": np.float32, "tgt_plane_offsets": np.int32, "tgt_plane_idx": np.int32,
     "src_planes": np.float32, "src_plane_offsets": np.int32, "src_plane_idx": np.int32,
 }
+# the acceptance chains of the last detect call of a cloud (ransac.h: ExtractTrace; replayed by tests/extract_replay.py):
+# untagged after extract_planes, tgt_ / src_ after a registration
+EXTRACT_TRACE_FIELDS = {"call_u": np.uint32, "call_f": np.float32, "entry": np.int32, "cand": np.float32,
+                        "slot_f": np.float32, "slot_u": np.uint32, "slot_w": np.float64}
+for _tag in ("", "tgt_", "src_"):
+    for _k, _dt in EXTRACT_TRACE_FIELDS.items():
+        DUMP_FIELDS[f"{_tag}extract_trace_{_k}"] = _dt
 
 
 def device_synchronize(device=0):

@@ -368,6 +368,9 @@ uint32_t merge_dev(plade_ctx *ctx, MergeWork &W, uint32_t k, const float *const 
         summary->reserved = 0;
     }
     float ms[4] = {0.f, 0.f, 0.f, 0.f};
+    // sync() above may have waited on a flag in host memory instead of the stream: the work is done, but the runtime need not
+    // have marked the events complete yet, and hipEventElapsedTime then answers "device not ready" (seen once in ~500 calls)
+    HIP_TRY(hipEventSynchronize(W.ev[fuse ? 4 : 1]));
     for (int q = 0; q < (fuse ? 4 : 1); ++q) HIP_TRY(hipEventElapsedTime(&ms[q], W.ev[q], W.ev[q + 1]));
     ctx->stats.clear();
     ctx->stats.add("merge_transform_s", 1e-3 * ms[0]);

@@ -13,7 +13,31 @@ struct RansacParams {
     bool host_indices = true;   // also copy the inlier index lists to the host (PlaneSetOut::idx)
 };
 
+// The acceptance chains of a detect call (plade_params.dump only), flat, E entries in the order of acceptance; see ransac.hip
+// (RTrace) and tests/extract_replay.py, which replays them on the CPU.
+struct ExtractTrace {
+    bool valid = false;
+    std::vector<uint32_t> call_u;   // n, min_support, orient, iterations, n_remaining, deferred chains, E, planes
+    std::vector<float> call_f;      // eps, 3 eps, bitmap eps, cos threshold
+    std::vector<int32_t> entry;     // E x 5: iteration, chain, final slot, stop index, plane index in the output or -1
+    std::vector<float> cand;        // E x 8: the hypothesis (n, dist), position
+    std::vector<float> slot_f;      // E x 4 x 7: n, pos, dist of every slot (slots the chain did not compute: zero)
+    std::vector<uint32_t> slot_u;   // E x 4 x 4: n_list, n_kept, err, converged
+    std::vector<double> slot_w;     // E x 4: wscore
+    void put(plade_ctx *ctx, const std::string &prefix) const {
+        if (!valid) return;
+        ctx->put(prefix + "extract_trace_call_u", call_u.data(), call_u.size());
+        ctx->put(prefix + "extract_trace_call_f", call_f.data(), call_f.size());
+        ctx->put(prefix + "extract_trace_entry", entry.data(), entry.size());
+        ctx->put(prefix + "extract_trace_cand", cand.data(), cand.size());
+        ctx->put(prefix + "extract_trace_slot_f", slot_f.data(), slot_f.size());
+        ctx->put(prefix + "extract_trace_slot_u", slot_u.data(), slot_u.size());
+        ctx->put(prefix + "extract_trace_slot_w", slot_w.data(), slot_w.size());
+    }
+};
+
 struct PlaneSetOut {
+    ExtractTrace trace;            // of the detect call that produced this set (dump only)
     std::vector<float> coef;       // P x 4 (unit n, d = -n.p)
     std::vector<int32_t> offsets;  // P + 1
     std::vector<int32_t> idx;      // original point indices

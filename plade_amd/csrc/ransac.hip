@@ -172,6 +172,31 @@ struct RResult {
     uint32_t offset[R_MAXP];
 };
 
+// The acceptance chains of a detect call as k_r_decide saw them (plade_params.dump only: the kernels get a null pointer
+// otherwise and nothing of this exists).  One entry per chain the loop accepted, in the order of acceptance -- also those
+// that end below min_support (points removed, no plane) or without a point -- with the hypothesis and all four slots, so
+// that a CPU replay can recompute every list, component, refit and score of the call (tests/extract_replay.py).
+struct TraceSlot {
+    float n[3], pos[3], dist;
+    uint32_t n_list, n_kept, err, converged, pad;
+    double wscore;
+};
+struct TraceEntry {
+    uint32_t it, chain, final_slot, stop;
+    int32_t out;                     // index of the entry's plane in the output, -1: none
+    uint32_t pad[3];
+    float cand[8];                   // ChainHdr::cand
+    TraceSlot st[4];
+};
+struct RTrace {
+    uint32_t n_entries, n_planes, closed;            // closed: the scalars below are those of the iteration that ended the call
+    uint32_t iterations, n_remaining, n_deferred;
+    uint32_t n, min_support, orient, pad;
+    float eps, eps3, bitmap_eps, cos_t;
+    uint32_t pad2[2];
+    TraceEntry e[R_MAXP];
+};
+
 struct CloudView {
     const float *x, *y, *z, *nx, *ny, *nz;
     uint32_t n;
@@ -233,6 +258,8 @@ struct RArgs {
     uint32_t tile_start[R_G + 1];
     uint32_t pad_;
     const RCloudArgs *dev;           // the committed device copy of c (nullptr: not committed)
+    RTrace *trace;                   // R_G trace blocks for k_r_init / k_r_decide (nullptr: no dump).  Part of the bytes that key the
+                                     // captured graphs: a traced call replays its own capture of the same launch sequence
     operator RKArgs() const {
         RKArgs k;
         k.c = dev; k.ng = ng; k.topup = topup; k.pad_ = 0;
@@ -565,11 +592,12 @@ struct RInitCloud {
 };
 struct RInit { RInitCloud c[R_G]; };
 
-__global__ __launch_bounds__(TPB) void k_r_init(const RKArgs A, const RInit I) {
+__global__ __launch_bounds__(TPB) void k_r_init(const RKArgs A, const RInit I, RTrace *trace) {
     uint32_t tile;
     const int g = scan_group(A, tile);
     const RCloudArgsK &C = cloud_args(A, g);
     const RInitCloud &P = I.c[g];
+    if (trace && P.active && tile == 0 && threadIdx.x == 0) { trace[g].n_entries = 0; trace[g].n_planes = 0; trace[g].closed = 0; }
     if (!P.active) {
         if (tile == 0 && threadIdx.x == 0) { C.st->active = 0; C.st->done = 1; C.st->nc = 0; C.st->aj_n = 0; C.st->npool = 0; C.st->sampling = 0; C.st->fresh = 0; }
         return;
@@ -1724,11 +1752,23 @@ __global__ __launch_bounds__(256) void k_r_fit(const RKArgs A, int k) {
 // bookkeeping (RansacShapeDetector.cpp:666-675), output planes (plane_extraction.cpp:134-149), the pool without
 // the batch, and what the next iteration does.  One lane per cloud does the sequential part.
 constexpr int DEC_T = 256;   // lanes of k_r_decide: the staging loads and the deferral tests use all of them, the rest wave 0
-__global__ __launch_bounds__(DEC_T) void k_r_decide(const RKArgs A) {
+// dump only: slot k of a traced entry, by one lane (lane k = 0 adds the hypothesis); the sequential lane wrote the header
+__device__ __forceinline__ void trace_slot(TraceEntry *te, int k, const PlaneState &s, const float4 *cand) {
+    TraceSlot &t = te->st[k];
+    for (int q = 0; q < 3; ++q) { t.n[q] = s.n[q]; t.pos[q] = s.pos[q]; }
+    t.dist = s.dist; t.n_list = s.n_list; t.n_kept = s.n_kept; t.err = s.err; t.converged = s.converged; t.pad = 0; t.wscore = s.wscore;
+    if (k == 0) {
+        te->cand[0] = cand[0].x; te->cand[1] = cand[0].y; te->cand[2] = cand[0].z; te->cand[3] = cand[0].w;
+        te->cand[4] = cand[1].x; te->cand[5] = cand[1].y; te->cand[6] = cand[1].z; te->cand[7] = cand[1].w;
+    }
+}
+
+__global__ __launch_bounds__(DEC_T) void k_r_decide(const RKArgs A, RTrace *trace) {
     const RCloudArgsK &C = cloud_args(A, blockIdx.x);
     RState *S = C.st;
     RResult *R = C.res;
     if (!S->active) return;
+    RTrace *T = trace ? trace + blockIdx.x : nullptr;
     // Everything the sequential part touches is fetched by all lanes at once (one lane alone pays a round trip to L2 per
     // field, and every store to the state forces the next load to be re-issued): the chains' results, the pool, the scalars.
     __shared__ PlaneState s_st[R_B][4];
@@ -1753,6 +1793,7 @@ __global__ __launch_bounds__(DEC_T) void k_r_decide(const RKArgs A) {
     // (1) per chain: the reference's refit loop replayed on the four slots' results (RansacShapeDetector.cpp:633-655)
     __shared__ int s_final[R_B], s_stop[R_B];
     __shared__ uint32_t s_defer[R_B];
+    __shared__ uint32_t s_trace[R_B];   // dump: the chain's entry in the trace, 0xffffffff = none
     if (threadIdx.x < nc_all) {
         const PlaneState *st = s_st[threadIdx.x];
         int final_slot = 0, stop = 4;
@@ -1768,6 +1809,7 @@ __global__ __launch_bounds__(DEC_T) void k_r_decide(const RKArgs A) {
         s_final[threadIdx.x] = final_slot;
         s_stop[threadIdx.x] = stop;
         s_defer[threadIdx.x] = 0;
+        s_trace[threadIdx.x] = 0xffffffffu;
     }
     __syncthreads();
     // (2) Accepting the chains of a batch together equals accepting them one by one, best first, only if no chain's score
@@ -1818,6 +1860,18 @@ __global__ __launch_bounds__(DEC_T) void k_r_decide(const RKArgs A) {
             n_stop[stop] += 1;
             const PlaneState &cs = st[final_slot];
             const uint32_t cand_size = cs.n_kept;
+            TraceEntry *te = nullptr;
+            if (T) {
+                const uint32_t q = T->n_entries;
+                T->n_entries = q + 1;
+                if (q < R_MAXP) {   // the header here, the slots by other lanes below
+                    te = &T->e[q];
+                    s_trace[b] = q;
+                    te->it = S->it; te->chain = b; te->final_slot = (uint32_t)final_slot; te->stop = (uint32_t)stop; te->out = -1;
+                    te->pad[0] = te->pad[1] = te->pad[2] = 0;
+                }
+            }
+            // nothing to remove and no plane: frac below would be 1 and `drawn`, n_remaining and the output stay as they are
             if (cand_size == 0) continue;
             if (n_acc >= R_MAXP) { err = 3; done = 1; break; }
             const uint32_t id = n_acc;
@@ -1842,6 +1896,7 @@ __global__ __launch_bounds__(DEC_T) void k_r_decide(const RKArgs A) {
                 S->acc_coef[id][0] = nn[0]; S->acc_coef[id][1] = nn[1]; S->acc_coef[id][2] = nn[2]; S->acc_coef[id][3] = d;
                 support = cand_size;
                 aj_out = out_off;
+                if (T) { if (te) te->out = (int32_t)T->n_planes; T->n_planes += 1; }
             }
             S->acc_support[id] = support;
             S->acc_dbg[id] = (S->it << 16) | (b << 8) | (uint32_t)final_slot;
@@ -1858,6 +1913,10 @@ __global__ __launch_bounds__(DEC_T) void k_r_decide(const RKArgs A) {
         S->n_accepts = n_accepts; S->n_remaining = n_remaining; S->n_acc = n_acc; S->out_off = out_off; S->drawn = drawn; S->err = err;
     }
     __syncthreads();
+    if (T && threadIdx.x >= DEC_T - 4 * R_B) {   // dump: one lane of the last wave per (chain, slot)
+        const uint32_t b = (threadIdx.x - (DEC_T - 4 * R_B)) >> 2, k = threadIdx.x & 3;
+        if (b < nc_all && s_trace[b] != 0xffffffffu) trace_slot(&T->e[s_trace[b]], (int)k, s_st[b][k], chain_of(C, b).hdr->cand);
+    }
     // the pool without the batch (batch indices are ascending), order kept: every lane moves its own entry
     if (nc_all) {
         bool in_batch = false;
@@ -1888,6 +1947,12 @@ __global__ __launch_bounds__(DEC_T) void k_r_decide(const RKArgs A) {
     // The host-mapped block is written once, when the call ends (stores over PCIe are slow: all 64 lanes share them);
     // until then the host only needs the iteration count.
     const uint32_t done_now = S->done;
+    if (T && done_now && threadIdx.x == 0 && !T->closed) {   // (a speculative iteration behind the end of the call finds it closed)
+        T->closed = 1;
+        T->iterations = S->it; T->n_remaining = S->n_remaining; T->n_deferred = S->n_deferred;
+        T->n = S->n; T->min_support = S->min_support; T->orient = S->orient;
+        T->eps = S->eps; T->eps3 = S->eps3; T->bitmap_eps = S->bitmap_eps; T->cos_t = S->cos_t;
+    }
     if (done_now) {
         const uint32_t na = S->n_acc;
         for (uint32_t i = threadIdx.x; i < 4 * na; i += DEC_T) (&R->coef[0][0])[i] = (&S->acc_coef[0][0])[i];
@@ -2389,6 +2454,7 @@ struct RansacWork {
     uint32_t generation = 0;         // detect calls issued on this work area
     DBuf<uint32_t> keys_in, vals_in, keys, perm;
     DBuf<RCloudArgs> args_dev;       // the per-cloud argument table the kernels read (args_commit)
+    DBuf<RTrace> trace;              // R_G trace blocks, allocated by the first detect call with plade_params.dump set
     uint64_t args_hash = 0;          // of the table uploaded last
     std::map<uint64_t, hipGraphExec_t> graphs;   // the iteration sequence, keyed on everything baked into its launches
     std::map<uint64_t, std::vector<std::string>> graph_tags;   // of the graphs captured with clock stamps (plade_ctx::graph_clocks)
@@ -2512,7 +2578,7 @@ void enqueue_iteration(plade_ctx *ctx, const RArgs &A) {
         hipLaunchKernelGGL(k_r_select_cc, dim3(std::min(VGRID_WGS, loop_grid(nb_max) * R_B * ng)), dim3(TPB), 0, st, A, k);
         hipLaunchKernelGGL(k_r_fit, dim3(R_B * ng), dim3(256), 0, st, A, k);
     }
-    hipLaunchKernelGGL(k_r_decide, dim3(ng), dim3(DEC_T), 0, st, A);
+    hipLaunchKernelGGL(k_r_decide, dim3(ng), dim3(DEC_T), 0, st, A, A.trace);
     hipLaunchKernelGGL(k_r_assign, dim3(std::min(VGRID_WGS, loop_grid(nb_max) * R_B * ng)), dim3(TPB), 0, st, A);
     // the scan view of the next iteration: the points this one left
     hipLaunchKernelGGL(k_view_count, dim3(std::min(VGRID_WGS, tiles)), dim3(TPB), 0, st, A);
@@ -2668,6 +2734,8 @@ void ransac_detect_prepared(plade_ctx *ctx, RansacWork &W, RansacJob jobs[RANSAC
     Clock::time_point t0 = Clock::now();
     RArgs A = make_args(W, ng, ctx->params.ransac_topup != 0);
     args_commit(ctx, W, A);
+    const bool tracing = ctx->params.dump != 0;
+    if (tracing) { W.trace.ensure(R_G); A.trace = W.trace.p; }
     RInit I;
     memset(&I, 0, sizeof(I));
     RResult *res[R_G];
@@ -2679,7 +2747,7 @@ void ransac_detect_prepared(plade_ctx *ctx, RansacWork &W, RansacJob jobs[RANSAC
         if (!J.active || s.n < 3) {
             if (J.active && J.out) {   // plane_extraction.cpp:181-184: fewer than three points, no planes
                 J.out->coef.clear(); J.out->offsets.assign(1, 0); J.out->idx.clear(); J.out->d_idx = nullptr; J.out->remaining = s.n;
-                J.out->n_score_passes = 0; J.out->score_bytes = 0;
+                J.out->n_score_passes = 0; J.out->score_bytes = 0; J.out->trace = ExtractTrace();
             }
             J.active = false;
             continue;
@@ -2707,7 +2775,7 @@ void ransac_detect_prepared(plade_ctx *ctx, RansacWork &W, RansacJob jobs[RANSAC
     if (nres == 0) return;
     uint32_t tiles = 0;
     for (int g = 0; g < ng; ++g) tiles += A.c[g].L.nb;
-    hipLaunchKernelGGL(k_r_init, dim3(tiles), dim3(TPB), 0, ctx->stream, A, I);
+    hipLaunchKernelGGL(k_r_init, dim3(tiles), dim3(TPB), 0, ctx->stream, A, I, A.trace);
     HIP_TRY(hipGetLastError());
     uint32_t iterations = 0;
     if (ctx->profiling()) {
@@ -2813,7 +2881,44 @@ void ransac_detect_prepared(plade_ctx *ctx, RansacWork &W, RansacJob jobs[RANSAC
     }
     bool any_host = false;
     for (int g = 0; g < ng; ++g) any_host = any_host || (jobs[g].active && jobs[g].rp.host_indices);
-    if (any_host) ctx->sync();
+    // dump: the trace blocks of this call's clouds come back behind everything the call queued
+    std::vector<std::vector<char>> tr(tracing ? ng : 0);
+    if (tracing)
+        for (int g = 0; g < ng; ++g) {
+            if (!jobs[g].active) continue;
+            tr[g].resize(sizeof(RTrace));
+            ctx->d2h(tr[g].data(), W.trace.p + g, sizeof(RTrace));
+        }
+    if (any_host || tracing) ctx->sync();
+    if (tracing)
+        for (int g = 0; g < ng; ++g) {
+            if (!jobs[g].active) continue;
+            const RTrace &T = *reinterpret_cast<const RTrace *>(tr[g].data());
+            PLADE_REQUIRE(T.closed == 1 && T.n_entries <= R_MAXP, PLADE_EDEVICE, "plane extraction: incomplete trace");
+            ExtractTrace &o = jobs[g].out->trace;
+            o = ExtractTrace();
+            o.valid = true;
+            o.call_u = {T.n, T.min_support, T.orient, T.iterations, T.n_remaining, T.n_deferred, T.n_entries, T.n_planes};
+            o.call_f = {T.eps, T.eps3, T.bitmap_eps, T.cos_t};
+            const uint32_t E = T.n_entries;
+            o.entry.resize(5 * (size_t)E); o.cand.resize(8 * (size_t)E);
+            o.slot_f.assign(28 * (size_t)E, 0.f); o.slot_u.assign(16 * (size_t)E, 0u); o.slot_w.assign(4 * (size_t)E, 0.0);
+            for (uint32_t e = 0; e < E; ++e) {
+                const TraceEntry &te = T.e[e];
+                int32_t *en = &o.entry[5 * (size_t)e];
+                en[0] = (int32_t)te.it; en[1] = (int32_t)te.chain; en[2] = (int32_t)te.final_slot; en[3] = (int32_t)te.stop; en[4] = te.out;
+                memcpy(&o.cand[8 * (size_t)e], te.cand, sizeof(te.cand));
+                for (uint32_t k = 0; k <= std::min(te.stop, 3u); ++k) {
+                    const TraceSlot &ts = te.st[k];
+                    float *f = &o.slot_f[28 * (size_t)e + 7 * k];
+                    for (int q = 0; q < 3; ++q) { f[q] = ts.n[q]; f[3 + q] = ts.pos[q]; }
+                    f[6] = ts.dist;
+                    uint32_t *u = &o.slot_u[16 * (size_t)e + 4 * k];
+                    u[0] = ts.n_list; u[1] = ts.n_kept; u[2] = ts.err; u[3] = ts.converged;
+                    o.slot_w[4 * (size_t)e + k] = ts.wscore;
+                }
+            }
+        }
 }
 
 void ransac_detect(plade_ctx *ctx, RansacWork &W, const CloudDev &cloud, const RansacParams &rp, PlaneSetOut &out) {

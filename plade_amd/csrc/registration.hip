@@ -84,6 +84,7 @@ void extract_clouds(plade_ctx *ctx, int n_clouds, const CloudDev *const clouds[]
                     r.offsets.push_back((int32_t)r.idx.size());
                 }
                 r.n_score_passes = pl.n_score_passes;
+                r.trace = std::move(pl.trace);   // (of the untrimmed call: its plane indices are those before the sort)
                 pl = std::move(r);   // d_idx is null now: the next stage uploads the reordered host lists
                 finished[g] = true;
                 continue;
@@ -122,6 +123,8 @@ int register_tail(plade_ctx *pc, plade_ctx *owner, int slot_t, const CloudDev &t
         ctx->put("src_planes", sp.coef.data(), sp.coef.size());
         ctx->put("src_plane_offsets", sp.offsets.data(), sp.offsets.size());
         ctx->put("src_plane_idx", sp.idx.data(), sp.idx.size());
+        tp.trace.put(ctx, "tgt_");
+        sp.trace.put(ctx, "src_");
     }
     ctx->stats.add("n_planes_tgt", tp.P());
     ctx->stats.add("n_planes_src", sp.P());
@@ -472,6 +475,7 @@ extern "C" int plade_extract_planes(plade_ctx *ctx, const float *pos_nrm, uint32
         rp.dist_rel = dist_rel; rp.bitmap_rel = bitmap_rel; rp.cos_thresh = cos_thresh; rp.overlook_p = overlook_p;
         PlaneSetOut out;
         ransac_detect(ctx, *ctx->ransac_work, cloud, rp, out);
+        out.trace.put(ctx, "");
         const uint32_t P = out.P();
         PLADE_REQUIRE(P <= max_planes, PLADE_ECAP, "plade_extract_planes: more planes than max_planes");
         memcpy(planes_out, out.coef.data(), 16 * (size_t)P);

@@ -696,6 +696,86 @@ int plade_cloud_m3c2_dev(plade_ctx *ctx, plade_cloud *core, plade_cloud *ref, pl
                          const plade_m3c2_params *params, double *distance_out, double *lod_out, uint8_t *significant_out,
                          uint32_t *count_out, double *sigma_out, double *moments_out, plade_m3c2_summary *summary);
 
+/* ---- point descriptors and their match between two clouds: FPFH (Rusu, Blodow, Beetz 2009; no reference counterpart) -------------
+ * Semantics (plade_amd/csrc/fpfh.h).  Input: n >= 1 rows x y z nx ny nz in fp32 with finite coordinates (the
+ * normals need not be unit and may be non-finite).
+ *   neighbours   d(i, j) = the fp32 squared distance of plade_smooth_cloud; N_i = { j : 0 < d(i, j) < r2 }, r2 = (float)r * (float)r:
+ *                strict on both sides, so coincident points -- i itself included -- are no neighbours.
+ *   axis         len2 = (nx nx + ny ny) + nz nz in fp64, n^ = double(n) / sqrt(len2).  A point whose len2 is 0 or not finite has no
+ *                axis: it has no descriptor and is nobody's neighbour.  Not an error.
+ *   pair (i, j)  for j in N_i, both with an axis, in fp64 without contraction, every dot product (a_x b_x + a_y b_y) + a_z b_z:
+ *                q = p_j - p_i, l = sqrt(q.q), e = q / l, a_i = n^_i.e, a_j = n^_j.e; when fabs(a_i) < fabs(a_j) the roles swap:
+ *                (n1, n2, dp) = (n^_j, n^_i, -e), otherwise (n^_i, n^_j, e).  f3 = n1.dp; v = dp x n1, a pair with |v| = 0 is not
+ *                counted, else v /= |v|; w = n1 x v; f2 = v.n2; f1 = atan2(w.n2, n1.n2).  Eleven bins per feature:
+ *                b1 = clamp((int)floor(11 ((f1 + pi) / (2 pi))), 0, 10), b2 = clamp((int)floor(11 ((f2 + 1) 0.5)), 0, 10), b3 from
+ *                f3 as b2; the pair adds one to H_i[b1], H_i[11 + b2] and H_i[22 + b3].
+ *   SPFH         H_i (33 counters) and c_i, the number of counted pairs: exact integers.  i is described iff it has an axis and
+ *                c_i >= min_pairs.
+ *   FPFH         for a described i, over the described j in N_i: w_ij = (double)r2 / (double)d(i, j), W_i = sum w_ij,
+ *                R_i[b] = sum w_ij (double(H_j[b]) / double(c_j)): fp64 sums in the fixed order of the grid walk, no atomics.
+ *                W_i > 0: F_i[b] = (float)(50 (double(H_i[b]) / double(c_i) + R_i[b] / W_i)); W_i = 0:
+ *                F_i[b] = (float)((100 double(H_i[b])) / double(c_i)).  Each block of 11 bins sums to 100 up to rounding.  A point
+ *                that is not described gets 33 NaNs.
+ *   output       by original index; each array may be NULL.  desc_out: n x 33 floats; described_out: n bytes 0 / 1; pairs_out: n
+ *                uint32 (c_i); spfh_out: n x 33 uint32 (H_i) and raw_out: n x 34 doubles (W_i, then R_i; zeros where the point is
+ *                not described) -- test seams.  summary: n, described, the largest c_i and the mean c_i over the described points
+ *                (an exact integer sum and one division; 0 when nothing is described).
+ * H, c and described depend on the point set and the radius only; the last bits of raw follow the grid (another bounding box, a
+ * permutation of the input).  The same input gives the same bits on every run, on every context and from plade_cloud_fpfh_dev.
+ * Errors: PLADE_EINVAL for a NULL cloud or summary, n = 0, a non-finite coordinate, radius <= 0 or not finite (or its fp32 square not
+ * finite or below FLT_MIN), min_pairs < 1; the context stays usable.  plade_stats_get then reports fpfh_grid_s (grid + axes),
+ * fpfh_spfh_s, fpfh_weight_s (HIP events on the context's stream) and fpfh_described. */
+typedef struct plade_fpfh_params {
+    double radius;               /* must be set (> 0), absolute, in the cloud's units */
+    int32_t min_pairs;           /* >= 1: the smallest number of counted pairs of a described point */
+    int32_t reserved;            /* 0 */
+} plade_fpfh_params;
+typedef struct plade_fpfh_summary {
+    uint64_t n, described;
+    double mean_pairs;           /* of c_i over the described points */
+    uint32_t max_pairs;          /* the largest c_i of any point */
+    uint32_t reserved;           /* 0 */
+} plade_fpfh_summary;
+typedef struct plade_features plade_features; /* a device-resident table of n x 33 descriptors */
+/* The defaults: radius = 0 (unset), min_pairs = 5.  Needs no GPU. */
+void plade_fpfh_default_params(plade_fpfh_params *p);
+int plade_cloud_fpfh(plade_ctx *ctx, const float *pos_nrm, uint32_t n, const plade_fpfh_params *params, float *desc_out,
+                     uint8_t *described_out, uint32_t *pairs_out, uint32_t *spfh_out, double *raw_out, plade_fpfh_summary *summary);
+/* The same on a resident cloud: the point data makes no host round trip, the outputs (host arrays) are the bits of plade_cloud_fpfh
+ * on the cloud's rows.  features_out (or NULL): receives a resident copy of the descriptors for plade_match_features_dev, to be
+ * released with plade_features_free. */
+int plade_cloud_fpfh_dev(plade_ctx *ctx, plade_cloud *cloud, const plade_fpfh_params *params, float *desc_out, uint8_t *described_out,
+                         uint32_t *pairs_out, uint32_t *spfh_out, double *raw_out, plade_features **features_out,
+                         plade_fpfh_summary *summary);
+void plade_features_free(plade_features *f);
+
+/* The match of two descriptor tables in feature space: src ns x 33 floats, tgt nt x 33, ns, nt >= 1.  A row is valid iff its first
+ * value is not NaN (the rows plade_cloud_fpfh gives to points that are not described are not).
+ *   distance     delta(s, t) = the sum over b = 0 .. 32, in that order, of (S_b - T_b) * (S_b - T_b), in fp32 without contraction
+ *                (numpy float32 reproduces it bit for bit).  A target whose delta is NaN is passed over.
+ *   neighbours   per valid source row the two smallest keys (delta, t) over the valid targets; ties go to the smaller index.
+ *                nn_out: ns int32, -1 where there is none; d2_out: ns x 2 floats, NaN where there is none.
+ *   mutual       with it the same search runs target -> source (back_out: nt int32) and s is kept iff back[nn[s]] == s.
+ *   max_ratio    0: off; otherwise s is kept iff it has no second neighbour or d2[s][0] < (max_ratio * max_ratio) * d2[s][1] in fp32.
+ *   output       nn_out, d2_out, back_out and corr_out may be NULL; back is computed when mutual is set or back_out is given.
+ *                corr_out: cap x 2 int32, the kept (s, nn[s]) ascending in s; *n_corr: their exact number.  PLADE_ECAP when
+ *                corr_out is given and *n_corr > cap (the first cap pairs are written).
+ * Integers and fp32 bit patterns only: the same on every run and for every launch geometry.  Errors: PLADE_EINVAL for a NULL table
+ * or n_corr, ns = 0 or nt = 0, max_ratio negative or not finite; the context stays usable.  plade_stats_get then reports
+ * feat_match_s (HIP events) and feat_corr. */
+typedef struct plade_feature_match_params {
+    int32_t mutual;              /* 1: keep s only when its neighbour's neighbour is s */
+    float max_ratio;             /* 0: off; else Lowe's ratio test on the distances (not squared) */
+} plade_feature_match_params;
+/* The defaults: mutual = 1, max_ratio = 0.  Needs no GPU. */
+void plade_feature_match_default_params(plade_feature_match_params *p);
+int plade_match_features(plade_ctx *ctx, const float *src, uint32_t ns, const float *tgt, uint32_t nt,
+                         const plade_feature_match_params *params, int32_t *nn_out, float *d2_out, int32_t *back_out, int32_t *corr_out,
+                         uint64_t cap, uint64_t *n_corr);
+/* The same on two resident tables (plade_cloud_fpfh_dev): bit-identical results. */
+int plade_match_features_dev(plade_ctx *ctx, plade_features *src, plade_features *tgt, const plade_feature_match_params *params,
+                             int32_t *nn_out, float *d2_out, int32_t *back_out, int32_t *corr_out, uint64_t cap, uint64_t *n_corr);
+
 /* ---- merging registered clouds: the step a scan-to-scan chain ends with (no reference counterpart) -----------------------------
  * Semantics (plade_amd/csrc/merge.h).  k clouds, 1 <= k <= 16; cloud c: n_c >= 1 rows x y z nx ny nz with
  * finite coordinates (the normals may be NaN); T: k row-major fp32 4 x 4 matrices, cloud c -> the output frame (NULL: identities,

@@ -35,6 +35,8 @@ ABI_SYMBOLS = [
     "plade_smooth_default_params", "plade_smooth_cloud", "plade_cloud_smooth_dev",
     "plade_gicp_default_params", "plade_refine_gicp", "plade_refine_gicp_dev", "plade_gicp_linearize",
     "plade_m3c2_default_params", "plade_cloud_m3c2", "plade_cloud_m3c2_dev",
+    "plade_fpfh_default_params", "plade_cloud_fpfh", "plade_cloud_fpfh_dev", "plade_features_free",
+    "plade_feature_match_default_params", "plade_match_features", "plade_match_features_dev",
 ]
 
 
@@ -140,6 +142,25 @@ class M3c2Summary(C.Structure):
                 ("max", C.c_double), ("max_count", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class FpfhParams(C.Structure):
+    """plade_fpfh_params: the radius of the neighbourhood (absolute, no default), min_pairs of a described point."""
+    _fields_ = [("radius", C.c_double), ("min_pairs", C.c_int32), ("reserved", C.c_int32)]
+
+
+class FpfhSummary(C.Structure):
+    """plade_fpfh_summary: n, described, mean_pairs (over the described points), max_pairs (of any point)."""
+    _fields_ = [("n", C.c_uint64), ("described", C.c_uint64), ("mean_pairs", C.c_double), ("max_pairs", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class FeatureMatchParams(C.Structure):
+    """plade_feature_match_params: mutual (0 / 1), max_ratio (0 = off)."""
+    _fields_ = [("mutual", C.c_int32), ("max_ratio", C.c_float)]
+
+
+FPFH_DIM = 33
+FEAT_CHUNK = 512     # fpfh.h: the smallest number of targets one workgroup of the match takes
+
 PLADE_OUTLIER_STATISTICAL, PLADE_OUTLIER_RADIUS = 0, 1
 OUTLIER_MODES = {"statistical": PLADE_OUTLIER_STATISTICAL, "radius": PLADE_OUTLIER_RADIUS}
 
@@ -230,6 +251,14 @@ def load_library(path=LIB_PATH):
     sig("plade_cloud_m3c2", argtypes=[p, p, u32, p, u32, u32, p, u32, u32, p, C.POINTER(M3c2Params), p, p, p, p, p, p,
                                       C.POINTER(M3c2Summary)])
     sig("plade_cloud_m3c2_dev", argtypes=[p, p, p, p, p, C.POINTER(M3c2Params), p, p, p, p, p, p, C.POINTER(M3c2Summary)])
+    sig("plade_fpfh_default_params", argtypes=[C.POINTER(FpfhParams)], restype=None)
+    sig("plade_cloud_fpfh", argtypes=[p, p, u32, C.POINTER(FpfhParams), p, p, p, p, p, C.POINTER(FpfhSummary)])
+    sig("plade_cloud_fpfh_dev", argtypes=[p, p, C.POINTER(FpfhParams), p, p, p, p, p, C.POINTER(p), C.POINTER(FpfhSummary)])
+    sig("plade_features_free", argtypes=[p], restype=None)
+    sig("plade_feature_match_default_params", argtypes=[C.POINTER(FeatureMatchParams)], restype=None)
+    sig("plade_match_features", argtypes=[p, p, u32, p, u32, C.POINTER(FeatureMatchParams), p, p, p, p, C.c_uint64,
+                                          C.POINTER(C.c_uint64)])
+    sig("plade_match_features_dev", argtypes=[p, p, p, C.POINTER(FeatureMatchParams), p, p, p, p, C.c_uint64, C.POINTER(C.c_uint64)])
     sig("plade_sort_segments", argtypes=[p, p, p, p, u32, C.c_int, p, p])
     sig("plade_set_candidate_shard", argtypes=[p, u32, u32, u32, EXCHANGE_FN, p])
     sig("plade_registration_minsupport", argtypes=[p, p, u32, p, u32, i32, i32, p])
@@ -401,6 +430,43 @@ def _m3c2_params(radius, depth, min_points, reg_error):
     return prm
 
 
+def fpfh_default_params():
+    """plade_fpfh_default_params (pure: needs no GPU) as a dict of the plade_fpfh_params fields."""
+    prm = FpfhParams()
+    load_library().plade_fpfh_default_params(C.byref(prm))
+    return {k: getattr(prm, k) for k, _ in FpfhParams._fields_ if k != "reserved"}
+
+
+def feature_match_default_params():
+    """plade_feature_match_default_params (pure: needs no GPU) as a dict."""
+    prm = FeatureMatchParams()
+    load_library().plade_feature_match_default_params(C.byref(prm))
+    return {k: getattr(prm, k) for k, _ in FeatureMatchParams._fields_}
+
+
+def _fpfh_params(radius, min_pairs):
+    prm = FpfhParams()
+    load_library().plade_fpfh_default_params(C.byref(prm))
+    prm.radius = float(radius)
+    if min_pairs is not None:
+        prm.min_pairs = int(min_pairs)
+    return prm
+
+
+def _feature_match_params(mutual, max_ratio):
+    prm = FeatureMatchParams()
+    load_library().plade_feature_match_default_params(C.byref(prm))
+    prm.mutual, prm.max_ratio = int(bool(mutual)), float(max_ratio)
+    return prm
+
+
+def _feature_table(a, what):
+    a = _f32(a)
+    if a.ndim != 2 or a.shape[1] != FPFH_DIM:
+        raise ValueError(f"{what}: an (N, 33) array of descriptors is required, got shape {a.shape}")
+    return a
+
+
 def gicp_default_params():
     """plade_gicp_default_params (pure: needs no GPU) as a dict of the plade_gicp_params fields."""
     prm = GicpParams()
@@ -539,6 +605,18 @@ class Cloud:
     def free(self):
         if self.h:
             self.ctx.L.plade_cloud_free(self.ctx.h, self.h)
+            self.h = C.c_void_p()
+
+
+class Features:
+    """Device-resident descriptor table (plade_features), made by Context.fpfh_dev(..., resident=True)."""
+
+    def __init__(self, ctx, n, handle):
+        self.ctx, self.n, self.h = ctx, n, handle
+
+    def free(self):
+        if self.h:
+            self.ctx.L.plade_features_free(self.h)
             self.h = C.c_void_p()
 
 
@@ -1168,6 +1246,70 @@ class Context:
         return self._m3c2(lambda T_in, prm, *out: self.L.plade_cloud_m3c2_dev(
             self.h, core_cloud.h, ref_cloud.h, cmp_cloud.h, T_in, prm, *out), core_cloud.n, radius, depth, T, min_points, reg_error,
             per_point, moments)
+
+    # ---- point descriptors: FPFH, and their match ------------------------------------------------------
+    def _fpfh(self, call, n, radius, min_pairs, per_point, seams):
+        prm = _fpfh_params(radius, min_pairs)
+        desc = np.empty((n, FPFH_DIM), np.float32)
+        described = np.zeros(n, np.uint8) if per_point else None
+        pairs = np.empty(n, np.uint32) if per_point else None
+        spfh = np.empty((n, FPFH_DIM), np.uint32) if seams else None
+        raw = np.empty((n, FPFH_DIM + 1), np.float64) if seams else None
+        summ = FpfhSummary()
+        self._check(call(C.byref(prm), _ptr(desc), _ptr(described), _ptr(pairs), _ptr(spfh), _ptr(raw), C.byref(summ)))
+        info = {k: getattr(summ, k) for k, _ in FpfhSummary._fields_ if k != "reserved"}
+        if per_point:
+            info.update(described_mask=described.view(np.bool_), pairs=pairs)
+        if seams:
+            info.update(spfh=spfh, raw=raw)
+        return desc, info
+
+    def fpfh(self, pos_nrm, radius, min_pairs=None, per_point=True, seams=False):
+        """plade_cloud_fpfh: the FPFH descriptors of an (N, 6) float32 cloud x y z nx ny nz over the neighbours closer than
+        `radius`.  Returns (desc, info): desc (N, 33) float32, three blocks of 11 bins that sum to 100 each, NaN rows where a
+        point has no usable normal or fewer than min_pairs (default 5) counted pairs; info: a dict with n, described,
+        mean_pairs, max_pairs and -- with per_point -- described_mask (N bools) and pairs (N uint32), with seams the (N, 33)
+        uint32 histograms spfh and the (N, 34) float64 weighted sums raw (W, then R)."""
+        a = _f32(pos_nrm)
+        self._check_cloud(a, "fpfh")
+        return self._fpfh(lambda prm, *out: self.L.plade_cloud_fpfh(self.h, _ptr(a), len(a), prm, *out), len(a), radius, min_pairs,
+                          per_point, seams)
+
+    def fpfh_dev(self, cloud, radius, min_pairs=None, per_point=True, seams=False, resident=False):
+        """plade_cloud_fpfh_dev: fpfh on a resident cloud (upload); bit-identical results.  With resident the return value is
+        (desc, info, features): a Features handle for match_features_dev (free() it)."""
+        fh = C.c_void_p()
+        out = self._fpfh(lambda prm, desc, described, pairs, spfh, raw, summ: self.L.plade_cloud_fpfh_dev(
+            self.h, cloud.h, prm, desc, described, pairs, spfh, raw, C.byref(fh) if resident else None, summ), cloud.n, radius,
+            min_pairs, per_point, seams)
+        return out + (Features(self, cloud.n, fh),) if resident else out
+
+    def _match_features(self, call, ns, nt, mutual, max_ratio, cap):
+        prm = _feature_match_params(mutual, max_ratio)
+        nn = np.empty(ns, np.int32)
+        d2 = np.empty((ns, 2), np.float32)
+        back = np.empty(nt, np.int32)
+        cap = ns if cap is None else int(cap)
+        corr = np.empty((max(cap, 1), 2), np.int32)
+        total = C.c_uint64()
+        rc = self._check(call(C.byref(prm), _ptr(nn), _ptr(d2), _ptr(back), _ptr(corr), cap, C.byref(total)), allow=(PLADE_ECAP,))
+        return corr[:min(cap, total.value)], {"n_corr": total.value, "nn": nn, "d2": d2, "back": back, "complete": rc == 0}
+
+    def match_features(self, src, tgt, mutual=True, max_ratio=0.0, cap=None):
+        """plade_match_features: nearest neighbours in feature space between two (N, 33) float32 descriptor tables (rows whose
+        first value is NaN take no part).  Returns (corr, info): corr (M, 2) int32, the kept (source, target) pairs ascending
+        in the source index -- with mutual only the pairs that are each other's nearest neighbour, with max_ratio > 0 only those
+        whose nearest distance is below max_ratio times the second nearest; info: n_corr (exact, also when cap -- the capacity
+        of corr, default len(src) -- was smaller: then complete is False), nn (Ns int32, -1: none), d2 (Ns, 2 float32 squared
+        distances of the two nearest, NaN: none), back (Nt int32, the targets' nearest sources)."""
+        s, t = _feature_table(src, "match_features"), _feature_table(tgt, "match_features")
+        return self._match_features(lambda prm, *out: self.L.plade_match_features(self.h, _ptr(s), len(s), _ptr(t), len(t), prm, *out),
+                                    len(s), len(t), mutual, max_ratio, cap)
+
+    def match_features_dev(self, src_features, tgt_features, mutual=True, max_ratio=0.0, cap=None):
+        """plade_match_features_dev: match_features on two resident tables (fpfh_dev(..., resident=True)); bit-identical results."""
+        return self._match_features(lambda prm, *out: self.L.plade_match_features_dev(self.h, src_features.h, tgt_features.h, prm, *out),
+                                    src_features.n, tgt_features.n, mutual, max_ratio, cap)
 
     # ---- merging registered clouds ---------------------------------------------------------------
     @staticmethod

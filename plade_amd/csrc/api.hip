@@ -12,6 +12,7 @@
 #include "smooth.h"
 #include "gicp.h"
 #include "m3c2.h"
+#include "fpfh.h"
 
 using namespace plade;
 
@@ -149,6 +150,7 @@ extern "C" void plade_ctx_destroy(plade_ctx *ctx) {
     if (ctx->smooth_work) plade::smooth_work_destroy(ctx->smooth_work);
     if (ctx->gicp_work) plade::gicp_work_destroy(ctx->gicp_work);
     if (ctx->m3c2_work) plade::m3c2_work_destroy(ctx->m3c2_work);
+    if (ctx->fpfh_work) plade::fpfh_work_destroy(ctx->fpfh_work);
     (void)hipStreamDestroy(ctx->stream);
     if (ctx->pf.stream) { (void)hipStreamSynchronize(ctx->pf.stream); (void)hipStreamDestroy(ctx->pf.stream); }
     delete ctx;

@@ -13,6 +13,7 @@
 
 #include <iosfwd>
 #include <string>
+#include <utility>
 #include <vector>
 
 #ifdef PLADE_USE_REAL_EIGEN_PCL
@@ -142,6 +143,27 @@ struct CloudComparison {
 bool compare_clouds(const Eigen::Matrix4f &transformation, pcl::PointCloud<pcl::PointNormal>::Ptr reference_cloud,
                     pcl::PointCloud<pcl::PointNormal>::Ptr compared_cloud, double radius, double depth, std::vector<double> &distances,
                     CloudComparison *info = nullptr, int min_points = 4, double reg_error = 0.0);
+
+/** Point descriptors (no counterpart in the reference): the fields of plade_fpfh_summary (include/plade_hip.h). */
+struct CloudDescription {
+    uint64_t n = 0, described = 0;   // points, those with a descriptor
+    double mean_pairs = 0;           // the mean number of counted neighbour pairs of a described point
+    uint32_t max_pairs = 0;          // the largest number of counted pairs of any point
+};
+/** FPFH descriptors on the GPU (plade_cloud_fpfh): `features` receives 33 floats per point of `cloud` -- three histograms of 11 bins
+ *  over the neighbours closer than `radius` (absolute, in the cloud's units), each summing to 100; 33 NaNs where the point's normal
+ *  is zero or not finite or it has fewer than min_pairs counted neighbour pairs.  false: invalid input or no GPU; a message is
+ *  printed, `features` and `info` are unchanged. */
+bool describe_cloud(pcl::PointCloud<pcl::PointNormal>::Ptr cloud, double radius, std::vector<float> &features,
+                    CloudDescription *info = nullptr, int min_pairs = 5);
+/** The match of two tables of describe_cloud in feature space on the GPU (plade_match_features): `correspondences` receives the
+ *  pairs (source point, target point), ascending in the source point, of the source points whose nearest target descriptor is
+ *  kept: with `mutual` only when that target's nearest source is the point itself, with max_ratio > 0 only when the nearest
+ *  distance is below max_ratio times the second nearest.  Points without a descriptor take no part.  false: invalid input or no
+ *  GPU; a message is printed, `correspondences` is unchanged.  The CLI prints one summary line per pair when
+ *  PLADE_FPFH_MATCH=<radius>[,<min_pairs>[,<max_ratio>]] is set. */
+bool match_features(const std::vector<float> &source_features, const std::vector<float> &target_features,
+                    std::vector<std::pair<int, int>> &correspondences, bool mutual = true, float max_ratio = 0.f);
 
 /** Merging registered clouds (no counterpart in the reference): the fields of plade_merge_summary (include/plade_hip.h). */
 struct CloudMerge {

@@ -330,6 +330,108 @@ void m3c2_line(plade_ctx *ctx, const float *T16, const float *tg, size_t n_t, co
     con_out() << b << std::endl;
 }
 
+// PLADE_FPFH_MATCH=<radius>[,<min_pairs>[,<max_ratio>]] (opt-in, absolute, in the clouds' units): both clouds of every pair -- registered
+// or not -- are described with FPFH on the GPU (plade_cloud_fpfh; min_pairs 5 when not given) and matched in feature space
+// (plade_match_features: mutual nearest neighbours, the ratio test when max_ratio is given), and one console line reports the
+// described counts, the number of correspondences and, when the pair registered, the share of them with |T s - t| < radius under the
+// final transformation (a host loop in fp64).  The pair is described as it was registered (after the target / source switch).  A
+// value that does not parse (radius not positive and finite, min_pairs not an integer >= 1, max_ratio negative or not finite,
+// anything behind them) prints one warning and does nothing; unset, nothing changes.
+struct FpfhSwitch { bool on = false; double radius = 0.0; int min_pairs = 5; float max_ratio = 0.f; };
+const FpfhSwitch &fpfh_switch() {
+    static const FpfhSwitch sw = [] {
+        FpfhSwitch v, off;
+        const char *w = getenv("PLADE_FPFH_MATCH");
+        if (!w) return off;
+        char *end = nullptr;
+        v.radius = strtod(w, &end);
+        const float rf = (float)v.radius;
+        bool ok = end != w && std::isfinite(v.radius) && rf > 0.f && std::isfinite(rf * rf) && rf * rf >= FLT_MIN;
+        if (ok && *end == ',') {
+            const char *a = end + 1;
+            const long m = strtol(a, &end, 10);
+            ok = end != a && m >= 1 && m <= INT32_MAX;
+            v.min_pairs = (int)m;
+            if (ok && *end == ',') {
+                a = end + 1;
+                const double q = strtod(a, &end);
+                ok = end != a && std::isfinite(q) && q >= 0.0 && std::isfinite((float)q * (float)q);
+                v.max_ratio = (float)q;
+            }
+        }
+        if (!ok || *end != '\0') {
+            std::cerr << "warning: PLADE_FPFH_MATCH=" << w
+                      << " is not <radius>[,<min_pairs>[,<max_ratio>]] with radius > 0, min_pairs >= 1 and max_ratio >= 0; no descriptors"
+                      << std::endl;
+            return off;
+        }
+        v.on = true;
+        return v;
+    }();
+    return sw;
+}
+// FPFH of a packed cloud (x y z nx ny nz rows): desc receives n x 33 floats.  false: a message has been printed
+bool fpfh_packed(plade_ctx *ctx, const float *rows, size_t n, double radius, int min_pairs, float *desc, plade_fpfh_summary &s) {
+    plade_fpfh_params prm;
+    plade_fpfh_default_params(&prm);
+    prm.radius = radius; prm.min_pairs = min_pairs;
+    trace("fpfh: describing");
+    const int rc = plade_cloud_fpfh(ctx, rows, (uint32_t)n, &prm, desc, nullptr, nullptr, nullptr, nullptr, &s);
+    trace("fpfh: done");
+    if (rc != PLADE_OK) {
+        con_err() << "cloud description failed: " << plade_last_error(ctx) << std::endl;
+        return false;
+    }
+    return true;
+}
+// the correspondences (source, target) of two descriptor tables.  false: a message has been printed
+bool match_packed(plade_ctx *ctx, const float *src, size_t ns, const float *tgt, size_t nt, bool mutual, float max_ratio,
+                  std::vector<int32_t> &corr) {
+    plade_feature_match_params prm;
+    plade_feature_match_default_params(&prm);
+    prm.mutual = mutual ? 1 : 0; prm.max_ratio = max_ratio;
+    std::vector<int32_t> c(2 * ns);
+    uint64_t m = 0;
+    const int rc = plade_match_features(ctx, src, (uint32_t)ns, tgt, (uint32_t)nt, &prm, nullptr, nullptr, nullptr, c.data(), ns, &m);
+    if (rc != PLADE_OK) {
+        con_err() << "feature match failed: " << plade_last_error(ctx) << std::endl;
+        return false;
+    }
+    c.resize(2 * (size_t)m);
+    corr.swap(c);
+    return true;
+}
+// T16: the final transformation of a pair that registered, or nullptr
+void fpfh_line(plade_ctx *ctx, const float *T16, const float *tg, size_t n_t, const float *sr, size_t n_s) {
+    const FpfhSwitch &sw = fpfh_switch();
+    if (!sw.on || !ctx) return;
+    std::vector<float> ft(33 * n_t), fs(33 * n_s);
+    std::vector<int32_t> corr;
+    plade_fpfh_summary st, ss;
+    if (!fpfh_packed(ctx, tg, n_t, sw.radius, sw.min_pairs, ft.data(), st) || !fpfh_packed(ctx, sr, n_s, sw.radius, sw.min_pairs, fs.data(), ss) ||
+        !match_packed(ctx, fs.data(), n_s, ft.data(), n_t, true, sw.max_ratio, corr))
+        return;
+    const size_t m = corr.size() / 2;
+    char b[320];
+    int len = snprintf(b, sizeof(b), "fpfh: %llu of %llu target and %llu of %llu source points described, %llu mutual correspondences",
+                       (unsigned long long)st.described, (unsigned long long)st.n, (unsigned long long)ss.described, (unsigned long long)ss.n,
+                       (unsigned long long)m);
+    if (T16) {
+        size_t close = 0;
+        for (size_t k = 0; k < m; ++k) {
+            const float *p = sr + 6 * (size_t)corr[2 * k], *q = tg + 6 * (size_t)corr[2 * k + 1];
+            double d2 = 0.0;
+            for (int r = 0; r < 3; ++r) {
+                const double v = (((double)T16[4 * r] * p[0] + (double)T16[4 * r + 1] * p[1]) + (double)T16[4 * r + 2] * p[2]) + (double)T16[4 * r + 3] - q[r];
+                d2 += v * v;
+            }
+            if (std::sqrt(d2) < sw.radius) ++close;
+        }
+        snprintf(b + len, sizeof(b) - (size_t)len, ", %.4f of them within the radius", m ? (double)close / (double)m : 0.0);
+    }
+    con_out() << b << std::endl;
+}
+
 // PLADE_REMOVE_OUTLIERS=<k>[,<alpha>] (opt-in, 0 / unset = off): both clouds of a pair pass the statistical outlier filter on the
 // GPU (plade_filter_outliers: k nearest neighbours, threshold mu + alpha sigma, alpha 1 when not given) after they are read and
 // before PLADE_ESTIMATE_NORMALS; one console line per cloud.  A value that does not parse (k not an integer in [1, 64], alpha
@@ -710,12 +812,14 @@ bool register_packed(Eigen::Matrix<float, 4, 4> &transformation, const float *tg
     int rc = plade_registration(ctx, tg, (uint32_t)n_t, sr, (uint32_t)n_s, T16);
     if (rc != PLADE_OK) {
         con_err() << plade_last_error(ctx) << std::endl;
+        fpfh_line(ctx, nullptr, tg, n_t, sr, n_s);
         return false;
     }
     con_out() << "done. time: " << w.str() << std::endl;
     refine_selected(ctx, T16, tg, n_t, sr, n_s);
     if (evaluate_dist() > 0.f) evaluate_line(ctx, T16, tg, n_t, sr, n_s);
     m3c2_line(ctx, T16, tg, n_t, sr, n_s);
+    fpfh_line(ctx, T16, tg, n_t, sr, n_s);
     to_matrix(T16, transformation);
     return true;
 }
@@ -877,6 +981,7 @@ void registration_group(size_t count, Eigen::Matrix<float, 4, 4> *transformation
         if (rc != PLADE_OK || status[q] != PLADE_OK) {
             const plade_ctx *pc = ctx ? (rc != PLADE_OK ? ctx : plade_pair_ctx(ctx, q)) : nullptr;
             if (pc) con_err() << plade_last_error(pc) << std::endl;
+            fpfh_line(ctx, nullptr, it.tg, it.n_t, it.sr, it.n_s);
             con_err() << "registration failed" << std::endl;
             continue;
         }
@@ -884,6 +989,7 @@ void registration_group(size_t count, Eigen::Matrix<float, 4, 4> *transformation
         refine_selected(ctx, T16 + 16 * q, it.tg, it.n_t, it.sr, it.n_s);
         if (evaluate_dist() > 0.f) evaluate_line(ctx, T16 + 16 * q, it.tg, it.n_t, it.sr, it.n_s);
         m3c2_line(ctx, T16 + 16 * q, it.tg, it.n_t, it.sr, it.n_s);
+        fpfh_line(ctx, T16 + 16 * q, it.tg, it.n_t, it.sr, it.n_s);
         to_matrix(T16 + 16 * q, transformations[it.pair]);
         if (it.switched) transformations[it.pair] = transformations[it.pair].inverse();
         if (merge_leaf() >= 0.f)
@@ -1007,6 +1113,37 @@ bool compare_clouds(const Eigen::Matrix4f &transformation, pcl::PointCloud<pcl::
         info->m = s.m; info->valid = s.valid; info->significant = s.significant;
         info->mean = s.mean; info->rms = s.rms; info->max = s.max; info->max_count = s.max_count;
     }
+    return true;
+}
+
+// point descriptors and their match: see plade.h
+bool describe_cloud(pcl::PointCloud<pcl::PointNormal>::Ptr cloud, double radius, std::vector<float> &features, CloudDescription *info,
+                    int min_pairs) {
+    plade_ctx *ctx = context();
+    if (!ctx) return false;
+    if (!cloud) { con_err() << "describe_cloud: null cloud" << std::endl; return false; }
+    std::vector<float> rows = flatten(*cloud), desc(33 * cloud->size());
+    plade_fpfh_summary s;
+    if (!fpfh_packed(ctx, rows.data(), cloud->size(), radius, min_pairs, desc.data(), s)) return false;
+    features.swap(desc);
+    if (info) { info->n = s.n; info->described = s.described; info->mean_pairs = s.mean_pairs; info->max_pairs = s.max_pairs; }
+    return true;
+}
+bool match_features(const std::vector<float> &source_features, const std::vector<float> &target_features,
+                    std::vector<std::pair<int, int>> &correspondences, bool mutual, float max_ratio) {
+    plade_ctx *ctx = context();
+    if (!ctx) return false;
+    if (source_features.size() % 33 || target_features.size() % 33) {
+        con_err() << "match_features: a table of descriptors holds 33 floats per point" << std::endl;
+        return false;
+    }
+    std::vector<int32_t> corr;
+    if (!match_packed(ctx, source_features.data(), source_features.size() / 33, target_features.data(), target_features.size() / 33, mutual,
+                      max_ratio, corr))
+        return false;
+    std::vector<std::pair<int, int>> out(corr.size() / 2);
+    for (size_t k = 0; k < out.size(); ++k) out[k] = {corr[2 * k], corr[2 * k + 1]};
+    correspondences.swap(out);
     return true;
 }
 

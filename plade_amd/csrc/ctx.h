@@ -539,6 +539,29 @@ struct StageTimer {
     }
 };
 
+// N marks on a context's stream and the spans between consecutive marks, as the cloud tools report them (their *_s statistics).
+// The events are created on first use and live as long as the owner (a tool's work struct).
+template <int N>
+struct EventSpans {
+    hipEvent_t ev[N] = {};
+    float ms[N - 1] = {};
+    ~EventSpans() { for (hipEvent_t &e : ev) if (e) (void)hipEventDestroy(e); }
+    void mark(plade_ctx *ctx, int i) {
+        if (!ev[i]) HIP_TRY(hipEventCreate(&ev[i]));
+        HIP_TRY(hipEventRecord(ev[i], ctx->stream));
+    }
+    // Measures the spans between the marks first .. last of this call (the other spans read 0), after the caller's sync().  That
+    // sync() may have waited on a flag in host memory instead of the stream: the work is done, but the runtime need not have
+    // marked the events complete yet, and hipEventElapsedTime then answers "device not ready" (seen once in ~500 calls of the
+    // merge).  So the last event is waited for first.
+    void collect(int last = N - 1, int first = 0) {
+        for (float &m : ms) m = 0.f;
+        HIP_TRY(hipEventSynchronize(ev[last]));
+        for (int i = first; i < last; ++i) HIP_TRY(hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]));
+    }
+    double seconds(int i) const { return 1e-3 * ms[i]; }   // the span from mark i to mark i + 1
+};
+
 // ---- kernels / stages implemented across the .hip files ----------------------------------
 // cloud upload: AoS N x 6 (host) -> SoA on device
 void cloud_upload(plade_ctx *ctx, const float *pos_nrm, uint32_t n, CloudDev &out);

@@ -36,12 +36,29 @@ inline GridView view_of(const TargetGrid &G, const char *who) {
     return g;
 }
 
+// the largest |coordinate| of a bounding box
+inline double amax_of(const float mn[3], const float mx[3]) {
+    double a = 0.0;
+    for (int t = 0; t < 3; ++t) a = std::max(a, std::max(std::fabs((double)mn[t]), std::fabs((double)mx[t])));
+    return a;
+}
+
 // what block_reach gives away for the fp32 cell assignment: (x - mn) * inv is off by a few ulps of the coordinates (bbmin / bbmax:
 // the bounding box of the grid's points); 1 % of a cell on top
 inline double grid_margin(const GridView &g, const float bbmin[3], const float bbmax[3]) {
-    double amax = 0.0;
-    for (int t = 0; t < 3; ++t) amax = std::max(amax, std::max(std::fabs((double)bbmin[t]), std::fabs((double)bbmax[t])));
-    return 0.01 * g.cell + 1e-6 * amax;
+    return 0.01 * g.cell + 1e-6 * amax_of(bbmin, bbmax);
+}
+
+// The cell of a search with radius r over points in the box [mn, mx]: at this cell the 27-cell block around a point holds every
+// point closer than r, exactly (the rule of DESIGN.md section 10).  A point at distance r lies less than one cell away along
+// every axis only if cell > r by more than the fp32 cell assignment can be off: (x - mn) * inv carries a few ulps of the
+// coordinates, 2^-23 max|coordinate| each -- 4e-6 max|coordinate| covers them with room to spare -- and `factor` adds a share of
+// r itself (3 %; the ICP's stage grids take 1 %, build() adds 0.1 % and may enlarge the cell, never shrink it).  The bound 1e37
+// keeps 1 / cell a normal fp32 number; it binds for k_m3c2 alone, whose radius is checked in fp64.  The other radius tools
+// require (float)r * (float)r finite, so r < 1.9e19 and 4e-6 max|coordinate| <= 1.4e33; k_distances takes the smaller of this and
+// its density cell and is exact at any cell.
+inline float radius_cell(double r, const float mn[3], const float mx[3], double factor = 1.03) {
+    return (float)std::min(factor * r + 4e-6 * amax_of(mn, mx), 1e37);
 }
 
 // The grid of a k-nearest-neighbour search over d_rows (n points, `stride` floats apart, bounding box known).  The cell: a

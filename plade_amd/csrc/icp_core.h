@@ -7,6 +7,7 @@
 // Included by those two .hip files only.  Everything sits in an unnamed namespace: each file gets kernels of its own.
 #pragma once
 #include "icp.h"
+#include "fixed_reduce.h"
 #include "grid_walk.h"
 
 namespace plade {
@@ -57,25 +58,10 @@ __device__ __forceinline__ u64 nearest_key(const GridView &g, const f3 q) {
     return best;
 }
 
-// fixed-order reduction of a lane's NM moments: butterfly across the wave (lane 0's sum), then the waves in order; the workgroup's
-// sums go to its own slot of `partial`
+// a lane's NM moments summed in the fixed order of fixed_reduce.h; the workgroup's sums go to its own slot of `partial`
 template <int NM>
 __device__ __forceinline__ void reduce_moments(const double (&m)[NM], double (&s_red)[CORR_TPB / 64][NM], double *partial) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < NM; ++k) {
-        double v = m[k];
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-        if (lane == 0) s_red[wave][k] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < NM) {
-        double v = s_red[0][threadIdx.x];
-#pragma unroll
-        for (int w = 1; w < CORR_TPB / 64; ++w) v += s_red[w][threadIdx.x];
-        partial[(size_t)blockIdx.x * NM + threadIdx.x] = v;
-    }
+    block_reduce<CORR_TPB>(m, s_red, partial, SumOp());
 }
 
 // the fp64 sums of the sample's x y z (`stride` floats apart), one partial per workgroup (the fixed order of reduce_moments)
@@ -93,18 +79,11 @@ __device__ __forceinline__ void apply_T(const double T[12], const double v[3], d
     for (int r = 0; r < 3; ++r) out[r] = ((T[4 * r] * v[0] + T[4 * r + 1] * v[1]) + T[4 * r + 2] * v[2]) + T[4 * r + 3];
 }
 
-// one wavefront: s-bar = the sum of the partials (lane l: l, l + 64, ..., then a butterfly) / n, and c_0 = T_0 s-bar
+// one wavefront: s-bar = the sum of the partials (final_reduce) / n, and c_0 = T_0 s-bar
 __global__ __launch_bounds__(64) void k_icp_mean(IcpState *st, const double *partial, uint32_t blocks, uint32_t n) {
-    const int lane = threadIdx.x;
-    double m[3] = {0.0, 0.0, 0.0};
-    for (uint32_t b = (uint32_t)lane; b < blocks; b += 64)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) m[k] += partial[(size_t)b * 3 + k];
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) m[k] += __shfl_xor(m[k], o, 64);
-    if (lane != 0) return;
+    double m[3];
+    final_reduce(partial, blocks, m, SumOp());
+    if (threadIdx.x != 0) return;
 #pragma unroll
     for (int k = 0; k < 3; ++k) st->sbar[k] = n ? m[k] / (double)n : 0.0;
     double c[3];
@@ -125,27 +104,16 @@ __device__ void rodrigues(const double w[3], double R[9]) {
     R[6] = -s * ky + c * (kz * kx);  R[7] = s * kx + c * (kz * ky);    R[8] = 1.0 + c * (kz * kz - 1.0);
 }
 
-// One wavefront sums the partials of NM moments in a fixed order (lane l: partials l, l + 64, ..., then a butterfly); lane 0 then
+// One wavefront sums the partials of NM moments in the fixed order of final_reduce; lane 0 then
 // either hands the sums out (the seam) or solves m[0..21) x = -m[21..27), updates T and c and applies the stage / convergence /
 // failure rules.  Slots: NM - 1 = the count, R2 -> sum_r2, AUX -> sum_aux (AUX < 0: none).
 template <int NM, int R2, int AUX>
 __global__ __launch_bounds__(64) void k_icp_solve(const IcpSolveArgs a) {
     IcpState *st = a.st;
     if (!a.moments && st->done) return;                // (uniform)
-    const int lane = threadIdx.x;
     double m[NM];
-#pragma unroll
-    for (int k = 0; k < NM; ++k) m[k] = 0.0;
-    for (uint32_t b = (uint32_t)lane; b < a.blocks; b += 64) {
-        const double *p = a.partial + (size_t)b * NM;
-#pragma unroll
-        for (int k = 0; k < NM; ++k) m[k] += p[k];
-    }
-#pragma unroll
-    for (int k = 0; k < NM; ++k)
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) m[k] += __shfl_xor(m[k], o, 64);
-    if (lane != 0) return;
+    final_reduce(a.partial, a.blocks, m, SumOp());
+    if (threadIdx.x != 0) return;
     if (a.moments) {
 #pragma unroll
         for (int k = 0; k < NM; ++k) a.moments[k] = m[k];
@@ -245,12 +213,6 @@ inline double diag_of(const float mn[3], const float mx[3]) {
     return std::sqrt(ex * ex + ey * ey + ez * ez);
 }
 
-inline double amax_of(const float mn[3], const float mx[3]) {
-    double a = 0.0;
-    for (int t = 0; t < 3; ++t) a = std::max(a, std::max(std::fabs((double)mn[t]), std::fabs((double)mx[t])));
-    return a;
-}
-
 // `who` opens every message ("refine_icp", "refine_gicp")
 inline void check_param(double v, const std::string &who, const char *what) {
     PLADE_REQUIRE(std::isfinite(v) && v >= 0.0, PLADE_EINVAL, who + ": " + what + " must be finite and >= 0");
@@ -290,9 +252,9 @@ inline IcpConfig resolve(const plade_icp_params *prm, const float tmn[3], const 
 // the grid of one stage distance d over the target (n_t x 6 on the device, bounding box known)
 inline IcpGridArgs stage_grid(plade_ctx *ctx, TargetGrid &G, const float *d_tgt, uint32_t n_t, const float tmn[3], const float tmx[3],
                               double d, const char *who) {
-    // cell >= d with a margin for the fp32 cell assignment: 1 % of d and a few ulps of the largest coordinate (build() adds 0.1 %
-    // and may enlarge the cell further; a larger cell only adds candidates)
-    G.build(ctx, d_tgt, n_t, 6, (float)(1.01 * d + 4e-6 * amax_of(tmn, tmx)), tmn, tmx, true);
+    // cell >= d with a margin for the fp32 cell assignment: radius_cell with 1 % of d (build() adds 0.1 % and may enlarge the
+    // cell further; a larger cell only adds candidates)
+    G.build(ctx, d_tgt, n_t, 6, radius_cell(d, tmn, tmx, 1.01), tmn, tmx, true);
     IcpGridArgs g;
     g.g = view_of(G, who);
     const float df = (float)d;

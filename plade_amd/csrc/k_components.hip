@@ -1,7 +1,7 @@
 // plade_amd/csrc/k_components.hip -- connected components of the radius graph on gfx950 (semantics: components.h).
 //
 // Layout
-//   grid     the dense row index of TargetGrid with the radius filter's cell, 1.03 r + 4e-6 max|coordinate| (the rule of DESIGN.md
+//   grid     the dense row index of TargetGrid with the radius filter's cell, radius_cell(r) of grid_walk.h (the rule of DESIGN.md
 //            section 10): the 27-cell block around a point holds everything closer than r.
 //   link     k_cc_link: one lane per point in the grid's sorted order walks the nine runs of its block and tests only the
 //            candidates at a smaller sorted position, so every undirected edge is tested once.  An edge unites the two original
@@ -15,7 +15,7 @@
 //            by its exclusive positions, the id of every root: ascending root = ascending smallest index.
 //   label    k_cc_label_size: label[i] = id[root[i]]; the sizes by integer atomics, one per distinct id of a wavefront.
 //   select   k_cc_pass; with keep_largest the keys ~size << 32 | id (all ones in the high word: does not pass) through the stable
-//            sort_pairs_u64 and k_cc_mark_first; k_cc_summary (largest, kept components); k_cc_keep, compact_flags, k_cc_gather.
+//            sort_pairs_u64 and k_cc_mark_first; k_cc_summary (largest, kept components); k_cc_keep, compact_flags, gather_rows (prims.h).
 #include "components.h"
 #include "grid_walk.h"
 #include "prims.h"
@@ -157,15 +157,6 @@ __global__ __launch_bounds__(ROW_TPB) void k_cc_keep(const int32_t *__restrict__
     flags[i] = k;
 }
 
-// out row o = in row kept[o], word by word (the gather of k_outliers.hip: whatever the floats hold keeps its bits)
-__global__ __launch_bounds__(ROW_TPB) void k_cc_gather(const uint32_t *__restrict__ in, uint32_t stride, const uint32_t *__restrict__ kept,
-                                                       uint32_t total, uint32_t *__restrict__ out) {
-    const size_t w = (size_t)blockIdx.x * ROW_TPB + threadIdx.x;
-    if (w >= (size_t)total * stride) return;
-    const uint32_t o = (uint32_t)(w / stride), c = (uint32_t)(w - (size_t)o * stride);
-    out[w] = in[(size_t)kept[o] * stride + c];
-}
-
 }  // namespace
 
 struct ComponentWork {
@@ -175,10 +166,9 @@ struct ComponentWork {
     DBuf<int32_t> label;
     DBuf<uint8_t> keep, comp_kept;
     DBuf<float> in, out;             // the host-pointer entry point's device copies (grow-only)
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    EventSpans<5> spans;             // grid, link, label, compact
     uint32_t h_count[2] = {0, 0};    // the largest size, the kept components
     uint32_t components = 0;
-    ~ComponentWork() { for (hipEvent_t &e : ev) if (e) (void)hipEventDestroy(e); }
 };
 ComponentWork *component_work_create() { return new ComponentWork; }
 void component_work_destroy(ComponentWork *w) { delete w; }
@@ -202,14 +192,11 @@ void check_params(uint32_t n, uint32_t stride, const plade_component_params &p) 
 uint32_t components_dev(plade_ctx *ctx, ComponentWork &W, const float *d_rows, uint32_t n, uint32_t stride, const float bbmin[3],
                         const float bbmax[3], const plade_component_params &p, const std::function<float *(uint32_t)> &dst,
                         plade_component_summary *summary) {
-    for (hipEvent_t &e : W.ev) if (!e) HIP_TRY(hipEventCreate(&e));
-    HIP_TRY(hipEventRecord(W.ev[0], ctx->stream));
+    W.spans.mark(ctx, 0);
     TargetGrid &G = W.grid;
     const float r = (float)p.radius;
-    double amax = 0.0;
-    for (int t = 0; t < 3; ++t) amax = std::max(amax, std::max(std::fabs((double)bbmin[t]), std::fabs((double)bbmax[t])));
-    G.build(ctx, d_rows, n, stride, (float)(1.03 * (double)r + 4e-6 * amax), bbmin, bbmax, true);
-    HIP_TRY(hipEventRecord(W.ev[1], ctx->stream));
+    G.build(ctx, d_rows, n, stride, radius_cell((double)r, bbmin, bbmax), bbmin, bbmax, true);
+    W.spans.mark(ctx, 1);
 
     LinkArgs a;
     memset(&a, 0, sizeof(a));
@@ -219,7 +206,7 @@ uint32_t components_dev(plade_ctx *ctx, ComponentWork &W, const float *d_rows, u
     hipLaunchKernelGGL(k_cc_init, dim3(cdiv(n, ROW_TPB)), dim3(ROW_TPB), 0, ctx->stream, a.parent, n);
     hipLaunchKernelGGL(k_cc_link, dim3(cdiv(n, LINK_TPB)), dim3(LINK_TPB), 0, ctx->stream, a);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(W.ev[2], ctx->stream));
+    W.spans.mark(ctx, 2);
 
     uint32_t *d_root = W.root.ensure(n), *d_flags = W.flags.ensure((size_t)n + 1), *d_size = W.size.ensure(n), *d_cnt = W.count.ensure(4);
     int32_t *d_label = W.label.ensure(n);
@@ -248,17 +235,11 @@ uint32_t components_dev(plade_ctx *ctx, ComponentWork &W, const float *d_rows, u
     hipLaunchKernelGGL(k_cc_keep, dim3(cdiv(n, ROW_TPB)), dim3(ROW_TPB), 0, ctx->stream, d_label, d_ckept, n, d_keep, d_flags);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(W.h_count, d_cnt, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipEventRecord(W.ev[3], ctx->stream));
+    W.spans.mark(ctx, 3);
 
     const uint32_t total = compact_flags(ctx, d_flags, n, W.pos, W.kept);   // (waits for the count)
-    if (total) {
-        float *d_out = dst(total);
-        const size_t words = (size_t)total * stride;
-        hipLaunchKernelGGL(k_cc_gather, dim3(cdiv(words, ROW_TPB)), dim3(ROW_TPB), 0, ctx->stream, reinterpret_cast<const uint32_t *>(d_rows),
-                           stride, W.kept.p, total, reinterpret_cast<uint32_t *>(d_out));
-        HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipEventRecord(W.ev[4], ctx->stream));
+    if (total) gather_rows(ctx, d_rows, stride, W.kept.p, total, dst(total));
+    W.spans.mark(ctx, 4);
     ctx->sync();
     if (summary) {
         summary->n = n;
@@ -268,13 +249,12 @@ uint32_t components_dev(plade_ctx *ctx, ComponentWork &W, const float *d_rows, u
         summary->largest = W.h_count[0];
         summary->reserved = 0;
     }
-    float ms[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int k = 0; k < 4; ++k) HIP_TRY(hipEventElapsedTime(&ms[k], W.ev[k], W.ev[k + 1]));
+    W.spans.collect();
     ctx->stats.clear();
-    ctx->stats.add("components_grid_s", 1e-3 * ms[0]);
-    ctx->stats.add("components_link_s", 1e-3 * ms[1]);
-    ctx->stats.add("components_label_s", 1e-3 * ms[2]);
-    ctx->stats.add("components_compact_s", 1e-3 * ms[3]);
+    ctx->stats.add("components_grid_s", W.spans.seconds(0));
+    ctx->stats.add("components_link_s", W.spans.seconds(1));
+    ctx->stats.add("components_label_s", W.spans.seconds(2));
+    ctx->stats.add("components_compact_s", W.spans.seconds(3));
     ctx->stats.add("components_count", C);
     ctx->stats.add("components_kept", total);
     return total;

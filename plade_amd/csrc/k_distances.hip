@@ -15,10 +15,10 @@
 //   ring    k_distances_ring: one wavefront per listed probe grows the block as k_normals_ring does (ring_step); the 64 keys of a
 //           batch are reduced by a wave min.  It stops at the first block whose outside is at least min(best, d) away, or that
 //           covers the grid.
-//   summary k_distances_summary: one lane per original index forms the plane residual in fp64 and the six summary terms; a
-//           butterfly per wave, the waves in order, one partial per workgroup.  k_distances_final sums the partials with one
-//           wavefront in a fixed order (lane l: partials l, l + 64, ..., then a butterfly).  No fp64 atomics.
+//   summary k_distances_summary: one lane per original index forms the plane residual in fp64 and the six summary terms, reduced
+//           per workgroup and then by k_distances_final in the fixed order of fixed_reduce.h.  No fp64 atomics.
 #include "distances.h"
+#include "fixed_reduce.h"
 #include "grid_walk.h"
 #include "prims.h"
 #include "voxel.h"
@@ -152,6 +152,10 @@ struct SumArgs {
     double *partial;                 // gridDim.x x SUM_TERMS
 };
 
+struct SumMax3 {                     // term 3 is a maximum, the others are sums
+    __device__ __forceinline__ double operator()(int k, double a, double b) const { return k == 3 ? fmax(a, b) : a + b; }
+};
+
 __global__ __launch_bounds__(SUM_TPB) void k_distances_summary(const SumArgs a) {
     __shared__ double s_red[SUM_TPB / 64][SUM_TERMS];
     const uint32_t i = blockIdx.x * SUM_TPB + threadIdx.x;
@@ -177,38 +181,13 @@ __global__ __launch_bounds__(SUM_TPB) void k_distances_summary(const SumArgs a) 
         }
         if (a.plane) a.plane[i] = (float)r;
     }
-    // fixed-order reduction: butterfly across the wave (lane 0's value), then the waves in order
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < SUM_TERMS; ++k) {
-        double v = m[k];
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) { const double w = __shfl_xor(v, o, 64); v = k == 3 ? fmax(v, w) : v + w; }
-        if (lane == 0) s_red[wave][k] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < SUM_TERMS) {
-        const int k = threadIdx.x;
-        double v = s_red[0][k];
-#pragma unroll
-        for (int w = 1; w < SUM_TPB / 64; ++w) v = k == 3 ? fmax(v, s_red[w][k]) : v + s_red[w][k];
-        a.partial[(size_t)blockIdx.x * SUM_TERMS + k] = v;
-    }
+    block_reduce<SUM_TPB>(m, s_red, a.partial, SumMax3());
 }
 
 __global__ __launch_bounds__(64) void k_distances_final(const double *__restrict__ partial, uint32_t blocks, double *__restrict__ out) {
-    const int lane = threadIdx.x;
-    double m[SUM_TERMS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    for (uint32_t b = (uint32_t)lane; b < blocks; b += 64) {
-        const double *p = partial + (size_t)b * SUM_TERMS;
-#pragma unroll
-        for (int k = 0; k < SUM_TERMS; ++k) m[k] = k == 3 ? fmax(m[k], p[k]) : m[k] + p[k];
-    }
-#pragma unroll
-    for (int k = 0; k < SUM_TERMS; ++k)
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) { const double w = __shfl_xor(m[k], o, 64); m[k] = k == 3 ? fmax(m[k], w) : m[k] + w; }
-    if (lane == 0)
+    double m[SUM_TERMS];
+    final_reduce(partial, blocks, m, SumMax3());
+    if (threadIdx.x == 0)
 #pragma unroll
         for (int k = 0; k < SUM_TERMS; ++k) out[k] = m[k];
 }
@@ -223,11 +202,10 @@ struct DistWork {
     DBuf<int32_t> idx;
     DBuf<float> dd, plane;
     DBuf<double> partial, out;
-    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    EventSpans<6> spans;             // grid, sort, lane, ring, summary
     float h_T[16];                   // the upload's source (kept until the call's sync)
     double h_out[SUM_TERMS];
     uint32_t h_count = 0;
-    ~DistWork() { for (hipEvent_t &e : ev) if (e) (void)hipEventDestroy(e); }
 };
 DistWork *dist_work_create() { return new DistWork; }
 void dist_work_destroy(DistWork *w) { delete w; }
@@ -245,19 +223,16 @@ void check_args(const float *T16, float max_dist) {
 void distances_dev(plade_ctx *ctx, DistWork &W, const float *d_tgt, uint32_t n_t, const float tmn[3], const float tmx[3],
                    const float *d_src, uint32_t n_s, uint32_t stride, const float *T16, float max_dist, int32_t *idx_out,
                    float *d2_out, float *plane_out, plade_distance_summary *summary) {
-    for (hipEvent_t &e : W.ev) if (!e) HIP_TRY(hipEventCreate(&e));
-    HIP_TRY(hipEventRecord(W.ev[0], ctx->stream));
+    W.spans.mark(ctx, 0);
     // cell: ~5 points per occupied cell of a surface spread over the faces of the target's box (k_normals' estimate at k = 8); a
-    // d of less than that takes d plus a margin (3 % and ulps of the coordinates), so one 27-cell block holds every point within d
+    // d of less than that takes the radius cell of d (radius_cell), so one 27-cell block holds every point within d
     const double ex = std::max(1e-9, (double)tmx[0] - tmn[0]), ey = std::max(1e-9, (double)tmx[1] - tmn[1]),
                  ez = std::max(1e-9, (double)tmx[2] - tmn[2]);
     const double area = 2 * (ex * ey + ey * ez + ex * ez);
-    double amax = 0.0;
-    for (int t = 0; t < 3; ++t) amax = std::max(amax, std::max(std::fabs((double)tmn[t]), std::fabs((double)tmx[t])));
-    const double dense_cell = 1.5 * std::sqrt(8.0 * area / (M_PI * (double)n_t)), d_cell = 1.03 * (double)max_dist + 4e-6 * amax;
+    const double dense_cell = 1.5 * std::sqrt(8.0 * area / (M_PI * (double)n_t));
     TargetGrid &G = W.grid;
-    G.build(ctx, d_tgt, n_t, 6, (float)std::min(dense_cell, d_cell), tmn, tmx, true);
-    HIP_TRY(hipEventRecord(W.ev[1], ctx->stream));
+    G.build(ctx, d_tgt, n_t, 6, std::min((float)dense_cell, radius_cell((double)max_dist, tmn, tmx)), tmn, tmx, true);
+    W.spans.mark(ctx, 1);
 
     DistArgs a;
     memset(&a, 0, sizeof(a));
@@ -280,12 +255,12 @@ void distances_dev(plade_ctx *ctx, DistWork &W, const float *d_tgt, uint32_t n_t
     sort_pairs_u32(ctx, W.keys.p, W.keys2.p, W.vals.p, W.vals2.p, n_s, bits);
     a.order = W.vals2.p;
     ctx->fill_async(a.fail_count, 0, 4);
-    HIP_TRY(hipEventRecord(W.ev[2], ctx->stream));
+    W.spans.mark(ctx, 2);
     hipLaunchKernelGGL(k_distances_lane, dim3(cdiv(n_s, LANE_TPB)), dim3(LANE_TPB), 0, ctx->stream, a);
-    HIP_TRY(hipEventRecord(W.ev[3], ctx->stream));
+    W.spans.mark(ctx, 3);
     hipLaunchKernelGGL(k_distances_ring, dim3(std::min(cdiv(n_s, RING_WAVES), 2048u)), dim3(64 * RING_WAVES), 0, ctx->stream, a);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(W.ev[4], ctx->stream));
+    W.spans.mark(ctx, 4);
 
     SumArgs sa;
     memset(&sa, 0, sizeof(sa));
@@ -298,7 +273,7 @@ void distances_dev(plade_ctx *ctx, DistWork &W, const float *d_tgt, uint32_t n_t
     hipLaunchKernelGGL(k_distances_summary, dim3(blocks), dim3(SUM_TPB), 0, ctx->stream, sa);
     hipLaunchKernelGGL(k_distances_final, dim3(1), dim3(64), 0, ctx->stream, sa.partial, blocks, d_out);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(W.ev[5], ctx->stream));
+    W.spans.mark(ctx, 5);
     HIP_TRY(hipMemcpyAsync(W.h_out, d_out, sizeof(W.h_out), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipMemcpyAsync(&W.h_count, a.fail_count, 4, hipMemcpyDeviceToHost, ctx->stream));
     if (idx_out) HIP_TRY(hipMemcpyAsync(idx_out, a.idx, (size_t)n_s * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -319,15 +294,14 @@ void distances_dev(plade_ctx *ctx, DistWork &W, const float *d_tgt, uint32_t n_t
     r.plane_rmse = r.plane_count ? std::sqrt(o[5] / (double)r.plane_count) : NAN;
     *summary = r;
 
-    float ms[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-    for (int k = 0; k < 5; ++k) HIP_TRY(hipEventElapsedTime(&ms[k], W.ev[k], W.ev[k + 1]));
+    W.spans.collect();
     ctx->stats.clear();
-    ctx->stats.add("distances_grid_s", 1e-3 * ms[0]);
-    ctx->stats.add("distances_sort_s", 1e-3 * ms[1]);
-    ctx->stats.add("distances_search_s", 1e-3 * (ms[2] + ms[3]));
-    ctx->stats.add("distances_lane_s", 1e-3 * ms[2]);
-    ctx->stats.add("distances_ring_s", 1e-3 * ms[3]);
-    ctx->stats.add("distances_summary_s", 1e-3 * ms[4]);
+    ctx->stats.add("distances_grid_s", W.spans.seconds(0));
+    ctx->stats.add("distances_sort_s", W.spans.seconds(1));
+    ctx->stats.add("distances_search_s", W.spans.seconds(2) + W.spans.seconds(3));
+    ctx->stats.add("distances_lane_s", W.spans.seconds(2));
+    ctx->stats.add("distances_ring_s", W.spans.seconds(3));
+    ctx->stats.add("distances_summary_s", W.spans.seconds(4));
     ctx->stats.add("distances_ring_queries", W.h_count);
 }
 

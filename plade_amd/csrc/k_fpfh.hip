@@ -1,7 +1,7 @@
 // plade_amd/csrc/k_fpfh.hip -- FPFH descriptors and their feature-space match on gfx950 (semantics: fpfh.h).
 //
 // Layout
-//   grid     the dense row index of TargetGrid, built exactly as k_smooth.hip builds it (cell 1.03 r + 4e-6 max|coordinate|), so the
+//   grid     the dense row index of TargetGrid, built exactly as k_smooth.hip builds it (cell radius_cell(r) of grid_walk.h), so the
 //            27-cell block around a point holds everything closer than r.
 //   axes     k_fpfh_axes: the fp32 normals gathered into grid order with a has-axis flag in w, so that a walk reads its neighbours'
 //            normals from the run it is reading the positions from (not by original index).  They are widened and normalised per
@@ -15,13 +15,14 @@
 //            once per point, not once per pair; the bits are the same.
 //   weight   k_fpfh_weight: the second walk, 34 fp64 accumulators per lane in registers (statically indexed: every bin of every
 //            neighbour is added, the bin loop is unrolled), rows of 34 doubles read as 17 double2; normalises, stores by original index.
-//   summary  k_fpfh_sum / k_fpfh_final, the pattern of k_smooth_sum / k_smooth_final on integers (exact, whatever the order).
+//   summary  k_fpfh_sum / k_fpfh_final, the fixed order of fixed_reduce.h on integers (exact, whatever the order).
 //   match    k_feat_match, the pattern of k_match.hip in fp32: one lane owns one query (33 floats in VGPRs), target tiles are staged
 //            through LDS (rows padded to 36 floats) and read as wave-wide broadcasts, the two best keys (delta, t) of a lane live in
 //            registers (insert<2> of grid_walk.h); the targets are split over blockIdx.y, two keys per (query, chunk);
 //            k_feat_merge takes the two smallest over the chunks (a minimum: order-independent, exact); k_feat_keep applies the
 //            mutual and ratio tests, the scan of prims.h places the kept pairs, k_feat_compact writes them.
 #include "fpfh.h"
+#include "fixed_reduce.h"
 #include "grid_walk.h"
 #include "prims.h"
 #include "voxel.h"
@@ -213,44 +214,27 @@ __global__ __launch_bounds__(WEIGHT_TPB) void k_fpfh_weight(const WeightArgs a) 
 }
 
 // per workgroup: pu[3 b] = its described points, pu[3 b + 1] = the sum of their c, pu[3 b + 2] = the largest c of any of its points
+// (the order: fixed_reduce.h; terms 0 and 1 are sums, term 2 a maximum)
+struct SumMaxU64 {
+    __device__ __forceinline__ u64 operator()(int k, u64 a, u64 b) const { return k == 2 ? (b > a ? b : a) : a + b; }
+};
+
 __global__ __launch_bounds__(SUM_TPB) void k_fpfh_sum(const uint8_t *__restrict__ described, const uint32_t *__restrict__ pairs, uint32_t n,
                                                       u64 *__restrict__ pu) {
-    __shared__ u64 s_f[SUM_TPB / 64], s_c[SUM_TPB / 64], s_m[SUM_TPB / 64];
+    __shared__ u64 s_red[SUM_TPB / 64][3];
     const uint32_t i = blockIdx.x * SUM_TPB + threadIdx.x;
-    u64 f = 0, sc = 0, mx = 0;
+    u64 v[3] = {0, 0, 0};            // described, its c, c
     if (i < n) {
-        mx = pairs[i];
-        if (described[i]) { f = 1; sc = mx; }
+        v[2] = pairs[i];
+        if (described[i]) { v[0] = 1; v[1] = v[2]; }
     }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        f += __shfl_xor(f, o, 64);
-        sc += __shfl_xor(sc, o, 64);
-        const u64 m = __shfl_xor(mx, o, 64);
-        mx = m > mx ? m : mx;
-    }
-    if ((threadIdx.x & 63) == 0) { s_f[threadIdx.x >> 6] = f; s_c[threadIdx.x >> 6] = sc; s_m[threadIdx.x >> 6] = mx; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        u64 tf = s_f[0], tc = s_c[0], tm = s_m[0];
-#pragma unroll
-        for (int w = 1; w < SUM_TPB / 64; ++w) { tf += s_f[w]; tc += s_c[w]; tm = s_m[w] > tm ? s_m[w] : tm; }
-        pu[3 * blockIdx.x] = tf; pu[3 * blockIdx.x + 1] = tc; pu[3 * blockIdx.x + 2] = tm;
-    }
+    block_reduce<SUM_TPB>(v, s_red, pu, SumMaxU64());
 }
 __global__ __launch_bounds__(64) void k_fpfh_final(const u64 *__restrict__ pu, uint32_t blocks, u64 *__restrict__ ru) {
-    const int lane = threadIdx.x;
-    u64 f = 0, sc = 0, mx = 0;
-    for (uint32_t b = (uint32_t)lane; b < blocks; b += 64) { f += pu[3 * b]; sc += pu[3 * b + 1]; mx = pu[3 * b + 2] > mx ? pu[3 * b + 2] : mx; }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        f += __shfl_xor(f, o, 64);
-        sc += __shfl_xor(sc, o, 64);
-        const u64 m = __shfl_xor(mx, o, 64);
-        mx = m > mx ? m : mx;
-    }
-    if (lane != 0) return;
-    ru[0] = f; ru[1] = sc; ru[2] = mx;
+    u64 v[3];
+    final_reduce(pu, blocks, v, SumMaxU64());
+    if (threadIdx.x != 0) return;
+    ru[0] = v[0]; ru[1] = v[1]; ru[2] = v[2];
 }
 
 // ---- the match ---------------------------------------------------------------------------------------------------------------------
@@ -346,8 +330,7 @@ struct FpfhWork {
     DBuf<u64> part;
     DBuf<int32_t> nn, back, corr;
     DBuf<uint32_t> flags, offs;
-    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    ~FpfhWork() { for (hipEvent_t &e : ev) if (e) (void)hipEventDestroy(e); }
+    EventSpans<6> spans;             // 0..3: grid, spfh, weight; 4..5: the match
 };
 FpfhWork *fpfh_work_create() { return new FpfhWork; }
 void fpfh_work_destroy(FpfhWork *w) { delete w; }
@@ -373,18 +356,15 @@ void check_params(uint32_t n, const plade_fpfh_params &p) {
 // pairs, spfh (and raw when wanted) in W, copies the wanted ones out, waits, fills the summary and the stats.
 void fpfh_dev(plade_ctx *ctx, FpfhWork &W, const float *d_rows, uint32_t n, uint32_t stride, const float bbmin[3], const float bbmax[3],
               const plade_fpfh_params &p, const Outputs &out, plade_fpfh_summary *summary) {
-    for (hipEvent_t &e : W.ev) if (!e) HIP_TRY(hipEventCreate(&e));
-    HIP_TRY(hipEventRecord(W.ev[0], ctx->stream));
+    W.spans.mark(ctx, 0);
     TargetGrid &G = W.grid;
     const float r = (float)p.radius;
-    double amax = 0.0;
-    for (int t = 0; t < 3; ++t) amax = std::max(amax, std::max(std::fabs((double)bbmin[t]), std::fabs((double)bbmax[t])));
-    G.build(ctx, d_rows, n, stride, (float)(1.03 * (double)r + 4e-6 * amax), bbmin, bbmax, true);
+    G.build(ctx, d_rows, n, stride, radius_cell((double)r, bbmin, bbmax), bbmin, bbmax, true);
     const GridView g = view_of(G, "cloud_fpfh");
     float4 *d_axes = W.axes.ensure(n);
     hipLaunchKernelGGL(k_fpfh_axes, dim3(cdiv(n, 256)), dim3(256), 0, ctx->stream, g.sorted, d_rows, stride, n, d_axes);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(W.ev[1], ctx->stream));
+    W.spans.mark(ctx, 1);
     SpfhArgs a;
     memset(&a, 0, sizeof(a));
     a.g = g; a.axes = d_axes; a.n = n; a.r2 = r * r; a.min_pairs = (uint32_t)p.min_pairs;
@@ -395,7 +375,7 @@ void fpfh_dev(plade_ctx *ctx, FpfhWork &W, const float *d_rows, uint32_t n, uint
     a.hn = W.hn.ensure((size_t)n * HN_STRIDE);
     hipLaunchKernelGGL(k_fpfh_spfh, dim3(cdiv(n, SPFH_TPB)), dim3(SPFH_TPB), 0, ctx->stream, a);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(W.ev[2], ctx->stream));
+    W.spans.mark(ctx, 2);
     WeightArgs w;
     memset(&w, 0, sizeof(w));
     w.g = g; w.n = n; w.r2 = a.r2; w.min_pairs = a.min_pairs;
@@ -404,7 +384,7 @@ void fpfh_dev(plade_ctx *ctx, FpfhWork &W, const float *d_rows, uint32_t n, uint
     w.raw = out.raw ? W.raw.ensure((size_t)n * (FPFH_DIM + 1)) : nullptr;
     hipLaunchKernelGGL(k_fpfh_weight, dim3(cdiv(n, WEIGHT_TPB)), dim3(WEIGHT_TPB), 0, ctx->stream, w);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(W.ev[3], ctx->stream));
+    W.spans.mark(ctx, 3);
     const uint32_t blocks = cdiv(n, SUM_TPB);
     u64 *d_pu = W.partial.ensure((size_t)3 * blocks), *d_ru = W.res.ensure(4);
     hipLaunchKernelGGL(k_fpfh_sum, dim3(blocks), dim3(SUM_TPB), 0, ctx->stream, a.described, a.pairs, n, d_pu);
@@ -422,12 +402,11 @@ void fpfh_dev(plade_ctx *ctx, FpfhWork &W, const float *d_rows, uint32_t n, uint
     summary->mean_pairs = W.h_u[0] ? (double)W.h_u[1] / (double)W.h_u[0] : 0.0;
     summary->max_pairs = (uint32_t)W.h_u[2];
     summary->reserved = 0;
-    float ms[3] = {0.f, 0.f, 0.f};
-    for (int k = 0; k < 3; ++k) HIP_TRY(hipEventElapsedTime(&ms[k], W.ev[k], W.ev[k + 1]));
+    W.spans.collect(3);
     ctx->stats.clear();
-    ctx->stats.add("fpfh_grid_s", 1e-3 * ms[0]);
-    ctx->stats.add("fpfh_spfh_s", 1e-3 * ms[1]);
-    ctx->stats.add("fpfh_weight_s", 1e-3 * ms[2]);
+    ctx->stats.add("fpfh_grid_s", W.spans.seconds(0));
+    ctx->stats.add("fpfh_spfh_s", W.spans.seconds(1));
+    ctx->stats.add("fpfh_weight_s", W.spans.seconds(2));
     ctx->stats.add("fpfh_described", (double)W.h_u[0]);
 }
 
@@ -447,8 +426,7 @@ void feat_search(plade_ctx *ctx, FpfhWork &W, const float *d_q, uint32_t nq, con
 int match_dev(plade_ctx *ctx, FpfhWork &W, const float *d_src, uint32_t ns, const float *d_tgt, uint32_t nt,
               const plade_feature_match_params &p, int32_t *nn_out, float *d2_out, int32_t *back_out, int32_t *corr_out, uint64_t cap,
               uint64_t *n_corr) {
-    for (hipEvent_t &e : W.ev) if (!e) HIP_TRY(hipEventCreate(&e));
-    HIP_TRY(hipEventRecord(W.ev[4], ctx->stream));
+    W.spans.mark(ctx, 4);
     int32_t *d_nn = W.nn.ensure(ns), *d_back = nullptr;
     float *d_d2 = W.d2.ensure((size_t)ns * 2);
     feat_search(ctx, W, d_src, ns, d_tgt, nt, d_nn, d_d2);
@@ -464,7 +442,7 @@ int match_dev(plade_ctx *ctx, FpfhWork &W, const float *d_src, uint32_t ns, cons
     int32_t *d_corr = W.corr.ensure((size_t)ns * 2);
     hipLaunchKernelGGL(k_feat_compact, dim3(cdiv(ns, 256)), dim3(256), 0, ctx->stream, d_flags, d_offs, d_nn, ns, d_corr);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(W.ev[5], ctx->stream));
+    W.spans.mark(ctx, 5);
     uint32_t total = 0;
     HIP_TRY(hipMemcpyAsync(&total, d_offs + ns, 4, hipMemcpyDeviceToHost, ctx->stream));
     if (nn_out) HIP_TRY(hipMemcpyAsync(nn_out, d_nn, (size_t)ns * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -477,10 +455,9 @@ int match_dev(plade_ctx *ctx, FpfhWork &W, const float *d_src, uint32_t ns, cons
         HIP_TRY(hipMemcpyAsync(corr_out, d_corr, (size_t)w * 8, hipMemcpyDeviceToHost, ctx->stream));
         ctx->sync();
     }
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, W.ev[4], W.ev[5]));
+    W.spans.collect(5, 4);
     ctx->stats.clear();
-    ctx->stats.add("feat_match_s", 1e-3 * ms);
+    ctx->stats.add("feat_match_s", W.spans.seconds(4));
     ctx->stats.add("feat_corr", (double)total);
     return (corr_out && total > cap) ? PLADE_ECAP : PLADE_OK;
 }

@@ -125,9 +125,8 @@ struct GicpWork {
     DBuf<double> partial, out;
     DBuf<IcpState> st;
     DBuf<int32_t> corr;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    EventSpans<4> spans;        // sample, grid, loop
     IcpState h_init, h_st;      // the upload's source and the read-back's destination (never the same memory in flight)
-    ~GicpWork() { for (hipEvent_t &e : ev) if (e) (void)hipEventDestroy(e); }
 };
 GicpWork *gicp_work_create() { return new GicpWork; }
 void gicp_work_destroy(GicpWork *w) { delete w; }
@@ -153,16 +152,15 @@ int refine_dev(plade_ctx *ctx, GicpWork &W, const float *d_tgt, uint32_t n_t, co
     const double eps = resolve_epsilon(gp.epsilon, "refine_gicp");
     float T_in[16];
     memcpy(T_in, T_in16, sizeof(T_in));
-    for (hipEvent_t &e : W.ev) if (!e) HIP_TRY(hipEventCreate(&e));
-    HIP_TRY(hipEventRecord(W.ev[0], ctx->stream));
+    W.spans.mark(ctx, 0);
     // sample: the voxel fuse of the source with its normals (waits for its size)
     const float *d_sample = nullptr;
     const uint32_t n = merge_fuse_one(ctx, d_src, n_s, (float)c.leaf, &d_sample, "refine_gicp");
-    HIP_TRY(hipEventRecord(W.ev[1], ctx->stream));
+    W.spans.mark(ctx, 1);
     GicpArgs a;
     memset(&a, 0, sizeof(a));
     for (int s = 0; s < c.n_stages; ++s) a.g[s] = stage_grid(ctx, W.grids[s], d_tgt, n_t, tmn, tmx, c.dist[s], "refine_gicp");
-    HIP_TRY(hipEventRecord(W.ev[2], ctx->stream));
+    W.spans.mark(ctx, 2);
     const uint32_t blocks = std::max(1u, cdiv(n, CORR_TPB));
     a.tgt = d_tgt; a.src = d_sample; a.n = n; a.k = 1.0 - eps;
     a.st = W.st.ensure(1);
@@ -182,7 +180,7 @@ int refine_dev(plade_ctx *ctx, GicpWork &W, const float *d_tgt, uint32_t n_t, co
         hipLaunchKernelGGL(k_gicp_solve, dim3(1), dim3(64), 0, ctx->stream, sa);
     }
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(W.ev[3], ctx->stream));
+    W.spans.mark(ctx, 3);
     HIP_TRY(hipMemcpyAsync(&W.h_st, W.st.p, sizeof(IcpState), hipMemcpyDeviceToHost, ctx->stream));
     ctx->sync();
     const IcpState &s = W.h_st;
@@ -199,12 +197,11 @@ int refine_dev(plade_ctx *ctx, GicpWork &W, const float *d_tgt, uint32_t n_t, co
     r.final_dist = c.dist[s.lin_stage];
     r.cost = s.count ? s.sum_aux / (double)s.count : 0.0;
     if (res) *res = r;
-    float ms[3] = {0.f, 0.f, 0.f};
-    for (int k = 0; k < 3; ++k) HIP_TRY(hipEventElapsedTime(&ms[k], W.ev[k], W.ev[k + 1]));
+    W.spans.collect();
     ctx->stats.clear();
-    ctx->stats.add("gicp_sample_s", 1e-3 * ms[0]);
-    ctx->stats.add("gicp_grid_s", 1e-3 * ms[1]);
-    ctx->stats.add("gicp_loop_s", 1e-3 * ms[2]);
+    ctx->stats.add("gicp_sample_s", W.spans.seconds(0));
+    ctx->stats.add("gicp_grid_s", W.spans.seconds(1));
+    ctx->stats.add("gicp_loop_s", W.spans.seconds(2));
     ctx->stats.add("gicp_iterations", s.iter);
     ctx->stats.add("gicp_stages", c.n_stages);
     if (s.failure) {

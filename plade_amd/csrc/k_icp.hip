@@ -90,9 +90,8 @@ struct IcpWork {
     DBuf<double> partial, out;
     DBuf<IcpState> st;
     DBuf<int32_t> corr;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    EventSpans<4> spans;        // sample, grid, loop
     IcpState h_init, h_st;      // the upload's source and the read-back's destination (never the same memory in flight)
-    ~IcpWork() { for (hipEvent_t &e : ev) if (e) (void)hipEventDestroy(e); }
 };
 IcpWork *icp_work_create() { return new IcpWork; }
 void icp_work_destroy(IcpWork *w) { delete w; }
@@ -106,15 +105,14 @@ int refine_dev(plade_ctx *ctx, IcpWork &W, const float *d_tgt, uint32_t n_t, con
     const IcpConfig c = resolve(prm, tmn, tmx, "refine_icp");
     float T_in[16];
     memcpy(T_in, T_in16, sizeof(T_in));
-    for (hipEvent_t &e : W.ev) if (!e) HIP_TRY(hipEventCreate(&e));
-    HIP_TRY(hipEventRecord(W.ev[0], ctx->stream));
+    W.spans.mark(ctx, 0);
     // sample: VoxelGrid of the source (waits for its size)
     const uint32_t n = W.vox.run(ctx, d_src, s_stride, nullptr, nullptr, n_s, 1, (float)c.leaf, smn, smx);
-    HIP_TRY(hipEventRecord(W.ev[1], ctx->stream));
+    W.spans.mark(ctx, 1);
     IcpArgs a;
     memset(&a, 0, sizeof(a));
     for (int s = 0; s < c.n_stages; ++s) a.g[s] = stage_grid(ctx, W.grids[s], d_tgt, n_t, tmn, tmx, c.dist[s], "refine_icp");
-    HIP_TRY(hipEventRecord(W.ev[2], ctx->stream));
+    W.spans.mark(ctx, 2);
     const uint32_t blocks = std::max(1u, cdiv(n, CORR_TPB));
     a.tgt = d_tgt; a.src = W.vox.out_xyz.p; a.stride = 3; a.n = n;
     a.st = W.st.ensure(1);
@@ -134,7 +132,7 @@ int refine_dev(plade_ctx *ctx, IcpWork &W, const float *d_tgt, uint32_t n_t, con
         hipLaunchKernelGGL(k_icp_solve29, dim3(1), dim3(64), 0, ctx->stream, sa);
     }
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(W.ev[3], ctx->stream));
+    W.spans.mark(ctx, 3);
     HIP_TRY(hipMemcpyAsync(&W.h_st, W.st.p, sizeof(IcpState), hipMemcpyDeviceToHost, ctx->stream));
     ctx->sync();
     const IcpState &s = W.h_st;
@@ -150,12 +148,11 @@ int refine_dev(plade_ctx *ctx, IcpWork &W, const float *d_tgt, uint32_t n_t, con
     r.fitness = n ? (double)s.count / (double)n : 0.0;
     r.final_dist = c.dist[s.lin_stage];
     if (res) *res = r;
-    float ms[3] = {0.f, 0.f, 0.f};
-    for (int k = 0; k < 3; ++k) HIP_TRY(hipEventElapsedTime(&ms[k], W.ev[k], W.ev[k + 1]));
+    W.spans.collect();
     ctx->stats.clear();
-    ctx->stats.add("icp_sample_s", 1e-3 * ms[0]);
-    ctx->stats.add("icp_grid_s", 1e-3 * ms[1]);
-    ctx->stats.add("icp_loop_s", 1e-3 * ms[2]);
+    ctx->stats.add("icp_sample_s", W.spans.seconds(0));
+    ctx->stats.add("icp_grid_s", W.spans.seconds(1));
+    ctx->stats.add("icp_loop_s", W.spans.seconds(2));
     ctx->stats.add("icp_iterations", s.iter);
     ctx->stats.add("icp_stages", c.n_stages);
     if (s.failure) {

@@ -2,7 +2,7 @@
 //
 // Layout
 //   grids    k_m3c2_transform writes B under T into a scratch xyz array; one dense row index of TargetGrid over A and one over
-//            B'.  The cell is 1.03 R + 4e-6 max|coordinate| (the smoothing cell of DESIGN.md section 15; build() may enlarge it), so
+//            B'.  The cell is radius_cell(R) (grid_walk.h: the smoothing cell of DESIGN.md section 15; build() may enlarge it), so
 //            a cylinder is a few cells wide and L / cell cells long.  The walk reads the grid's actual cell, never R.
 //   walk     k_m3c2_walk: one wavefront per core point (a cylinder is long: one lane per core point would diverge over its whole
 //            length); the core point, the axis and every bound are wave-uniform.  The cover is by grid rows -- a row is a (y, z)
@@ -17,9 +17,9 @@
 //            every row once with one run (so every grid point at most once), and reads the cells of the clipped stretches only:
 //            O(L / cell (R / cell + 1)^2) cells for a generic axis.  What scales with the bounding rectangle is the row test (a
 //            few fp64 operations per row, no memory access).
-//   summary  k_m3c2_sum / k_m3c2_final, the pattern of k_smooth_sum / k_smooth_final: a butterfly per wave, the waves in order,
-//            one partial per workgroup; one wavefront reduces the partials in a fixed order.
+//   summary  k_m3c2_sum / k_m3c2_final, in the fixed order of fixed_reduce.h.
 #include "m3c2.h"
+#include "fixed_reduce.h"
 #include "grid_walk.h"
 #include "voxel.h"
 
@@ -172,67 +172,44 @@ __global__ __launch_bounds__(64 * WALK_WAVES) void k_m3c2_walk(const WalkArgs a)
 
 // per workgroup: pd[3 b] = the sum of distance, pd[3 b + 1] = of distance^2, pd[3 b + 2] = the max of |distance| over its valid core
 // points (a valid core point is one whose distance is not NaN); pu[3 b] = their number, pu[3 b + 1] = the significant ones,
-// pu[3 b + 2] = its largest count.  Fixed order: a butterfly across the wave, the waves in order
+// pu[3 b + 2] = its largest count (the order: fixed_reduce.h; terms 0 and 1 of each type are sums, term 2 a maximum)
+struct SumMaxD {
+    __device__ __forceinline__ double operator()(int k, double a, double b) const { return k == 2 ? fmax(a, b) : a + b; }
+};
+struct SumMaxU {
+    __device__ __forceinline__ uint32_t operator()(int k, uint32_t a, uint32_t b) const { return k == 2 ? max(a, b) : a + b; }
+};
+
 __global__ __launch_bounds__(SUM_TPB) void k_m3c2_sum(const double *__restrict__ distance, const uint8_t *__restrict__ significant,
                                                       const uint32_t *__restrict__ count, uint32_t m, double *__restrict__ pd,
                                                       uint32_t *__restrict__ pu) {
-    __shared__ double s_sum[SUM_TPB / 64], s_sq[SUM_TPB / 64], s_max[SUM_TPB / 64];
-    __shared__ uint32_t s_val[SUM_TPB / 64], s_sig[SUM_TPB / 64], s_cnt[SUM_TPB / 64];
+    __shared__ double s_d[SUM_TPB / 64][3];
+    __shared__ uint32_t s_u[SUM_TPB / 64][3];
     const uint32_t i = blockIdx.x * SUM_TPB + threadIdx.x;
-    double v = 0.0, q = 0.0, mx = 0.0;
-    uint32_t f = 0, sg = 0, c = 0;
+    double d[3] = {0.0, 0.0, 0.0};   // distance, distance^2, |distance|
+    uint32_t u[3] = {0, 0, 0};       // valid, significant, count
     if (i < m) {
-        c = max(count[2 * (size_t)i], count[2 * (size_t)i + 1]);
+        u[2] = max(count[2 * (size_t)i], count[2 * (size_t)i + 1]);
         const double e = distance[i];
-        if (e == e) { v = e; q = e * e; mx = fabs(e); f = 1; sg = significant[i]; }
+        if (e == e) { d[0] = e; d[1] = e * e; d[2] = fabs(e); u[0] = 1; u[1] = significant[i]; }
     }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        v += __shfl_xor(v, o, 64);
-        q += __shfl_xor(q, o, 64);
-        mx = fmax(mx, __shfl_xor(mx, o, 64));
-        f += __shfl_xor(f, o, 64);
-        sg += __shfl_xor(sg, o, 64);
-        c = max(c, __shfl_xor(c, o, 64));
-    }
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { s_sum[w] = v; s_sq[w] = q; s_max[w] = mx; s_val[w] = f; s_sig[w] = sg; s_cnt[w] = c; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = s_sum[0], tq = s_sq[0], tm = s_max[0];
-        uint32_t tf = s_val[0], ts = s_sig[0], tc = s_cnt[0];
-#pragma unroll
-        for (int k = 1; k < SUM_TPB / 64; ++k) { t += s_sum[k]; tq += s_sq[k]; tm = fmax(tm, s_max[k]); tf += s_val[k]; ts += s_sig[k]; tc = max(tc, s_cnt[k]); }
-        pd[3 * blockIdx.x] = t; pd[3 * blockIdx.x + 1] = tq; pd[3 * blockIdx.x + 2] = tm;
-        pu[3 * blockIdx.x] = tf; pu[3 * blockIdx.x + 1] = ts; pu[3 * blockIdx.x + 2] = tc;
-    }
+    block_reduce<SUM_TPB>(d, s_d, pd, SumMaxD());
+    block_reduce<SUM_TPB>(u, s_u, pu, SumMaxU());
 }
 
 // rd[0] = mean, rd[1] = rms of distance, rd[2] = max of |distance| over the valid core points (NaN when there is none);
 // ru[0] = valid, ru[1] = significant, ru[2] = the largest count
 __global__ __launch_bounds__(64) void k_m3c2_final(const double *__restrict__ pd, const uint32_t *__restrict__ pu, uint32_t blocks,
                                                    double *__restrict__ rd, uint32_t *__restrict__ ru) {
-    const int lane = threadIdx.x;
-    double v = 0.0, q = 0.0, mx = 0.0;
-    uint32_t f = 0, sg = 0, c = 0;
-    for (uint32_t b = (uint32_t)lane; b < blocks; b += 64) {
-        v += pd[3 * b]; q += pd[3 * b + 1]; mx = fmax(mx, pd[3 * b + 2]);
-        f += pu[3 * b]; sg += pu[3 * b + 1]; c = max(c, pu[3 * b + 2]);
-    }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        v += __shfl_xor(v, o, 64);
-        q += __shfl_xor(q, o, 64);
-        mx = fmax(mx, __shfl_xor(mx, o, 64));
-        f += __shfl_xor(f, o, 64);
-        sg += __shfl_xor(sg, o, 64);
-        c = max(c, __shfl_xor(c, o, 64));
-    }
-    if (lane != 0) return;
-    rd[0] = f ? v / (double)f : NAN;
-    rd[1] = f ? sqrt(q / (double)f) : NAN;
-    rd[2] = f ? mx : NAN;
-    ru[0] = f; ru[1] = sg; ru[2] = c;
+    double d[3];
+    uint32_t u[3];
+    final_reduce(pd, pu, blocks, d, SumMaxD(), u, SumMaxU());
+    if (threadIdx.x != 0) return;
+    const uint32_t f = u[0];
+    rd[0] = f ? d[0] / (double)f : NAN;
+    rd[1] = f ? sqrt(d[1] / (double)f) : NAN;
+    rd[2] = f ? d[2] : NAN;
+    ru[0] = f; ru[1] = u[1]; ru[2] = u[2];
 }
 
 }  // namespace
@@ -243,10 +220,9 @@ struct M3c2Work {
     DBuf<double> distance, lod, sigma, moments, partial_d, res_d;
     DBuf<uint32_t> count, partial_u, res_u;
     DBuf<uint8_t> significant;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    EventSpans<4> spans;             // grid, walk, reduce
     double h_d[3] = {0.0, 0.0, 0.0};
     uint32_t h_u[3] = {0, 0, 0};
-    ~M3c2Work() { for (hipEvent_t &e : ev) if (e) (void)hipEventDestroy(e); }
 };
 M3c2Work *m3c2_work_create() { return new M3c2Work; }
 void m3c2_work_destroy(M3c2Work *w) { delete w; }
@@ -271,21 +247,12 @@ void check_params(const float *T16, const plade_m3c2_params &p) {
     PLADE_REQUIRE(p.min_points >= M3C2_MIN_POINTS, PLADE_EINVAL, "cloud_m3c2: min_points must be >= 2");
 }
 
-// the smoothing cell of section 15 on a cloud with this bounding box
-float cell_for(double R, const float mn[3], const float mx[3]) {
-    double amax = 0.0;
-    for (int t = 0; t < 3; ++t) amax = std::max(amax, std::max(std::fabs((double)mn[t]), std::fabs((double)mx[t])));
-    const double cell = 1.03 * R + 4e-6 * amax;
-    return (float)std::min(cell, 1e37);            // (1 / cell stays a normal fp32 number)
-}
-
 // M3C2 on device arrays: core m x core_stride (x y z nx ny nz first), A n_a x stride_a with a known bounding box, B n_b x stride_b.
 // Fills the wanted host outputs and the summary, waits, sets the stats.
 void m3c2_dev(plade_ctx *ctx, M3c2Work &W, const float *d_core, uint32_t m, uint32_t core_stride, const float *d_a, uint32_t n_a,
               uint32_t stride_a, const float amn[3], const float amx[3], const float *d_b, uint32_t n_b, uint32_t stride_b,
               const float *T16, const plade_m3c2_params &p, const Outputs &out, plade_m3c2_summary *summary) {
-    for (hipEvent_t &e : W.ev) if (!e) HIP_TRY(hipEventCreate(&e));
-    HIP_TRY(hipEventRecord(W.ev[0], ctx->stream));
+    W.spans.mark(ctx, 0);
     Xf T;
     for (int k = 0; k < 12; ++k) T.m[k] = T16[k];
     float *d_bt = W.xyz_b.ensure((size_t)n_b * 3 + 4);
@@ -293,9 +260,9 @@ void m3c2_dev(plade_ctx *ctx, M3c2Work &W, const float *d_core, uint32_t m, uint
     HIP_TRY(hipGetLastError());
     float bmn[3], bmx[3];
     bbox_host(ctx, d_bt, n_b, 3, bmn, bmx);          // (refuses a B' that left the fp32 range)
-    W.grid_a.build(ctx, d_a, n_a, stride_a, cell_for(p.radius, amn, amx), amn, amx, true);
-    W.grid_b.build(ctx, d_bt, n_b, 3, cell_for(p.radius, bmn, bmx), bmn, bmx, true);
-    HIP_TRY(hipEventRecord(W.ev[1], ctx->stream));
+    W.grid_a.build(ctx, d_a, n_a, stride_a, radius_cell(p.radius, amn, amx), amn, amx, true);
+    W.grid_b.build(ctx, d_bt, n_b, 3, radius_cell(p.radius, bmn, bmx), bmn, bmx, true);
+    W.spans.mark(ctx, 1);
 
     WalkArgs a;
     memset(&a, 0, sizeof(a));
@@ -314,7 +281,7 @@ void m3c2_dev(plade_ctx *ctx, M3c2Work &W, const float *d_core, uint32_t m, uint
     a.significant = W.significant.ensure((size_t)m + 4);
     hipLaunchKernelGGL(k_m3c2_walk, dim3(cdiv(m, WALK_WAVES)), dim3(64 * WALK_WAVES), 0, ctx->stream, a);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(W.ev[2], ctx->stream));
+    W.spans.mark(ctx, 2);
     const uint32_t blocks = cdiv(m, SUM_TPB);
     double *d_pd = W.partial_d.ensure((size_t)3 * blocks), *d_rd = W.res_d.ensure(4);
     uint32_t *d_pu = W.partial_u.ensure((size_t)3 * blocks), *d_ru = W.res_u.ensure(4);
@@ -323,7 +290,7 @@ void m3c2_dev(plade_ctx *ctx, M3c2Work &W, const float *d_core, uint32_t m, uint
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(W.h_d, d_rd, sizeof(W.h_d), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipMemcpyAsync(W.h_u, d_ru, sizeof(W.h_u), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipEventRecord(W.ev[3], ctx->stream));
+    W.spans.mark(ctx, 3);
     if (out.distance) HIP_TRY(hipMemcpyAsync(out.distance, a.distance, (size_t)m * 8, hipMemcpyDeviceToHost, ctx->stream));
     if (out.lod) HIP_TRY(hipMemcpyAsync(out.lod, a.lod, (size_t)m * 8, hipMemcpyDeviceToHost, ctx->stream));
     if (out.significant) HIP_TRY(hipMemcpyAsync(out.significant, a.significant, m, hipMemcpyDeviceToHost, ctx->stream));
@@ -339,12 +306,11 @@ void m3c2_dev(plade_ctx *ctx, M3c2Work &W, const float *d_core, uint32_t m, uint
     summary->max = W.h_d[2];
     summary->max_count = W.h_u[2];
     summary->reserved = 0;
-    float ms[3] = {0.f, 0.f, 0.f};
-    for (int k = 0; k < 3; ++k) HIP_TRY(hipEventElapsedTime(&ms[k], W.ev[k], W.ev[k + 1]));
+    W.spans.collect();
     ctx->stats.clear();
-    ctx->stats.add("m3c2_grid_s", 1e-3 * ms[0]);
-    ctx->stats.add("m3c2_walk_s", 1e-3 * ms[1]);
-    ctx->stats.add("m3c2_reduce_s", 1e-3 * ms[2]);
+    ctx->stats.add("m3c2_grid_s", W.spans.seconds(0));
+    ctx->stats.add("m3c2_walk_s", W.spans.seconds(1));
+    ctx->stats.add("m3c2_reduce_s", W.spans.seconds(2));
     ctx->stats.add("m3c2_valid", W.h_u[0]);
 }
 

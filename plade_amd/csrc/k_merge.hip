@@ -248,9 +248,8 @@ struct MergeWork {
     DBuf<float> sorted;              // six planes in voxel order
     DBuf<float> out_rows;
     DBuf<uint32_t> out_count, out_mask;
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    EventSpans<5> spans;             // transform; with a leaf: sort, runs, fuse
     uint32_t h_count[4] = {0, 0, 0, 0};
-    ~MergeWork() { for (hipEvent_t &e : ev) if (e) (void)hipEventDestroy(e); }
 };
 MergeWork *merge_work_create() { return new MergeWork; }
 void merge_work_destroy(MergeWork *w) { delete w; }
@@ -285,7 +284,6 @@ uint32_t check_args(uint32_t k, const void *const clouds[], const uint32_t n[], 
 // is the result.  With leaf > 0 the fused rows, counts and masks are left in W.out_*; returns the number of output rows (waits).
 uint32_t merge_dev(plade_ctx *ctx, MergeWork &W, uint32_t k, const float *const d_rows[], const uint32_t n[], const float *const *T,
                    float leaf, uint32_t total, float *d_cat, plade_merge_summary *summary) {
-    for (hipEvent_t &e : W.ev) if (!e) HIP_TRY(hipEventCreate(&e));
     MergeArgs A;
     memset(&A, 0, sizeof(A));
     for (uint32_t c = 0; c < (uint32_t)MERGE_MAX_CLOUDS; ++c) {
@@ -298,12 +296,12 @@ uint32_t merge_dev(plade_ctx *ctx, MergeWork &W, uint32_t k, const float *const 
     int init[8], box[8];
     bbox_init_pattern(init);
     int *d_slot = reinterpret_cast<int *>(ctx->scratch[3].ensure(64));
-    HIP_TRY(hipEventRecord(W.ev[0], ctx->stream));
+    W.spans.mark(ctx, 0);
     ctx->h2d(d_slot, init, 32);
     hipLaunchKernelGGL(k_merge_transform, dim3(std::min(cdiv(total, 1024), 1024u)), dim3(256), 0, ctx->stream, A, d_cat, d_slot);
     HIP_TRY(hipGetLastError());
     ctx->d2h(box, d_slot, 32);
-    HIP_TRY(hipEventRecord(W.ev[1], ctx->stream));
+    W.spans.mark(ctx, 1);
     ctx->sync();
     float mn[3], mx[3];
     bbox_decode(box, mn, mx);   // (refuses non-finite coordinates)
@@ -343,7 +341,7 @@ uint32_t merge_dev(plade_ctx *ctx, MergeWork &W, uint32_t k, const float *const 
                                lmin[2], bits[0], bits[1], W.keys.p, W.vals.p);
             sort_pairs_u64(ctx, W.keys.p, W.keys2.p, W.vals.p, W.vals2.p, total, key_bits);
         }
-        HIP_TRY(hipEventRecord(W.ev[2], ctx->stream));
+        W.spans.mark(ctx, 2);
         const ScanTicket t = scan_ticket(ctx, total, MR_TILE);
         if (narrow)
             hipLaunchKernelGGL(k_merge_runs<uint32_t>, dim3(t.tiles), dim3(MR_T), 0, ctx->stream, k32b, W.vals2.p, total, d_cat, A, t.state,
@@ -351,11 +349,11 @@ uint32_t merge_dev(plade_ctx *ctx, MergeWork &W, uint32_t k, const float *const 
         else
             hipLaunchKernelGGL(k_merge_runs<uint64_t>, dim3(t.tiles), dim3(MR_T), 0, ctx->stream, W.keys2.p, W.vals2.p, total, d_cat, A,
                                t.state, t.ticket, t.base, t.gen, W.heads.p, W.count.p, W.sorted.p, W.sbit.p);
-        HIP_TRY(hipEventRecord(W.ev[3], ctx->stream));
+        W.spans.mark(ctx, 3);
         hipLaunchKernelGGL(k_merge_fuse, dim3(cdiv(total, MF_T)), dim3(MF_T), 0, ctx->stream, W.sorted.p, W.sbit.p, W.heads.p, W.count.p,
                            total, W.out_rows.p, W.out_count.p, W.out_mask.p, W.count.p + 1);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(W.ev[4], ctx->stream));
+        W.spans.mark(ctx, 4);
         ctx->d2h(W.h_count, W.count.p, 16);
         ctx->sync();
         n_out = W.h_count[0]; n_shared = W.h_count[1]; max_count = W.h_count[2];
@@ -367,16 +365,12 @@ uint32_t merge_dev(plade_ctx *ctx, MergeWork &W, uint32_t k, const float *const 
         summary->max_count = max_count;
         summary->reserved = 0;
     }
-    float ms[4] = {0.f, 0.f, 0.f, 0.f};
-    // sync() above may have waited on a flag in host memory instead of the stream: the work is done, but the runtime need not
-    // have marked the events complete yet, and hipEventElapsedTime then answers "device not ready" (seen once in ~500 calls)
-    HIP_TRY(hipEventSynchronize(W.ev[fuse ? 4 : 1]));
-    for (int q = 0; q < (fuse ? 4 : 1); ++q) HIP_TRY(hipEventElapsedTime(&ms[q], W.ev[q], W.ev[q + 1]));
+    W.spans.collect(fuse ? 4 : 1);
     ctx->stats.clear();
-    ctx->stats.add("merge_transform_s", 1e-3 * ms[0]);
-    ctx->stats.add("merge_sort_s", 1e-3 * ms[1]);
-    ctx->stats.add("merge_runs_s", 1e-3 * ms[2]);
-    ctx->stats.add("merge_fuse_s", 1e-3 * ms[3]);
+    ctx->stats.add("merge_transform_s", W.spans.seconds(0));
+    ctx->stats.add("merge_sort_s", W.spans.seconds(1));
+    ctx->stats.add("merge_runs_s", W.spans.seconds(2));
+    ctx->stats.add("merge_fuse_s", W.spans.seconds(3));
     ctx->stats.add("merge_rows", n_out);
     return n_out;
 }

@@ -29,10 +29,9 @@ struct NormalsWork {
     DBuf<uint32_t> fail, count;
     DBuf<float> in, out, curv;       // the host-pointer entry points' device copies (grow-only)
     DBuf<int32_t> nbr;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    EventSpans<3> spans;             // grid, search
     int builds = 0;
     uint32_t h_count = 0;
-    ~NormalsWork() { for (hipEvent_t &e : ev) if (e) (void)hipEventDestroy(e); }
 };
 NormalsWork *normals_work_create() { return new NormalsWork; }
 void normals_work_destroy(NormalsWork *w) { delete w; }
@@ -187,13 +186,12 @@ void normals_check_args(uint32_t n, uint32_t stride, int k, const float *view) {
 
 void estimate_normals_dev(plade_ctx *ctx, NormalsWork &W, const float *d_xyz, uint32_t n, uint32_t stride, const float bbmin[3],
                           const float bbmax[3], int k, const float view[3], float *d_out, float *d_curv, int32_t *d_nbr) {
-    for (hipEvent_t &e : W.ev) if (!e) HIP_TRY(hipEventCreate(&e));
-    HIP_TRY(hipEventRecord(W.ev[0], ctx->stream));
+    W.spans.mark(ctx, 0);
     TargetGrid &G = W.grid;
     const int m = (int)std::min<uint32_t>((uint32_t)k, n);
     uint32_t *d_occ = W.count.ensure(4);   // [0]: the ring list's length, [1]: occupied cells
     W.builds = build_knn_grid(ctx, G, d_xyz, n, stride, bbmin, bbmax, k, d_occ + 1, "estimate_normals");
-    HIP_TRY(hipEventRecord(W.ev[1], ctx->stream));
+    W.spans.mark(ctx, 1);
     NrmArgs a;
     a.g = view_of(G, "estimate_normals");
     a.xyz = d_xyz; a.stride = stride; a.n = n; a.m = m; a.k = k;
@@ -207,17 +205,15 @@ void estimate_normals_dev(plade_ctx *ctx, NormalsWork &W, const float *d_xyz, ui
     else if (k <= 32) launch_search<32>(ctx, a);
     else launch_search<64>(ctx, a);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(W.ev[2], ctx->stream));
+    W.spans.mark(ctx, 2);
     ctx->d2h(&W.h_count, d_occ, 4);
 }
 
 void normals_stats(plade_ctx *ctx, NormalsWork &W) {
-    float t01 = 0.f, t12 = 0.f;
-    HIP_TRY(hipEventElapsedTime(&t01, W.ev[0], W.ev[1]));
-    HIP_TRY(hipEventElapsedTime(&t12, W.ev[1], W.ev[2]));
+    W.spans.collect();
     ctx->stats.clear();
-    ctx->stats.add("normals_grid_s", 1e-3 * t01);
-    ctx->stats.add("normals_search_s", 1e-3 * t12);
+    ctx->stats.add("normals_grid_s", W.spans.seconds(0));
+    ctx->stats.add("normals_search_s", W.spans.seconds(1));
     ctx->stats.add("normals_grid_builds", W.builds);
     ctx->stats.add("normals_ring_queries", W.h_count);
 }

@@ -3,7 +3,7 @@
 // Layout
 //   grid     the dense row index of TargetGrid, walked with the pieces of grid_walk.h.  Statistical mode: the cell of k_normals
 //            (build_knn_grid: an occupied cell holds about 0.7 k points, adapted to the measured occupancy).  Radius mode: the cell
-//            is 1.03 r + 4e-6 max|coordinate| (the rule of DESIGN.md section 10), so the 27-cell block around a point holds
+//            is radius_cell(r) of grid_walk.h (the rule of DESIGN.md section 10), so the 27-cell block around a point holds
 //            everything closer than r.
 //   search   k_outliers_grid<K>: one lane per point in the grid's sorted order keeps its K best (d, j) keys -- 64-bit words
 //            d_bits << 32 | j -- as a sorted list in registers, the point itself left out by its index.  A point whose k-th key is
@@ -13,12 +13,12 @@
 //            wave_merge).  m_i is summed in the same order by a broadcast per key: the same bits as the grid kernel would give.
 //   radius   k_outliers_radius: one lane per point in grid order counts the points of its 27-cell block closer than r.  Without
 //            the per-point counts a lane stops at the end of the row run that reaches min_neighbours.
-//   mu sigma k_outliers_sum / k_outliers_final, twice: a butterfly per wave, the waves in order, one partial per workgroup; one
-//            wavefront sums the partials (lane l: partials l, l + 64, ..., then a butterfly).  No fp64 atomics.  mu, sigma and the
-//            threshold stay on the device for the next kernel.
-//   keep     k_outliers_flags; compact_flags (one scan) gives the ascending kept list; k_outliers_gather copies the kept rows
-//            word by word.
+//   mu sigma k_outliers_sum / k_outliers_final, twice, in the fixed order of fixed_reduce.h.  mu, sigma and the threshold stay on
+//            the device for the next kernel.
+//   keep     k_outliers_flags; compact_flags (one scan) gives the ascending kept list; gather_rows (prims.h) copies the kept
+//            rows word by word.
 #include "outliers.h"
+#include "fixed_reduce.h"
 #include "grid_walk.h"
 #include "prims.h"
 #include "stages.h"
@@ -146,38 +146,26 @@ __global__ __launch_bounds__(RAD_TPB) void k_outliers_radius(const RadArgs a) {
     a.flags[self] = keep;
 }
 
-// pass 0: the partial sums of m_i; pass 1: of (m_i - mu)^2 with mu = stat[0].  Fixed order: a butterfly across the wave, the
-// waves in order
+// pass 0: the partial sums of m_i; pass 1: of (m_i - mu)^2 with mu = stat[0] (the order: fixed_reduce.h)
 __global__ __launch_bounds__(SUM_TPB) void k_outliers_sum(const double *__restrict__ mean, uint32_t n, const double *__restrict__ stat,
                                                           int pass, double *__restrict__ partial) {
-    __shared__ double s_red[SUM_TPB / 64];
+    __shared__ double s_red[SUM_TPB / 64][1];
     const uint32_t i = blockIdx.x * SUM_TPB + threadIdx.x;
-    double v = 0.0;
+    double v[1] = {0.0};
     if (i < n) {
-        v = mean[i];
-        if (pass) { const double e = v - stat[0]; v = e * e; }
+        v[0] = mean[i];
+        if (pass) { const double e = v[0] - stat[0]; v[0] = e * e; }
     }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = s_red[0];
-#pragma unroll
-        for (int w = 1; w < SUM_TPB / 64; ++w) t += s_red[w];
-        partial[blockIdx.x] = t;
-    }
+    block_reduce<SUM_TPB>(v, s_red, partial, SumOp());
 }
 
 // stat[0] = mu (pass 0); stat[1] = sigma, stat[2] = mu + alpha sigma (pass 1)
 __global__ __launch_bounds__(64) void k_outliers_final(const double *__restrict__ partial, uint32_t blocks, uint32_t n, int pass,
                                                        double alpha, double *__restrict__ stat) {
-    const int lane = threadIdx.x;
-    double v = 0.0;
-    for (uint32_t b = (uint32_t)lane; b < blocks; b += 64) v += partial[b];
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    if (lane != 0) return;
+    double s[1];
+    final_reduce(partial, blocks, s, SumOp());
+    if (threadIdx.x != 0) return;
+    const double v = s[0];
     if (!pass) { stat[0] = v / (double)n; return; }
     const double sigma = n > 1 ? sqrt(v / (double)(n - 1)) : 0.0;
     stat[1] = sigma;
@@ -191,15 +179,6 @@ __global__ __launch_bounds__(ROW_TPB) void k_outliers_flags(const double *__rest
     const uint32_t k = mean[i] <= stat[2] ? 1u : 0u;
     keep[i] = (uint8_t)k;
     flags[i] = k;
-}
-
-// out row o = in row kept[o], word by word (whatever the floats hold: NaN normals keep their bits)
-__global__ __launch_bounds__(ROW_TPB) void k_outliers_gather(const uint32_t *__restrict__ in, uint32_t stride, const uint32_t *__restrict__ kept,
-                                                             uint32_t total, uint32_t *__restrict__ out) {
-    const size_t w = (size_t)blockIdx.x * ROW_TPB + threadIdx.x;
-    if (w >= (size_t)total * stride) return;
-    const uint32_t o = (uint32_t)(w / stride), c = (uint32_t)(w - (size_t)o * stride);
-    out[w] = in[(size_t)kept[o] * stride + c];
 }
 
 template <int K>
@@ -216,11 +195,10 @@ struct OutlierWork {
     DBuf<float> in, out;             // the host-pointer entry point's device copies (grow-only)
     DBuf<double> mean, partial, stat;
     DBuf<uint8_t> keep;
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    EventSpans<5> spans;             // grid, search, reduce, compact
     int builds = 0;
     uint32_t h_count = 0;
     double h_stat[3] = {0.0, 0.0, 0.0};
-    ~OutlierWork() { for (hipEvent_t &e : ev) if (e) (void)hipEventDestroy(e); }
 };
 OutlierWork *outlier_work_create() { return new OutlierWork; }
 void outlier_work_destroy(OutlierWork *w) { delete w; }
@@ -248,8 +226,7 @@ void check_params(uint32_t n, uint32_t stride, const plade_outlier_params &p) {
 uint32_t filter_dev(plade_ctx *ctx, OutlierWork &W, const float *d_rows, uint32_t n, uint32_t stride, const float bbmin[3],
                     const float bbmax[3], const plade_outlier_params &p, bool want_values, const std::function<float *(uint32_t)> &dst,
                     plade_outlier_summary *summary) {
-    for (hipEvent_t &e : W.ev) if (!e) HIP_TRY(hipEventCreate(&e));
-    HIP_TRY(hipEventRecord(W.ev[0], ctx->stream));
+    W.spans.mark(ctx, 0);
     TargetGrid &G = W.grid;
     const bool stat = p.mode == PLADE_OUTLIER_STATISTICAL;
     uint32_t *d_cnt = W.count.ensure(4);   // [0]: the ring list's length, [1]: occupied cells
@@ -265,10 +242,10 @@ uint32_t filter_dev(plade_ctx *ctx, OutlierWork &W, const float *d_rows, uint32_
         double *d_mean = W.mean.ensure(n);
         if (m == 0) {                      // n = 1: m_0 = 0
             ctx->fill_async(d_mean, 0, 8);
-            HIP_TRY(hipEventRecord(W.ev[1], ctx->stream));
+            W.spans.mark(ctx, 1);
         } else {
             W.builds = build_knn_grid(ctx, G, d_rows, n, stride, bbmin, bbmax, k, d_cnt + 1, "filter_outliers");
-            HIP_TRY(hipEventRecord(W.ev[1], ctx->stream));
+            W.spans.mark(ctx, 1);
             StatArgs a;
             memset(&a, 0, sizeof(a));
             a.g = view_of(G, "filter_outliers");
@@ -282,7 +259,7 @@ uint32_t filter_dev(plade_ctx *ctx, OutlierWork &W, const float *d_rows, uint32_
             else launch_search<64>(ctx, a);
             HIP_TRY(hipGetLastError());
         }
-        HIP_TRY(hipEventRecord(W.ev[2], ctx->stream));
+        W.spans.mark(ctx, 2);
         const uint32_t blocks = cdiv(n, SUM_TPB);
         double *d_partial = W.partial.ensure(blocks);
         for (int pass = 0; pass < 2; ++pass) {
@@ -295,11 +272,9 @@ uint32_t filter_dev(plade_ctx *ctx, OutlierWork &W, const float *d_rows, uint32_
         HIP_TRY(hipMemcpyAsync(&W.h_count, d_cnt, 4, hipMemcpyDeviceToHost, ctx->stream));
     } else {
         const float r = (float)p.radius;
-        double amax = 0.0;
-        for (int t = 0; t < 3; ++t) amax = std::max(amax, std::max(std::fabs((double)bbmin[t]), std::fabs((double)bbmax[t])));
-        G.build(ctx, d_rows, n, stride, (float)(1.03 * (double)r + 4e-6 * amax), bbmin, bbmax, true);
+        G.build(ctx, d_rows, n, stride, radius_cell((double)r, bbmin, bbmax), bbmin, bbmax, true);
         ++W.builds;
-        HIP_TRY(hipEventRecord(W.ev[1], ctx->stream));
+        W.spans.mark(ctx, 1);
         RadArgs a;
         memset(&a, 0, sizeof(a));
         a.g = view_of(G, "filter_outliers");
@@ -310,18 +285,12 @@ uint32_t filter_dev(plade_ctx *ctx, OutlierWork &W, const float *d_rows, uint32_
         a.keep = d_keep; a.flags = d_flags;
         hipLaunchKernelGGL(k_outliers_radius, dim3(cdiv(n, RAD_TPB)), dim3(RAD_TPB), 0, ctx->stream, a);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(W.ev[2], ctx->stream));
+        W.spans.mark(ctx, 2);
     }
-    HIP_TRY(hipEventRecord(W.ev[3], ctx->stream));
+    W.spans.mark(ctx, 3);
     const uint32_t total = compact_flags(ctx, d_flags, n, W.pos, W.kept);   // (waits for the count)
-    if (total) {
-        float *d_out = dst(total);
-        const size_t words = (size_t)total * stride;
-        hipLaunchKernelGGL(k_outliers_gather, dim3(cdiv(words, ROW_TPB)), dim3(ROW_TPB), 0, ctx->stream,
-                           reinterpret_cast<const uint32_t *>(d_rows), stride, W.kept.p, total, reinterpret_cast<uint32_t *>(d_out));
-        HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipEventRecord(W.ev[4], ctx->stream));
+    if (total) gather_rows(ctx, d_rows, stride, W.kept.p, total, dst(total));
+    W.spans.mark(ctx, 4);
     ctx->sync();
     if (summary) {
         summary->n = n;
@@ -330,13 +299,12 @@ uint32_t filter_dev(plade_ctx *ctx, OutlierWork &W, const float *d_rows, uint32_
         summary->sigma = stat ? W.h_stat[1] : NAN;
         summary->threshold = stat ? W.h_stat[2] : NAN;
     }
-    float ms[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int k = 0; k < 4; ++k) HIP_TRY(hipEventElapsedTime(&ms[k], W.ev[k], W.ev[k + 1]));
+    W.spans.collect();
     ctx->stats.clear();
-    ctx->stats.add("outliers_grid_s", 1e-3 * ms[0]);
-    ctx->stats.add("outliers_search_s", 1e-3 * ms[1]);
-    ctx->stats.add("outliers_reduce_s", 1e-3 * ms[2]);
-    ctx->stats.add("outliers_compact_s", 1e-3 * ms[3]);
+    ctx->stats.add("outliers_grid_s", W.spans.seconds(0));
+    ctx->stats.add("outliers_search_s", W.spans.seconds(1));
+    ctx->stats.add("outliers_reduce_s", W.spans.seconds(2));
+    ctx->stats.add("outliers_compact_s", W.spans.seconds(3));
     ctx->stats.add("outliers_grid_builds", W.builds);
     ctx->stats.add("outliers_ring_queries", W.h_count);
     ctx->stats.add("outliers_kept", total);

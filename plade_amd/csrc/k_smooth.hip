@@ -2,16 +2,16 @@
 //
 // Layout
 //   grid     the dense row index of TargetGrid, built as the radius filter of k_outliers.hip builds it: the cell is
-//            1.03 r + 4e-6 max|coordinate| (the rule of DESIGN.md section 10; build() may enlarge it, never shrink it), so the 27-cell
+//            radius_cell(r) of grid_walk.h (the rule of DESIGN.md section 10; build() may enlarge it, never shrink it), so the 27-cell
 //            block around a point holds everything closer than r.
 //   fit      k_smooth_fit: one lane per point in the grid's sorted order (the 64 queries of a wavefront share their candidate runs,
 //            as in k_outliers_radius).  A lane walks the nine runs of for_block27 with ten fp64 accumulators (W, S, M about the
 //            query) and a count, then solves the fit with pca_eig (pca_eig.h, the eigen-solve of k_normals), projects the point
 //            and writes its outputs by original index.  No LDS, no atomics.
-//   summary  k_smooth_sum / k_smooth_final, the pattern of k_outliers_sum / k_outliers_final: a butterfly per wave, the waves in
-//            order, one partial per workgroup; one wavefront reduces the partials (lane l: partials l, l + 64, ..., then a
-//            butterfly).  Sum of delta^2 and max |delta| over the fitted points, their number, the largest count.
+//   summary  k_smooth_sum / k_smooth_final, in the fixed order of fixed_reduce.h: sum of delta^2 and max |delta| over the fitted
+//            points, their number, the largest count.
 #include "smooth.h"
+#include "fixed_reduce.h"
 #include "grid_walk.h"
 #include "pca_eig.h"
 #include "voxel.h"
@@ -108,56 +108,40 @@ __global__ __launch_bounds__(FIT_TPB) void k_smooth_fit(const FitArgs a) {
 }
 
 // per workgroup: pd[2 b] = the sum of delta^2, pd[2 b + 1] = the max of |delta| over its fitted points; pu[2 b] = their number,
-// pu[2 b + 1] = its largest count.  Fixed order: a butterfly across the wave, the waves in order
+// pu[2 b + 1] = its largest count (the order: fixed_reduce.h; term 0 of each type is a sum, term 1 a maximum)
+struct SumMaxD {
+    __device__ __forceinline__ double operator()(int k, double a, double b) const { return k == 1 ? fmax(a, b) : a + b; }
+};
+struct SumMaxU {
+    __device__ __forceinline__ uint32_t operator()(int k, uint32_t a, uint32_t b) const { return k == 1 ? max(a, b) : a + b; }
+};
+
 __global__ __launch_bounds__(SUM_TPB) void k_smooth_sum(const double *__restrict__ disp, const uint8_t *__restrict__ fitted,
                                                         const uint32_t *__restrict__ count, uint32_t n, double *__restrict__ pd,
                                                         uint32_t *__restrict__ pu) {
-    __shared__ double s_sum[SUM_TPB / 64], s_max[SUM_TPB / 64];
-    __shared__ uint32_t s_fit[SUM_TPB / 64], s_cnt[SUM_TPB / 64];
+    __shared__ double s_d[SUM_TPB / 64][2];
+    __shared__ uint32_t s_u[SUM_TPB / 64][2];
     const uint32_t i = blockIdx.x * SUM_TPB + threadIdx.x;
-    double v = 0.0, mx = 0.0;
-    uint32_t f = 0, c = 0;
+    double d[2] = {0.0, 0.0};        // delta^2, |delta|
+    uint32_t u[2] = {0, 0};          // fitted, count
     if (i < n) {
-        c = count[i];
-        if (fitted[i]) { const double e = disp[i]; v = e * e; mx = fabs(e); f = 1; }
+        u[1] = count[i];
+        if (fitted[i]) { const double e = disp[i]; d[0] = e * e; d[1] = fabs(e); u[0] = 1; }
     }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        v += __shfl_xor(v, o, 64);
-        mx = fmax(mx, __shfl_xor(mx, o, 64));
-        f += __shfl_xor(f, o, 64);
-        c = max(c, __shfl_xor(c, o, 64));
-    }
-    if ((threadIdx.x & 63) == 0) { s_sum[threadIdx.x >> 6] = v; s_max[threadIdx.x >> 6] = mx; s_fit[threadIdx.x >> 6] = f; s_cnt[threadIdx.x >> 6] = c; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = s_sum[0], m = s_max[0];
-        uint32_t tf = s_fit[0], tc = s_cnt[0];
-#pragma unroll
-        for (int w = 1; w < SUM_TPB / 64; ++w) { t += s_sum[w]; m = fmax(m, s_max[w]); tf += s_fit[w]; tc = max(tc, s_cnt[w]); }
-        pd[2 * blockIdx.x] = t; pd[2 * blockIdx.x + 1] = m;
-        pu[2 * blockIdx.x] = tf; pu[2 * blockIdx.x + 1] = tc;
-    }
+    block_reduce<SUM_TPB>(d, s_d, pd, SumMaxD());
+    block_reduce<SUM_TPB>(u, s_u, pu, SumMaxU());
 }
 
 // rd[0] = rms, rd[1] = max of |delta| over the fitted points (0 when there is none); ru[0] = fitted, ru[1] = the largest count
 __global__ __launch_bounds__(64) void k_smooth_final(const double *__restrict__ pd, const uint32_t *__restrict__ pu, uint32_t blocks,
                                                      double *__restrict__ rd, uint32_t *__restrict__ ru) {
-    const int lane = threadIdx.x;
-    double v = 0.0, mx = 0.0;
-    uint32_t f = 0, c = 0;
-    for (uint32_t b = (uint32_t)lane; b < blocks; b += 64) { v += pd[2 * b]; mx = fmax(mx, pd[2 * b + 1]); f += pu[2 * b]; c = max(c, pu[2 * b + 1]); }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        v += __shfl_xor(v, o, 64);
-        mx = fmax(mx, __shfl_xor(mx, o, 64));
-        f += __shfl_xor(f, o, 64);
-        c = max(c, __shfl_xor(c, o, 64));
-    }
-    if (lane != 0) return;
-    rd[0] = f ? sqrt(v / (double)f) : 0.0;
-    rd[1] = mx;
-    ru[0] = f; ru[1] = c;
+    double d[2];
+    uint32_t u[2];
+    final_reduce(pd, pu, blocks, d, SumMaxD(), u, SumMaxU());
+    if (threadIdx.x != 0) return;
+    rd[0] = u[0] ? sqrt(d[0] / (double)u[0]) : 0.0;
+    rd[1] = d[1];
+    ru[0] = u[0]; ru[1] = u[1];
 }
 
 }  // namespace
@@ -168,10 +152,9 @@ struct SmoothWork {
     DBuf<double> disp, moments, partial_d, res_d;
     DBuf<uint32_t> count, partial_u, res_u;
     DBuf<uint8_t> fitted;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    EventSpans<4> spans;             // grid, fit, reduce
     double h_d[2] = {0.0, 0.0};
     uint32_t h_u[2] = {0, 0};
-    ~SmoothWork() { for (hipEvent_t &e : ev) if (e) (void)hipEventDestroy(e); }
 };
 SmoothWork *smooth_work_create() { return new SmoothWork; }
 void smooth_work_destroy(SmoothWork *w) { delete w; }
@@ -195,14 +178,11 @@ void check_params(uint32_t n, uint32_t stride, const plade_smooth_params &p) {
 // in W, waits, fills the summary and the stats.
 void smooth_dev(plade_ctx *ctx, SmoothWork &W, const float *d_rows, uint32_t n, uint32_t stride, const float bbmin[3], const float bbmax[3],
                 const plade_smooth_params &p, FitArgs a, plade_smooth_summary *summary) {
-    for (hipEvent_t &e : W.ev) if (!e) HIP_TRY(hipEventCreate(&e));
-    HIP_TRY(hipEventRecord(W.ev[0], ctx->stream));
+    W.spans.mark(ctx, 0);
     TargetGrid &G = W.grid;
     const float r = (float)p.radius;
-    double amax = 0.0;
-    for (int t = 0; t < 3; ++t) amax = std::max(amax, std::max(std::fabs((double)bbmin[t]), std::fabs((double)bbmax[t])));
-    G.build(ctx, d_rows, n, stride, (float)(1.03 * (double)r + 4e-6 * amax), bbmin, bbmax, true);
-    HIP_TRY(hipEventRecord(W.ev[1], ctx->stream));
+    G.build(ctx, d_rows, n, stride, radius_cell((double)r, bbmin, bbmax), bbmin, bbmax, true);
+    W.spans.mark(ctx, 1);
     a.g = view_of(G, "smooth_cloud");
     a.n = n; a.r2 = r * r;
     a.min_nb = (uint32_t)p.min_neighbours;
@@ -212,7 +192,7 @@ void smooth_dev(plade_ctx *ctx, SmoothWork &W, const float *d_rows, uint32_t n, 
     a.fitted = W.fitted.ensure((size_t)n + 4);
     hipLaunchKernelGGL(k_smooth_fit, dim3(cdiv(n, FIT_TPB)), dim3(FIT_TPB), 0, ctx->stream, a);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(W.ev[2], ctx->stream));
+    W.spans.mark(ctx, 2);
     const uint32_t blocks = cdiv(n, SUM_TPB);
     double *d_pd = W.partial_d.ensure((size_t)2 * blocks), *d_rd = W.res_d.ensure(2);
     uint32_t *d_pu = W.partial_u.ensure((size_t)2 * blocks), *d_ru = W.res_u.ensure(2);
@@ -221,7 +201,7 @@ void smooth_dev(plade_ctx *ctx, SmoothWork &W, const float *d_rows, uint32_t n, 
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(W.h_d, d_rd, sizeof(W.h_d), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipMemcpyAsync(W.h_u, d_ru, sizeof(W.h_u), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipEventRecord(W.ev[3], ctx->stream));
+    W.spans.mark(ctx, 3);
     ctx->sync();
     if (summary) {
         summary->n = n;
@@ -231,12 +211,11 @@ void smooth_dev(plade_ctx *ctx, SmoothWork &W, const float *d_rows, uint32_t n, 
         summary->max_count = W.h_u[1];
         summary->reserved = 0;
     }
-    float ms[3] = {0.f, 0.f, 0.f};
-    for (int k = 0; k < 3; ++k) HIP_TRY(hipEventElapsedTime(&ms[k], W.ev[k], W.ev[k + 1]));
+    W.spans.collect();
     ctx->stats.clear();
-    ctx->stats.add("smooth_grid_s", 1e-3 * ms[0]);
-    ctx->stats.add("smooth_fit_s", 1e-3 * ms[1]);
-    ctx->stats.add("smooth_reduce_s", 1e-3 * ms[2]);
+    ctx->stats.add("smooth_grid_s", W.spans.seconds(0));
+    ctx->stats.add("smooth_fit_s", W.spans.seconds(1));
+    ctx->stats.add("smooth_reduce_s", W.spans.seconds(2));
     ctx->stats.add("smooth_fitted", W.h_u[0]);
 }
 

@@ -25,5 +25,7 @@ void exclusive_scan_u32(plade_ctx *ctx, const uint32_t *in, uint32_t *out, size_
 // tagged with gen in bits 34..63, status in bits 32..33 (1 aggregate, 2 inclusive prefix), value in bits 0..31.
 struct ScanTicket { uint64_t *state; uint32_t *ticket; uint32_t base, gen, tiles; };
 ScanTicket scan_ticket(plade_ctx *ctx, size_t n, uint32_t tile_items);
+// d_out row o = d_rows row kept[o] for o < total (rows of `stride` floats, copied as words: every bit pattern survives)
+void gather_rows(plade_ctx *ctx, const float *d_rows, uint32_t stride, const uint32_t *kept, uint32_t total, float *d_out);
 
 }  // namespace plade

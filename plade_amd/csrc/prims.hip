@@ -124,6 +124,26 @@ void exclusive_scan_u32(plade_ctx *ctx, const uint32_t *in, uint32_t *out, size_
     launch<k_scan_u32, SC_T>(ctx, dim3(t.tiles), 0, in, out, (uint32_t)n, t.state, t.ticket, t.base, t.gen);
 }
 
+// ---- the kept-row gather ----------------------------------------------------------------------------------------------------
+namespace {
+constexpr int ROW_TPB = 256;
+// out row o = in row kept[o], word by word (whatever the floats hold: NaN normals keep their bits)
+__global__ __launch_bounds__(ROW_TPB) void k_gather_rows(const uint32_t *__restrict__ in, uint32_t stride, const uint32_t *__restrict__ kept,
+                                                         uint32_t total, uint32_t *__restrict__ out) {
+    const size_t w = (size_t)blockIdx.x * ROW_TPB + threadIdx.x;
+    if (w >= (size_t)total * stride) return;
+    const uint32_t o = (uint32_t)(w / stride), c = (uint32_t)(w - (size_t)o * stride);
+    out[w] = in[(size_t)kept[o] * stride + c];
+}
+}  // namespace
+
+void gather_rows(plade_ctx *ctx, const float *d_rows, uint32_t stride, const uint32_t *kept, uint32_t total, float *d_out) {
+    const size_t words = (size_t)total * stride;
+    if (!words) return;
+    hipLaunchKernelGGL(k_gather_rows, dim3(cdiv(words, ROW_TPB)), dim3(ROW_TPB), 0, ctx->stream, reinterpret_cast<const uint32_t *>(d_rows),
+                       stride, kept, total, reinterpret_cast<uint32_t *>(d_out));
+    HIP_TRY(hipGetLastError());
+}
 
 // ---- device -> host hand-over (ctx.h: plade_ctx::d2h / sync) ----------------------------------------------------------
 // grid (chunks, ranges): workgroup (x, r) copies words x * 1024 .. of range r into the arena; the workgroup that finishes

@@ -189,6 +189,30 @@ int plade_overlap_counts(plade_ctx *ctx, const float *src_ds, uint32_t n_s, cons
 int plade_cluster_transforms(plade_ctx *ctx, const float *t_xyz, const float *euler, uint32_t m, float dist_threshold,
                              float angle_gate, int32_t *cluster_of, uint32_t *n_clusters);
 
+/* ---- seam of the penetration filter (A11) -------------------------------------------------------
+ * Replaces the loop code/PLADE/util.cpp:450-519 around AreTwoPlanesPenetrable (util.cpp:1279-1458) on the filter's own
+ * tables: cand = K x 12 (R row-major, then T); per side (s_ = source, t_ = target) coef P x 4, center P x 3, four P x 12
+ * (the plane's projected rectangle), pts = the per-plane downsampled clouds end to end (x, y, z), off = P + 1 offsets into
+ * them (points).  flags[k] = 1 when candidate k has a penetrating plane pair.  PLADE_ELIMIT when a common segment is
+ * longer than 1024 search steps.
+ * items != NULL asks for the AUDIT: one plade_pen_item per (candidate, source plane, target plane) that reached the walks
+ * (in no particular order; *n_items of them, PLADE_ECAP when items_cap is smaller; K * ps * pt always suffices), and every
+ * such item is then evaluated in full -- no early exit once its candidate is flagged, the second walk also behind a failed
+ * first one.  plane1 = the transformed source plane, start / direc / length = the common segment, nsteps = the search
+ * steps with dist < length; pass 0 classifies the transformed source points against the target plane behind the target
+ * cloud's gate, pass 1 the other way round: pos / neg = points on either side, gated = the steps whose gate found two
+ * points; verdict = 1 when the pair penetrates. */
+typedef struct plade_pen_item {
+    uint32_t k, i1, j1;
+    float plane1[4], start[3], direc[3], length;
+    int32_t nsteps, pos[2], neg[2], gated[2], verdict;
+} plade_pen_item;
+int plade_penetration_filter(plade_ctx *ctx, const float *cand, uint32_t K, const float *s_coef, const float *s_center,
+                             const float *s_four, const float *s_pts, const uint32_t *s_off, uint32_t ps,
+                             const float *t_coef, const float *t_center, const float *t_four, const float *t_pts,
+                             const uint32_t *t_off, uint32_t pt, float length_threshold, float angle_threshold,
+                             int32_t *flags, plade_pen_item *items, uint64_t items_cap, uint64_t *n_items);
+
 /* ---- seams of the line geometry (A6 / A11) ------------------------------------------------------
  * plade_closest_points replaces ComputeNearstTwoPointsOfTwo3DLine (code/PLADE/util.cpp:1167-1229) for n line pairs:
  * u1, u2 (n x 3, directions: normalised first, as the reference does in place), p1, p2 (n x 3, a point of each line) ->

@@ -85,6 +85,25 @@ class Oracle:
         L.orc_cluster_transforms.argtypes = [_p, _p, _i, _f, _f, _p]
         L.orc_euler_angles.argtypes = [_p, _p]
         L.orc_pen_walk.argtypes = [_p, _i, _p, _i, _p, _p, _p, _f, _f, _f, _p, _p, _p]
+        L.orc_penetration_items.argtypes = [_p, _i, _p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _i, _f, _f, _p]
+
+    def penetration_items(self, cand, src, tgt, length_threshold, angle_threshold):
+        """Every triple (k, i1, j1) of the penetration filter, none short-circuited (orc_penetration_items).  cand: K x 12;
+        src / tgt: (coef P x 4, center P x 3, four P x 12, pts N x 3, off P + 1).  Returns K * Ps * Pt records (PEN_RECORD)
+        in (k, i1, j1) order."""
+        cand = _f32(cand).reshape(-1, 12)
+        sides = []
+        for coef, center, four, pts, off in (src, tgt):
+            coef = _f32(coef).reshape(-1, 4)
+            off = _i32(off)
+            assert len(off) == len(coef) + 1
+            sides.append((coef, _f32(center).reshape(-1, 3), _f32(four).reshape(-1, 12), _f32(pts).reshape(-1, 3), off))
+        (sc, sce, sf, sp, so), (tc, tce, tf, tp, to) = sides
+        rec = np.zeros(len(cand) * len(sc) * len(tc), PEN_RECORD)
+        self.L.orc_penetration_items(_ptr(cand), len(cand), _ptr(sc), _ptr(sce), _ptr(sf), _ptr(sp), _ptr(so), len(sc),
+                                     _ptr(tc), _ptr(tce), _ptr(tf), _ptr(tp), _ptr(to), len(tc), length_threshold,
+                                     angle_threshold, _ptr(rec))
+        return rec
 
     def set_closest_point_mode(self, mode):
         """1 / "svd_fp32" (default, = the HIP path's default): the reference's fp32 cv::solve (DECOMP_SVD) restated from OpenCV 2.4
@@ -255,6 +274,12 @@ class Oracle:
         return bool(ok), T, dump
 
 
+# orc_pen_record (oracle/plade_oracle.h)
+PEN_GATED, PEN_NO_LINE, PEN_NO_HITS, PEN_HIT_COUNT, PEN_NO_OVERLAP, PEN_WALKED = range(6)
+PEN_RECORD = np.dtype([("k", np.int32), ("i1", np.int32), ("j1", np.int32), ("status", np.int32), ("plane1", np.float32, 4),
+                       ("start", np.float32, 3), ("direc", np.float32, 3), ("length", np.float32), ("nsteps", np.int32),
+                       ("positive", np.int32, 2), ("negative", np.int32, 2), ("skipped", np.int32, 2), ("verdict", np.int32)])
+
 # name -> dtype of every intermediate the oracle (and the product, under the same names) can dump
 ORC_DUMP_FIELDS = {
     "average_spacing": np.float32, "scale": np.float32,
@@ -268,7 +293,7 @@ ORC_DUMP_FIELDS = {
     "tgt_desc": np.float32, "src_desc": np.float32,
     "match_offsets": np.int64, "match_nbr": np.int32, "match_dist2": np.float64,
     "initial_RT": np.float32, "cluster_sizes": np.int32, "cluster_seeds": np.int32,
-    "plane_match_counts": np.int32, "pen_tested": np.int32, "pen_flags": np.int32,
+    "plane_match_counts": np.int32, "pen_tested": np.int32, "pen_flags": np.int32, "pen_candidates": np.float32,
     "candidates": np.float32, "candidate_centers": np.float32, "overlap_counts": np.int32,
     "scores": np.float32, "best_index": np.int32, "timing": np.float64, "timing_names": np.uint8,
 }

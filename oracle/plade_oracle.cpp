@@ -1036,12 +1036,16 @@ void pen_walk(const std::vector<V3> &ptsA, const GridIndex &gA, const GridIndex 
     }
 }
 
-// AreTwoPlanesPenetrable (code/PLADE/util.cpp:1279-1458)
+// AreTwoPlanesPenetrable (code/PLADE/util.cpp:1279-1458).  `au` (orc_penetration_items): where the pair left the function,
+// the common segment and both walks' counts; with it the second walk runs also where the first fails its thresholds
+// (the verdict is the same: it needs both).
 int planes_penetrable(const float *plane1, const float *plane2, const V3 *corners1, const V3 *corners2,
                       const std::vector<V3> &pts1, const GridIndex &g1, const std::vector<V3> &pts2,
-                      const GridIndex &g2, bool &pen, float searchRadius, int minPointsNum, float minDistance) {
+                      const GridIndex &g2, bool &pen, float searchRadius, int minPointsNum, float minDistance,
+                      orc_pen_record *au = nullptr) {
     pen = false;
     V3 lineVec, linePoint;
+    if (au) au->status = ORC_PEN_NO_LINE;
     if (0 != intersection_line(plane1, plane2, lineVec, linePoint)) return -1;
     auto edge_hits = [&](const V3 *c, std::vector<V3> &out) {
         const int num = 4;
@@ -1057,7 +1061,9 @@ int planes_penetrable(const float *plane1, const float *plane2, const V3 *corner
     std::vector<V3> ip1, ip2;
     edge_hits(corners1, ip1);
     edge_hits(corners2, ip2);
+    if (au) au->status = ip1.empty() ? ORC_PEN_NO_HITS : ORC_PEN_HIT_COUNT;
     if (ip1.empty()) { pen = false; return 0; } else if (ip1.size() != 2) return -1;
+    if (au) au->status = ip2.empty() ? ORC_PEN_NO_HITS : ORC_PEN_HIT_COUNT;
     if (ip2.empty()) { pen = false; return 0; } else if (ip2.size() != 2) return -1;
     V3 direc = ip1[1] - ip1[0];
     normalize(direc);
@@ -1065,25 +1071,30 @@ int planes_penetrable(const float *plane1, const float *plane2, const V3 *corner
     LengthIndex lv[4];
     for (int i = 0; i < 4; ++i) { lv[i].length = dot(inter[i] - inter[0], direc); lv[i].index = i; }
     std::sort(lv, lv + 4, cmp_less);
+    if (au) au->status = ORC_PEN_NO_OVERLAP;
     if (0 == (lv[0].index / 2 - lv[1].index / 2)) { pen = false; return 0; }
     V3 startPoint = inter[lv[1].index], endPoint = inter[lv[2].index];
     float length = norm(endPoint - startPoint);
-    float half_r2 = pcl_r2((double)(searchRadius / 2));
-    float full_r2 = pcl_r2((double)searchRadius);
-    auto walk = [&](const std::vector<V3> &ptsA, const GridIndex &gA, const GridIndex &gB, const float *planeB,
-                    int &positiveNum, int &negativeNum) {
-        int skipped;
-        pen_walk(ptsA, gA, gB, planeB, startPoint, direc, length, searchRadius, minDistance, positiveNum, negativeNum, skipped);
-    };
-    (void)half_r2; (void)full_r2;
-    int pos, neg;
-    walk(pts1, g1, g2, plane2, pos, neg);
-    if (pos < minPointsNum || neg < minPointsNum) { pen = false; return 0; }
-    if (double(std::max(pos, neg)) / std::min(pos, neg + 1) > 5) { pen = false; return 0; }
-    walk(pts2, g2, g1, plane1, pos, neg);
-    if (pos < minPointsNum && neg < minPointsNum) { pen = false; return 0; }
-    if (double(std::max(pos, neg)) / std::min(pos, neg + 1) > 5) { pen = false; return 0; }
-    pen = true;
+    int pos[2] = {0, 0}, neg[2] = {0, 0}, skipped[2] = {0, 0};
+    auto ratio_ok = [&](int w) { return !(double(std::max(pos[w], neg[w])) / std::min(pos[w], neg[w] + 1) > 5); };
+    pen_walk(pts1, g1, g2, plane2, startPoint, direc, length, searchRadius, minDistance, pos[0], neg[0], skipped[0]);
+    const bool ok0 = !(pos[0] < minPointsNum || neg[0] < minPointsNum) && ratio_ok(0);
+    bool ok1 = false;
+    if (ok0 || au) {
+        pen_walk(pts2, g2, g1, plane1, startPoint, direc, length, searchRadius, minDistance, pos[1], neg[1], skipped[1]);
+        ok1 = !(pos[1] < minPointsNum && neg[1] < minPointsNum) && ratio_ok(1);
+    }
+    pen = ok0 && ok1;
+    if (au) {
+        au->status = ORC_PEN_WALKED;
+        for (int q = 0; q < 4; ++q) au->plane1[q] = plane1[q];
+        st3(au->start, startPoint); st3(au->direc, direc);
+        au->length = length;
+        au->nsteps = 0;
+        for (float dist = 0; dist < length; dist += searchRadius) au->nsteps++;   // the walks' own loop (pen_walk)
+        for (int w = 0; w < 2; ++w) { au->positive[w] = pos[w]; au->negative[w] = neg[w]; au->skipped[w] = skipped[w]; }
+        au->verdict = pen ? 1 : 0;
+    }
     return 0;
 }
 
@@ -1342,6 +1353,55 @@ int orc_pen_walk(const float *pts_a, int na, const float *pts_b, int nb, const f
     ga.build(A.data(), na, searchRadius > 0 ? searchRadius : 1.f);
     gb.build(B.data(), nb, searchRadius > 0 ? searchRadius : 1.f);
     pen_walk(A, ga, gb, plane_b4, ld3(start3), ld3(direc3), length, searchRadius, minDistance, *positive, *negative, *skipped);
+    return 0;
+}
+
+// Every triple (candidate, source plane, target plane) of the penetration filter's loop (util.cpp:450-519), none skipped:
+// the loop of orc_registration below without its two `break`s, on the filter's own tables.
+int orc_penetration_items(const float *cand, int K, const float *s_coef, const float *s_center, const float *s_four,
+                          const float *s_pts, const int32_t *s_off, int ps, const float *t_coef, const float *t_center,
+                          const float *t_four, const float *t_pts, const int32_t *t_off, int pt, float lengthThreshold,
+                          float angleThreshold, orc_pen_record *records) {
+    std::vector<std::vector<V3>> tds(pt);
+    std::vector<GridIndex> tgrid(pt);
+    for (int j1 = 0; j1 < pt; ++j1) {
+        for (int q = t_off[j1]; q < t_off[j1 + 1]; ++q) tds[j1].push_back(ld3(t_pts + 3 * (size_t)q));
+        tgrid[j1].build(tds[j1].data(), (int)tds[j1].size(), lengthThreshold > 0 ? lengthThreshold : 1.f);
+    }
+    for (int k = 0; k < K; ++k) {
+        const float *c = cand + 12 * (size_t)k;
+        M3 R;
+        for (int r = 0; r < 3; ++r) for (int q = 0; q < 3; ++q) R.m[r][q] = c[3 * r + q];
+        const V3 T = ld3(c + 9);
+        float T16[16];
+        make_T(R, T, T16);
+        for (int i1 = 0; i1 < ps; ++i1) {
+            V3 pn = mul(R, ld3(s_coef + 4 * (size_t)i1));
+            float plane1[4] = {pn.x, pn.y, pn.z, 0};
+            plane1[3] = -(-s_coef[4 * (size_t)i1 + 3] + dot_seq(pn, T));
+            std::vector<V3> tp;
+            for (int q = s_off[i1]; q < s_off[i1 + 1]; ++q) tp.push_back(pcl_transform(T16, ld3(s_pts + 3 * (size_t)q)));
+            V3 four[4], tfour[4];
+            for (int q = 0; q < 4; ++q) four[q] = pcl_transform(T16, ld3(s_four + 12 * (size_t)i1 + 3 * q));
+            GridIndex tg;
+            bool built = false;
+            V3 c2m = mul(R, ld3(s_center + 3 * (size_t)i1)) + T;
+            for (int j1 = 0; j1 < pt; ++j1) {
+                orc_pen_record &rec = records[((size_t)k * ps + i1) * pt + j1];
+                memset(&rec, 0, sizeof(rec));
+                rec.k = k; rec.i1 = i1; rec.j1 = j1; rec.status = ORC_PEN_GATED;
+                V3 plane_A = ld3(t_coef + 4 * (size_t)j1);
+                double c2p = (std::fabs(dot(plane_A, c2m) + t_coef[4 * (size_t)j1 + 3]) +
+                              std::fabs(dot(pn, ld3(t_center + 3 * (size_t)j1)) + plane1[3])) / 2;
+                if (c2p < lengthThreshold && dot(pn, plane_A) > angleThreshold) continue;
+                if (!built) { tg.build(tp.data(), (int)tp.size(), lengthThreshold > 0 ? lengthThreshold : 1.f); built = true; }
+                for (int q = 0; q < 4; ++q) tfour[q] = ld3(t_four + 12 * (size_t)j1 + 3 * q);
+                bool isPen = false;
+                planes_penetrable(plane1, t_coef + 4 * (size_t)j1, four, tfour, tp, tg, tds[j1], tgrid[j1], isPen,
+                                  (float)(double)lengthThreshold, 10, (float)((double)lengthThreshold / 2), &rec);
+            }
+        }
+    }
     return 0;
 }
 
@@ -1657,6 +1717,14 @@ int orc_registration_sampled(orc_reg *h, const float *tgt_pn, int nt, const floa
             }
     }
     h->put("pen_tested", tested.data(), tested.size());
+    {
+        std::vector<float> pc(12 * tested.size());
+        for (size_t i = 0; i < tested.size(); ++i) {
+            for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) pc[12 * i + 3 * r + c] = Rs[tested[i]].m[r][c];
+            st3(&pc[12 * i + 9], Ts[tested[i]]);
+        }
+        h->put("pen_candidates", pc.data(), pc.size());
+    }
     h->put("pen_flags", penflag.data(), penflag.size());
     lap("penetration");
     if (pen_stride > 1 || results.empty()) {   // a sampled run ends here: the verification needs every flag

@@ -70,6 +70,23 @@ void orc_euler_angles(const float *R9, float *rpy3);
 int orc_pen_walk(const float *pts_a, int na, const float *pts_b, int nb, const float *plane_b4, const float *start3,
                  const float *direc3, float length, float searchRadius, float minDistance, int *positive, int *negative,
                  int *skipped);
+/* The penetration filter (util.cpp:450-519) item by item: one record for EVERY triple (candidate k, source plane i1, target
+ * plane j1), at records[(k * ps + i1) * pt + j1], nothing short-circuited.  cand: K x 12 (R row-major, then T); per side coef
+ * P x 4, center P x 3, four P x 12 (the projected rectangle), pts = the per-plane downsampled clouds end to end, off P + 1.
+ * status: where AreTwoPlanesPenetrable (util.cpp:1279-1458) or the gate in front of it (util.cpp:487-492) left the triple.
+ * For ORC_PEN_WALKED: the transformed source plane, the common segment, nsteps = the steps with dist < length, and for walk
+ * 0 (source points against the target plane) and walk 1 (the other way round) positive / negative / skipped steps; BOTH
+ * walks are run, also where the first fails its thresholds.  verdict: the reference's rule (1 = penetrating). */
+enum { ORC_PEN_GATED = 0, ORC_PEN_NO_LINE = 1, ORC_PEN_NO_HITS = 2, ORC_PEN_HIT_COUNT = 3, ORC_PEN_NO_OVERLAP = 4, ORC_PEN_WALKED = 5 };
+typedef struct orc_pen_record {
+    int32_t k, i1, j1, status;
+    float plane1[4], start[3], direc[3], length;
+    int32_t nsteps, positive[2], negative[2], skipped[2], verdict;
+} orc_pen_record;
+int orc_penetration_items(const float *cand, int K, const float *s_coef, const float *s_center, const float *s_four,
+                          const float *s_pts, const int32_t *s_off, int ps, const float *t_coef, const float *t_center,
+                          const float *t_four, const float *t_pts, const int32_t *t_off, int pt, float lengthThreshold,
+                          float angleThreshold, orc_pen_record *records);
 /* closest points of two lines / least-squares point of two lines (util.cpp:1167-1229, 1461-1500): 0 = exact closed form in fp64
  * (default; what the HIP path computes), 1 = "svd_fp32": the reference's cv::solve(DECOMP_SVD) in float, restated from OpenCV 2.4's
  * JacobiSVDImpl_ / SVBkSbImpl_ (lapack.cpp:533-710, 751-812) */

@@ -37,7 +37,13 @@ ABI_SYMBOLS = [
     "plade_m3c2_default_params", "plade_cloud_m3c2", "plade_cloud_m3c2_dev",
     "plade_fpfh_default_params", "plade_cloud_fpfh", "plade_cloud_fpfh_dev", "plade_features_free",
     "plade_feature_match_default_params", "plade_match_features", "plade_match_features_dev",
+    "plade_penetration_filter",
 ]
+
+# plade_pen_item (include/plade_hip.h): one audited item of the penetration filter
+PEN_ITEM = np.dtype([("k", np.uint32), ("i1", np.uint32), ("j1", np.uint32), ("plane1", np.float32, 4), ("start", np.float32, 3),
+                     ("direc", np.float32, 3), ("length", np.float32), ("nsteps", np.int32), ("pos", np.int32, 2),
+                     ("neg", np.int32, 2), ("gated", np.int32, 2), ("verdict", np.int32)])
 
 
 class PladeError(RuntimeError):
@@ -205,6 +211,7 @@ def load_library(path=LIB_PATH):
     sig("plade_extract_planes", argtypes=[p, p, u32, u32, f, f, f, f, p, p, p, u32, p])
     sig("plade_match_descriptors", argtypes=[p, p, u32, p, u32, f, p, p, p, u64, p])
     sig("plade_cluster_transforms", argtypes=[p, p, p, u32, f, f, p, p])
+    sig("plade_penetration_filter", argtypes=[p, p, u32, p, p, p, p, p, u32, p, p, p, p, p, u32, f, f, p, p, u64, p])
     sig("plade_overlap_counts", argtypes=[p, p, u32, p, u32, p, u32, p, f, f, p])
     sig("plade_average_spacing", argtypes=[p, p, u32, u32, u32, u32, p])
     sig("plade_voxel_downsample", argtypes=[p, p, u32, u32, f, p, p])
@@ -302,7 +309,7 @@ DUMP_FIELDS = {
     "tgt_desc": np.float32, "src_desc": np.float32,
     "match_offsets": np.int64, "match_nbr": np.int32, "match_dist2": np.float64,
     "initial_RT": np.float32, "cluster_sizes": np.int32, "cluster_seeds": np.int32,
-    "plane_match_counts": np.int32, "pen_tested": np.int32, "pen_flags": np.int32,
+    "plane_match_counts": np.int32, "pen_tested": np.int32, "pen_flags": np.int32, "pen_candidates": np.float32,
     "candidates": np.float32, "candidate_centers": np.float32, "overlap_counts": np.int32,
     "scores": np.float32, "best_index": np.int32,
     "tgt_planes": np.float32, "tgt_plane_offsets": np.int32, "tgt_plane_idx": np.int32,
@@ -778,6 +785,33 @@ class Context:
         n = C.c_uint32()
         self._check(self.L.plade_cluster_transforms(self.h, _ptr(t), _ptr(e), len(t), dist_threshold, angle_gate, _ptr(out), C.byref(n)))
         return out, n.value
+
+    def penetration_filter(self, cand, src, tgt, length_threshold, angle_threshold, audit=False):
+        """Seam of the penetration filter (util.cpp:450-519).  cand: K x 12 (R row-major, T); src / tgt: (coef P x 4, center P x 3,
+        four P x 12, pts N x 3, off P + 1).  Returns the K flags; with audit=True (flags, items) with one PEN_ITEM record per item
+        that reached the walks, every one evaluated in full."""
+        cand = _f32(cand).reshape(-1, 12)
+        K = len(cand)
+        sides = []
+        for coef, center, four, pts, off in (src, tgt):
+            coef = _f32(coef).reshape(-1, 4)
+            off = np.ascontiguousarray(off, np.uint32)
+            if len(off) != len(coef) + 1:
+                raise ValueError("penetration_filter: off must hold P + 1 offsets")
+            pts = _f32(pts).reshape(-1, 3)
+            if len(pts) < int(off[-1]):
+                raise ValueError("penetration_filter: offsets reach past the plane clouds")
+            sides.append((coef, _f32(center).reshape(len(coef), 3), _f32(four).reshape(len(coef), 12), pts, off))
+        (sc, sce, sf, sp, so), (tc, tce, tf, tp, to) = sides
+        flags = np.zeros(K, np.int32)
+        cap = K * len(sc) * len(tc) if audit else 0
+        items = np.zeros(max(cap, 1), PEN_ITEM) if audit else None
+        n = C.c_uint64()
+        self._check(self.L.plade_penetration_filter(self.h, _ptr(cand), K, _ptr(sc), _ptr(sce), _ptr(sf), _ptr(sp), _ptr(so), len(sc),
+                                                    _ptr(tc), _ptr(tce), _ptr(tf), _ptr(tp), _ptr(to), len(tc),
+                                                    C.c_float(length_threshold), C.c_float(angle_threshold), _ptr(flags),
+                                                    _ptr(items) if audit else None, cap, C.byref(n)))
+        return (flags, items[: n.value].copy()) if audit else flags
 
     def overlap_counts(self, src_ds, tgt_ds, T, centers, src_radius, inlier_dist):
         s, t = _f32(src_ds), _f32(tgt_ds)

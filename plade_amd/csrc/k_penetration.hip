@@ -287,7 +287,7 @@ void build_pen_grid(plade_ctx *ctx, PlaneCloudsDev &pc, const PlaneGeomHost &geo
                            1.f / cell, pc.ckeys.p, pc.cvals.p);
     int bits = 1;
     while ((1ull << bits) < total) ++bits;
-    sort_pairs_u32(ctx, pc.ckeys.p, pc.ckeys2.p, pc.cvals.p, pc.cvals2.p, n, bits);
+    if (n) sort_pairs_u32(ctx, pc.ckeys.p, pc.ckeys2.p, pc.cvals.p, pc.cvals2.p, n, bits);
     launch<k_pen_cell_fill, 256>(ctx, dim3(cdiv(std::max(n, total + 1), 256)), 0, pc.xyz.p, pc.ckeys2.p,
                        pc.cvals2.p, n, total, pc.cell_pts.p, pc.cell_start.p);
     if (!staged) ctx->sync();   // `fr` must outlive the copy
@@ -315,7 +315,9 @@ __device__ __forceinline__ void pen_visit(const PenFrame &f, const float4 *__res
     const int na = major_u ? f.nu : f.nv, nbm = major_u ? f.nv : f.nu;
     const float pad = rr * 1.4143f + 0.02f * cell;   // perpendicular rr seen along the minor axis (slope <= 1) + rounding
     const float amin = fminf(a0, a1) - rr - 0.02f * cell, amax = fmaxf(a0, a1) + rr + 0.02f * cell;
-    const int ca0 = max((int)floorf(amin * inv) + 1, 0), ca1 = min((int)floorf(amax * inv) + 1, na - 1);
+    // a grid stops at 4096 cells per axis (build_pen_grid) and k_pen_cell_keys puts every point beyond into the last cell: a
+    // walk out there starts in that cell too (both ends clamped), and the distance tests decide
+    const int ca0 = min(max((int)floorf(amin * inv) + 1, 0), na - 1), ca1 = min((int)floorf(amax * inv) + 1, na - 1);
     const float da = a1 - a0;
     const float slope = fabsf(da) > 1e-12f ? (b1 - b0) / da : 0.f;
     for (int base = ca0; base <= ca1; base += 64) {          // wave-uniform
@@ -323,11 +325,12 @@ __device__ __forceinline__ void pen_visit(const PenFrame &f, const float4 *__res
         int cb0 = 0, ncell = 0;
         if (ca <= ca1) {
             // the part of the segment (extended by rr at both ends) inside this column
-            float lo = fmaxf((float)(ca - 1) * cell, amin), hi = fminf((float)ca * cell, amax);
+            // (the last column reaches the segment's end, also where it stands for everything beyond the grid)
+            float lo = fmaxf((float)(ca - 1) * cell, amin), hi = ca == ca1 ? amax : fminf((float)ca * cell, amax);
             if (hi < lo) { const float t = lo; lo = hi; hi = t; }
             const float bl = b0 + (lo - a0) * slope, bh = b0 + (hi - a0) * slope;
-            cb0 = max((int)floorf((fminf(bl, bh) - pad) * inv) + 1, 0);
             const int cb1 = min((int)floorf((fmaxf(bl, bh) + pad) * inv) + 1, nbm - 1);
+            cb0 = min(max((int)floorf((fminf(bl, bh) - pad) * inv) + 1, 0), nbm - 1);
             ncell = max(cb1 - cb0 + 1, 0);
         }
         int most = ncell;
@@ -386,11 +389,17 @@ struct PenSide {
 // (util.cpp:1383, fp32 accumulation), PEN_MAXS + 1 entries computed once on the host -- it does not depend
 // on the item.  All distance tests are the reference's arithmetic on the reference's operands (source
 // points moved by the candidate with pcl_xform); the grids only select which points are looked at.
-__device__ void k_pen_walk(const VB &vb, const PenItem *__restrict__ items, const uint32_t *__restrict__ pair_count,
-                                                      const uint32_t *__restrict__ pair_order, PenTables tb,
-                                                      const float *__restrict__ step_dist, PenSide S, PenSide T_, float cell,
-                                                      float search_radius, int min_points, float min_distance,
-                                                      uint32_t *__restrict__ cand_flags, uint32_t *__restrict__ overflow) {
+//
+// AUDIT (plade_penetration_filter with an item buffer): every item is carried to its end -- no early exit on the candidate's
+// flag, pass 1 also behind a failed pass 0 -- and leaves a plade_pen_item in its slot of `audit`.  The production
+// instantiation (AUDIT = false) compiles to what it was without the parameter: `audit` is never read there.
+template <bool AUDIT>
+__device__ __forceinline__ void pen_walk_item(const VB &vb, const PenItem *__restrict__ items, const uint32_t *__restrict__ pair_count,
+                                              const uint32_t *__restrict__ pair_order, const PenTables &tb,
+                                              const float *__restrict__ step_dist, const PenSide &S, const PenSide &T_, float cell,
+                                              float search_radius, int min_points, float min_distance,
+                                              uint32_t *__restrict__ cand_flags, uint32_t *__restrict__ overflow,
+                                              plade_pen_item *__restrict__ audit) {
     __shared__ uint32_t s_cnt_all[PEN_G][PEN_MAXS];
     __shared__ float s_dist[PEN_MAXS + 1];
     const uint32_t pair = pair_order[vb.bx];   // heaviest plane pairs first (longest-processing-time order)
@@ -408,7 +417,18 @@ __device__ void k_pen_walk(const VB &vb, const PenItem *__restrict__ items, cons
     const PenItem it = items[(size_t)pair * tb.K + slot];
     // the verdict per candidate is an OR over its items: once one item has rejected the candidate the
     // others cannot change it
-    if (__atomic_load_n(&cand_flags[it.k], __ATOMIC_RELAXED)) return;
+    if (!AUDIT && __atomic_load_n(&cand_flags[it.k], __ATOMIC_RELAXED)) return;
+    plade_pen_item rec;
+    if (AUDIT) {
+        rec.k = it.k; rec.i1 = it.i1; rec.j1 = it.j1;
+        for (int q = 0; q < 4; ++q) rec.plane1[q] = it.plane1[q];
+        rec.start[0] = it.sx; rec.start[1] = it.sy; rec.start[2] = it.sz;
+        rec.direc[0] = it.dx; rec.direc[1] = it.dy; rec.direc[2] = it.dz;
+        rec.length = it.length;
+        for (int q = 0; q < 2; ++q) rec.pos[q] = rec.neg[q] = rec.gated[q] = 0;
+        rec.nsteps = 0; rec.verdict = 0;
+    }
+    bool verdict = true;
     // number of steps with dist < length (the sequence is increasing)
     int nsteps;
     {
@@ -417,7 +437,10 @@ __device__ void k_pen_walk(const VB &vb, const PenItem *__restrict__ items, cons
         if (lo == PEN_MAXS && s_dist[PEN_MAXS] < it.length && lane == 0) atomicExch(overflow, 1u);
         nsteps = lo;
     }
-    if (nsteps == 0) return;  // length <= 0: both walks see nothing -> positive/negative < minPoints
+    if (nsteps == 0) {        // length <= 0: both walks see nothing -> positive/negative < minPoints
+        if (AUDIT && lane == 0) audit[(size_t)pair * tb.K + slot] = rec;
+        return;
+    }
     const f3 start(it.sx, it.sy, it.sz), direc(it.dx, it.dy, it.dz);
     const float half_r2 = (float)((double)(search_radius / 2) * (double)(search_radius / 2));
     const float full_r2 = (float)((double)search_radius * (double)search_radius);
@@ -454,7 +477,13 @@ __device__ void k_pen_walk(const VB &vb, const PenItem *__restrict__ items, cons
         if (pass == 0) pen_visit(ft, T_.pts, T_.cell_start, start, direc, L, search_radius * 0.5f, cell, lane, gate);
         else pen_visit(fs, S.pts, S.cell_start, start_s, direc_s, L, search_radius * 0.5f, cell, lane, gate);
         __syncwarp();
-        if (__atomic_load_n(&cand_flags[it.k], __ATOMIC_RELAXED)) return;   // rejected by another item meanwhile
+        if (!AUDIT && __atomic_load_n(&cand_flags[it.k], __ATOMIC_RELAXED)) return;   // rejected by another item meanwhile
+        if (AUDIT) {    // steps whose gate found two points
+            int g = 0;
+            for (int i = lane; i < nsteps; i += 64) g += s_cnt[i] >= 2u;
+            for (int dlt = 32; dlt >= 1; dlt >>= 1) g += __shfl_xor(g, dlt, 64);
+            rec.gated[pass] = g;
+        }
         const float pl0 = pass == 0 ? tc[0] : it.plane1[0], pl1 = pass == 0 ? tc[1] : it.plane1[1],
                     pl2 = pass == 0 ? tc[2] : it.plane1[2], pl3 = pass == 0 ? tc[3] : it.plane1[3];
         int pos = 0, neg = 0;
@@ -479,21 +508,48 @@ __device__ void k_pen_walk(const VB &vb, const PenItem *__restrict__ items, cons
         else pen_visit(ft, T_.pts, T_.cell_start, start, direc, L, search_radius, cell, lane, classify);
         for (int dlt = 32; dlt >= 1; dlt >>= 1) { pos += __shfl_xor(pos, dlt, 64); neg += __shfl_xor(neg, dlt, 64); }
         __syncwarp();   // all reads of s_cnt done before the next pass clears it
-        if (pass == 0) {
-            if (pos < min_points || neg < min_points) return;
+        if (!AUDIT) {
+            if (pass == 0) {
+                if (pos < min_points || neg < min_points) return;
+            } else {
+                if (pos < min_points && neg < min_points) return;
+            }
+            if ((double)max(pos, neg) / (double)min(pos, neg + 1) > 5) return;
         } else {
-            if (pos < min_points && neg < min_points) return;
+            rec.pos[pass] = pos; rec.neg[pass] = neg;
+            const bool few = pass == 0 ? (pos < min_points || neg < min_points) : (pos < min_points && neg < min_points);
+            if (few || (double)max(pos, neg) / (double)min(pos, neg + 1) > 5) verdict = false;
         }
-        if ((double)max(pos, neg) / (double)min(pos, neg + 1) > 5) return;
+    }
+    if (AUDIT) {
+        rec.nsteps = nsteps; rec.verdict = verdict ? 1 : 0;
+        if (lane == 0) audit[(size_t)pair * tb.K + slot] = rec;
+        if (!verdict) return;
     }
     if (lane == 0) atomicOr(&cand_flags[it.k], 1u);
+}
+
+__device__ void k_pen_walk(const VB &vb, const PenItem *__restrict__ items, const uint32_t *__restrict__ pair_count,
+                           const uint32_t *__restrict__ pair_order, PenTables tb, const float *__restrict__ step_dist, PenSide S,
+                           PenSide T_, float cell, float search_radius, int min_points, float min_distance,
+                           uint32_t *__restrict__ cand_flags, uint32_t *__restrict__ overflow) {
+    pen_walk_item<false>(vb, items, pair_count, pair_order, tb, step_dist, S, T_, cell, search_radius, min_points, min_distance, cand_flags,
+                         overflow, nullptr);
+}
+__device__ void k_pen_walk_audit(const VB &vb, const PenItem *__restrict__ items, const uint32_t *__restrict__ pair_count,
+                                 const uint32_t *__restrict__ pair_order, PenTables tb, const float *__restrict__ step_dist, PenSide S,
+                                 PenSide T_, float cell, float search_radius, int min_points, float min_distance,
+                                 uint32_t *__restrict__ cand_flags, uint32_t *__restrict__ overflow, plade_pen_item *__restrict__ audit) {
+    pen_walk_item<true>(vb, items, pair_count, pair_order, tb, step_dist, S, T_, cell, search_radius, min_points, min_distance, cand_flags,
+                        overflow, audit);
 }
 
 void penetration_filter(plade_ctx *ctx, const float *cand_rt_host, uint32_t K, const PlaneGeomHost &src,
                         const PlaneGeomHost &tgt, PlaneCloudsDev &src_pts, PlaneCloudsDev &tgt_pts,
                         float length_threshold, float angle_threshold, std::vector<int32_t> &flags_out, const float *cand_rt_dev,
-                        const PenGather *gather) {
+                        const PenGather *gather, std::vector<plade_pen_item> *audit) {
     flags_out.assign(K, 0);
+    if (audit) audit->clear();
     if (!K || !src.P || !tgt.P) {   // (the caller's read-back of the table rides on our wait)
         if (gather && K) {
             uint32_t *d_ids = reinterpret_cast<uint32_t *>(ctx->scratch[4].ensure(4 * (size_t)K + 64));
@@ -571,6 +627,13 @@ void penetration_filter(plade_ctx *ctx, const float *cand_rt_host, uint32_t K, c
     const PenSide sS{src_pts.frames.p, src_pts.cell_pts.p, src_pts.cell_start.p}, sT{tgt_pts.frames.p, tgt_pts.cell_pts.p, tgt_pts.cell_start.p};
     // a plane pair holds at most K items: grid.y covers the worst case, empty groups exit at once
     ctx->ev_begin("pen_walk", 0.0);
+    DBuf<plade_pen_item> d_audit;       // audit only: one slot per item slot, read back whole, the used slots picked below
+    std::vector<plade_pen_item> h_audit;
+    if (audit) {
+        d_audit.ensure(total);
+        launch<k_pen_walk_audit, PEN_TPB, 6>(ctx, dim3(n_pairs, cdiv(K, PEN_G)), 0, d_items, d_pair, d_order, tb, d_steps,
+                           sS, sT, cell, search_radius, 10, min_distance, d_flags, d_over, d_audit.p);
+    } else
     launch<k_pen_walk, PEN_TPB, 6>(ctx, dim3(n_pairs, cdiv(K, PEN_G)), 0, d_items, d_pair, d_order, tb, d_steps,
                        sS, sT, cell, search_radius, 10, min_distance, d_flags, d_over);
     ctx->ev_end();
@@ -578,6 +641,12 @@ void penetration_filter(plade_ctx *ctx, const float *cand_rt_host, uint32_t K, c
     ctx->d2h(out.data(), d_ctr, n_ctr * 4);
     ctx->sync();
     HIP_TRY(hipGetLastError());
+    if (audit) {
+        h_audit.resize(total);
+        HIP_TRY(hipMemcpy(h_audit.data(), d_audit.p, total * sizeof(plade_pen_item), hipMemcpyDeviceToHost));
+        for (uint32_t pr = 0; pr < n_pairs; ++pr)
+            for (uint32_t q = 0; q < out[(size_t)K + 2 + pr]; ++q) audit->push_back(h_audit[(size_t)pr * K + q]);
+    }
     double items = 0;
     for (uint32_t pr = 0; pr < n_pairs; ++pr) items += out[(size_t)K + 2 + pr];
     ctx->stats.add("pen_items", items);
@@ -586,3 +655,59 @@ void penetration_filter(plade_ctx *ctx, const float *cand_rt_host, uint32_t K, c
 }
 
 }  // namespace plade
+
+using namespace plade;
+
+// ---- C ABI: seam of the penetration filter ------------------------------------------------------
+// The filter's own host tables in, the K flags out, through penetration_filter's host-candidate path; with an item buffer
+// also the audit records (k_pen_walk_audit).
+extern "C" int plade_penetration_filter(plade_ctx *ctx, const float *cand, uint32_t K, const float *s_coef, const float *s_center,
+                                        const float *s_four, const float *s_pts, const uint32_t *s_off, uint32_t ps,
+                                        const float *t_coef, const float *t_center, const float *t_four, const float *t_pts,
+                                        const uint32_t *t_off, uint32_t pt, float length_threshold, float angle_threshold,
+                                        int32_t *flags, plade_pen_item *items, uint64_t items_cap, uint64_t *n_items) {
+    return guarded(ctx, [&]() -> int {
+        PLADE_REQUIRE((K == 0 || (cand && flags)) && s_off && t_off && (!items || n_items), PLADE_EINVAL,
+                      "plade_penetration_filter: null argument");
+        PLADE_REQUIRE(length_threshold > 0 && std::isfinite(length_threshold), PLADE_EINVAL,
+                      "plade_penetration_filter: the length threshold must be positive");
+        if (n_items) *n_items = 0;
+        PlaneGeomHost geom[2];
+        PlaneCloudsDev pcl[2];
+        const float *coef[2] = {s_coef, t_coef}, *center[2] = {s_center, t_center}, *four[2] = {s_four, t_four}, *pts[2] = {s_pts, t_pts};
+        const uint32_t *off[2] = {s_off, t_off}, P[2] = {ps, pt};
+        for (int sd = 0; sd < 2; ++sd) {
+            const uint32_t p = P[sd];
+            PLADE_REQUIRE(p == 0 || (coef[sd] && center[sd] && four[sd]), PLADE_EINVAL, "plade_penetration_filter: null plane table");
+            PLADE_REQUIRE(off[sd][0] == 0, PLADE_EINVAL, "plade_penetration_filter: plane offsets must start at 0");
+            for (uint32_t g = 0; g < p; ++g)
+                PLADE_REQUIRE(off[sd][g] <= off[sd][g + 1], PLADE_EINVAL, "plade_penetration_filter: plane offsets must not decrease");
+            const uint32_t n = off[sd][p];
+            PLADE_REQUIRE(n == 0 || pts[sd], PLADE_EINVAL, "plade_penetration_filter: null plane clouds");
+            PlaneGeomHost &g = geom[sd];
+            g.P = p;
+            g.coef.assign(coef[sd], coef[sd] + 4 * (size_t)p);
+            g.center.assign(center[sd], center[sd] + 3 * (size_t)p);
+            g.four.assign(four[sd], four[sd] + 12 * (size_t)p);
+            g.radius.assign(p, 0.f);   // (the filter does not read it)
+            PlaneCloudsDev &c = pcl[sd];
+            c.off.assign(off[sd], off[sd] + p + 1);
+            c.xyz.ensure(3 * (size_t)n + 3);
+            c.d_off.ensure((size_t)p + 1);
+            if (n) HIP_TRY(hipMemcpyAsync(c.xyz.p, pts[sd], 12 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+            HIP_TRY(hipMemcpyAsync(c.d_off.p, off[sd], 4 * ((size_t)p + 1), hipMemcpyHostToDevice, ctx->stream));
+        }
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        std::vector<int32_t> fl;
+        std::vector<plade_pen_item> rec;
+        penetration_filter(ctx, cand, K, geom[0], geom[1], pcl[0], pcl[1], length_threshold, angle_threshold, fl, nullptr, nullptr,
+                           items ? &rec : nullptr);
+        for (uint32_t k = 0; k < K; ++k) flags[k] = fl[k];
+        if (items) {
+            *n_items = rec.size();
+            PLADE_REQUIRE(rec.size() <= items_cap, PLADE_ECAP, "plade_penetration_filter: item buffer too small");
+            if (!rec.empty()) memcpy(items, rec.data(), rec.size() * sizeof(plade_pen_item));
+        }
+        return PLADE_OK;
+    });
+}

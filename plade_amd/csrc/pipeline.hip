@@ -482,6 +482,7 @@ bool run_registration(plade_ctx *ctx, RegistrationWork &W, const CloudDev &tgt, 
         penetration_filter(ctx, nullptr, K, C.geom, M.geom, C.pcl, M.pcl, lengthThreshold, angleThreshold, penflags, W.d_rt12.p, &pg);
     }
     ctx->put("pen_flags", penflags.data(), penflags.size());
+    ctx->put("pen_candidates", rt12.data(), rt12.size());
     // survivors = MatchedResult list (util.cpp:513-517)
     std::vector<uint32_t> surv;
     for (uint32_t i = 0; i < K; ++i) if (!penflags[i]) surv.push_back(i);

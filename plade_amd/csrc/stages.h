@@ -102,8 +102,10 @@ struct PenGather { const uint32_t *ids; std::function<void(const uint32_t *d_ids
 void penetration_filter(plade_ctx *ctx, const float *cand_rt_host /*K x 12: R row-major, T*/, uint32_t K,
                         const PlaneGeomHost &src, const PlaneGeomHost &tgt, PlaneCloudsDev &src_pts,
                         PlaneCloudsDev &tgt_pts, float length_threshold, float angle_threshold,
-                        std::vector<int32_t> &flags_out, const float *cand_rt_dev = nullptr, const PenGather *gather = nullptr);
+                        std::vector<int32_t> &flags_out, const float *cand_rt_dev = nullptr, const PenGather *gather = nullptr,
+                        std::vector<plade_pen_item> *audit = nullptr);
 // cand_rt_dev: the same K x 12 table already on the device (cand_rt_host may then be null: nothing is uploaded)
+// audit: one record per emitted item, plane pair by plane pair; every item is then evaluated in full (k_pen_walk_audit)
 
 // ---- oriented bounding boxes (k_obb.hip; ComputeBoundingBox, util.h:186-248) ---------------------------------
 // Result block (floats): whole cloud = centre(3), pad, radius as a double (2 floats), pad, valid flag;

@@ -800,6 +800,93 @@ int plade_match_features(plade_ctx *ctx, const float *src, uint32_t ns, const fl
 int plade_match_features_dev(plade_ctx *ctx, plade_features *src, plade_features *tgt, const plade_feature_match_params *params,
                              int32_t *nn_out, float *d2_out, int32_t *back_out, int32_t *corr_out, uint64_t cap, uint64_t *n_corr);
 
+/* ---- a rigid pose from feature correspondences: RANSAC with prerejection (no reference counterpart) --------------------------------
+ * Semantics (plade_amd/csrc/corr_pose.h).  Source points (ns rows) and target points (nt rows): fp32 x y z,
+ * `stride` >= 3 floats apart, finite; m correspondences as int32 pairs (s, t), 0 <= s < ns, 0 <= t < nt.  S_m, Q_m: the two points of
+ * correspondence m widened to fp64.  All arithmetic below is fp64 with + - * / sqrt only, no contraction, every dot product
+ * (a_x b_x + a_y b_y) + a_z b_z, so numpy reproduces every step up to the least-squares refit bit for bit.
+ *   sample       base = mix64(seed) (splitmix64's finaliser); for k = 0, 1, 2: z = mix64(base ^ (4 h + k)),
+ *                index = ((z >> 32) * m) >> 32: the triple (a, b, c) of hypothesis h.  status 1 when two of them are equal (no redraw).
+ *   prerejection for the edges (a, b), (b, c), (c, a): ls = sqrt(|S_i - S_j|^2), lt = sqrt(|Q_i - Q_j|^2); status 2 when
+ *                fmin(ls, lt) < edge_similarity * fmax(ls, lt) on any edge.
+ *   transform    per side u = p_b - p_a, v = p_c - p_a, e1 = u / sqrt(u.u), w = u x v, e3 = w / sqrt(w.w), e2 = e3 x e1; status 3
+ *                when sqrt(w.w) is 0 or not finite on either side.  R_ij = (e1t_i e1s_j + e2t_i e2s_j) + e3t_i e3s_j;
+ *                c_s = ((S_a + S_b) + S_c) / 3.0, c_t likewise; t_i = c_t,i - ((R_i0 c_s0 + R_i1 c_s1) + R_i2 c_s2).  status 0:
+ *                the hypothesis is scored.
+ *   score        count_h = the number of m with d2 < inlier_dist * inlier_dist, x'_i = ((R_i0 S_0 + R_i1 S_1) + R_i2 S_2) + t_i,
+ *                d = x' - Q, d2 = (d_x d_x + d_y d_y) + d_z d_z.  Exact integers.
+ *   best         the scored hypothesis with the largest count, ties to the smallest h.  PLADE_EFAIL with T = identity and
+ *                result->failure set when m < 3 (PLADE_CORR_POSE_TOO_FEW), nothing is scored (PLADE_CORR_POSE_NONE_SCORED) or the best
+ *                count is below min_inliers (PLADE_CORR_POSE_FEW_INLIERS).
+ *   refinement   at most refine_iterations times: over the inliers of the current T (in correspondence order, the fixed order of
+ *                the cloud tools' summaries, workgroups of 256) n, sum S, sum Q, the means, then the nine sums
+ *                C_ij = sum (Q - q)_i (S - s)_j; the least-squares rotation of C by Horn's unit quaternion (the eigenvector of the
+ *                largest eigenvalue of the symmetric 4 x 4 matrix N(C), 12 cyclic Jacobi sweeps: a proper rotation by construction),
+ *                t = q - R s.  The new T is accepted when its inlier count is >= the old one (refinements counts these); otherwise
+ *                the old T stays and the loop stops.  It also stops when the flags did not change.
+ *   output       T16: row-major fp32 4 x 4, the fp32 of the fp64 iterate.  result: see the struct; rmse = sqrt(sum d2 / inliers)
+ *                under the final T.  inlier_out (m bytes 0 / 1) and the per-hypothesis test seams triple_out (H x 3 int32),
+ *                status_out (H bytes), count_out (H uint32, 0 unless scored) and T_out (H x 12 doubles, rows of [R | t]; zeros unless
+ *                scored) may each be NULL.
+ * The same input gives the same bits on every run, on every context and from plade_estimate_pose_corr_dev.  Errors: PLADE_EINVAL for
+ * NULL arguments, ns, nt or m = 0, a stride below 3, an index out of range, a non-finite coordinate, inlier_dist not finite or <= 0,
+ * hypotheses outside 1 .. 2^24, edge_similarity outside [0, 1], min_inliers < 3, refine_iterations < 0; the context stays usable.
+ * plade_stats_get then reports corr_pose_build_s, corr_pose_score_s, corr_pose_refine_s (HIP events), corr_pose_scored and
+ * corr_pose_inliers. */
+#define PLADE_CORR_POSE_TOO_FEW 1
+#define PLADE_CORR_POSE_NONE_SCORED 2
+#define PLADE_CORR_POSE_FEW_INLIERS 3
+typedef struct plade_corr_pose_params {
+    double inlier_dist;          /* must be set (> 0), absolute */
+    double edge_similarity;      /* [0, 1]: the prerejection's bound on the ratio of the triangles' edge lengths */
+    uint64_t seed;
+    int32_t hypotheses;          /* 1 .. 2^24 */
+    int32_t min_inliers;         /* >= 3 */
+    int32_t refine_iterations;   /* >= 0 */
+    int32_t reserved;            /* 0 */
+} plade_corr_pose_params;
+typedef struct plade_corr_pose_result {
+    uint32_t hypotheses, scored; /* drawn; with status 0 */
+    uint32_t best_hypothesis, best_count;
+    uint32_t inliers;            /* under the final T */
+    int32_t refinements;         /* accepted refits */
+    int32_t failure;             /* 0 or PLADE_CORR_POSE_* */
+    int32_t reserved;            /* 0 */
+    double rmse, fitness;        /* sqrt(sum d2 / inliers); inliers / m */
+    double T[12];                /* the fp64 iterate T16 is rounded from: 3 rows of [R | t] (the identity's when it failed) */
+} plade_corr_pose_result;
+/* The defaults: inlier_dist = 0 (unset), hypotheses = 65536, edge_similarity = 0.9, min_inliers = 3, refine_iterations = 5, seed = 0.
+ * Needs no GPU. */
+void plade_corr_pose_default_params(plade_corr_pose_params *p);
+int plade_estimate_pose_corr(plade_ctx *ctx, const float *src, uint32_t ns, uint32_t src_stride, const float *tgt, uint32_t nt,
+                             uint32_t tgt_stride, const int32_t *corr, uint64_t m, const plade_corr_pose_params *params, float *T16,
+                             uint8_t *inlier_out, int32_t *triple_out, uint8_t *status_out, uint32_t *count_out, double *T_out,
+                             plade_corr_pose_result *result);
+/* The same on two resident clouds (the list stays a host array): bit-identical results. */
+int plade_estimate_pose_corr_dev(plade_ctx *ctx, plade_cloud *src, plade_cloud *tgt, const int32_t *corr, uint64_t m,
+                                 const plade_corr_pose_params *params, float *T16, uint8_t *inlier_out, int32_t *triple_out,
+                                 uint8_t *status_out, uint32_t *count_out, double *T_out, plade_corr_pose_result *result);
+/* Test seam: one refinement pass without the solve.  T12: 3 rows of [R | t] in fp64; flags_out (m bytes): d2 < inlier_dist^2 under
+ * T12; moments_out: 17 doubles -- n, the mean of S (3), the mean of Q (3), C row-major (9), sum d2 -- over the flagged
+ * correspondences (n = 0: the means are 0 / 0 = NaN, C and sum d2 are 0). */
+int plade_corr_pose_moments(plade_ctx *ctx, const float *src, uint32_t ns, uint32_t src_stride, const float *tgt, uint32_t nt,
+                            uint32_t tgt_stride, const int32_t *corr, uint64_t m, const double *T12, double inlier_dist,
+                            uint8_t *flags_out, double *moments_out);
+/* FPFH of both clouds (rows x y z nx ny nz), their match and the pose from the correspondences in one call, with nothing but the
+ * summaries leaving the device in between: the bits of plade_cloud_fpfh on each cloud, plade_match_features (source -> target) and
+ * plade_estimate_pose_corr chained.  match may be NULL (the defaults).  T16: source -> target, the identity with PLADE_EFAIL when
+ * the pose fails (fewer than 3 correspondences included: PLADE_CORR_POSE_TOO_FEW).  corr_out (or NULL): cap x 2 int32, the first
+ * min(cap, *n_corr) pairs (s, t); n_corr may be NULL.  Errors: those of the three calls. */
+int plade_register_features(plade_ctx *ctx, const float *tgt_pos_nrm, uint32_t n_t, const float *src_pos_nrm, uint32_t n_s,
+                            const plade_fpfh_params *fpfh, const plade_feature_match_params *match, const plade_corr_pose_params *pose,
+                            float *T16, plade_fpfh_summary *src_summary, plade_fpfh_summary *tgt_summary,
+                            plade_corr_pose_result *result, int32_t *corr_out, uint64_t cap, uint64_t *n_corr);
+/* The same on two resident clouds: bit-identical results. */
+int plade_register_features_dev(plade_ctx *ctx, plade_cloud *tgt, plade_cloud *src, const plade_fpfh_params *fpfh,
+                                const plade_feature_match_params *match, const plade_corr_pose_params *pose, float *T16,
+                                plade_fpfh_summary *src_summary, plade_fpfh_summary *tgt_summary, plade_corr_pose_result *result,
+                                int32_t *corr_out, uint64_t cap, uint64_t *n_corr);
+
 /* ---- merging registered clouds: the step a scan-to-scan chain ends with (no reference counterpart) -----------------------------
  * Semantics (plade_amd/csrc/merge.h).  k clouds, 1 <= k <= 16; cloud c: n_c >= 1 rows x y z nx ny nz with
  * finite coordinates (the normals may be NaN); T: k row-major fp32 4 x 4 matrices, cloud c -> the output frame (NULL: identities,

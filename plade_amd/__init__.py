@@ -37,6 +37,8 @@ ABI_SYMBOLS = [
     "plade_m3c2_default_params", "plade_cloud_m3c2", "plade_cloud_m3c2_dev",
     "plade_fpfh_default_params", "plade_cloud_fpfh", "plade_cloud_fpfh_dev", "plade_features_free",
     "plade_feature_match_default_params", "plade_match_features", "plade_match_features_dev",
+    "plade_corr_pose_default_params", "plade_estimate_pose_corr", "plade_estimate_pose_corr_dev", "plade_corr_pose_moments",
+    "plade_register_features", "plade_register_features_dev",
     "plade_penetration_filter",
 ]
 
@@ -164,6 +166,26 @@ class FeatureMatchParams(C.Structure):
     _fields_ = [("mutual", C.c_int32), ("max_ratio", C.c_float)]
 
 
+class CorrPoseParams(C.Structure):
+    """plade_corr_pose_params: inlier_dist (absolute, no default), edge_similarity of the prerejection, seed, hypotheses, min_inliers,
+    refine_iterations."""
+    _fields_ = [("inlier_dist", C.c_double), ("edge_similarity", C.c_double), ("seed", C.c_uint64), ("hypotheses", C.c_int32),
+                ("min_inliers", C.c_int32), ("refine_iterations", C.c_int32), ("reserved", C.c_int32)]
+
+
+class CorrPoseResult(C.Structure):
+    """plade_corr_pose_result: hypotheses drawn and scored, the best one and its count, inliers / rmse / fitness under the final T,
+    refinements (accepted refits), failure (0 or PLADE_CORR_POSE_*)."""
+    _fields_ = [("hypotheses", C.c_uint32), ("scored", C.c_uint32), ("best_hypothesis", C.c_uint32), ("best_count", C.c_uint32),
+                ("inliers", C.c_uint32), ("refinements", C.c_int32), ("failure", C.c_int32), ("reserved", C.c_int32),
+                ("rmse", C.c_double), ("fitness", C.c_double), ("T", C.c_double * 12)]
+
+
+PLADE_CORR_POSE_TOO_FEW, PLADE_CORR_POSE_NONE_SCORED, PLADE_CORR_POSE_FEW_INLIERS = 1, 2, 3
+CORR_POSE_FAILURES = {0: None, PLADE_CORR_POSE_TOO_FEW: "fewer than 3 correspondences", PLADE_CORR_POSE_NONE_SCORED: "nothing scored",
+                      PLADE_CORR_POSE_FEW_INLIERS: "too few inliers"}
+CORR_MOMENTS = 17    # corr_pose.h: n, mean S (3), mean Q (3), C (9), sum d2
+
 FPFH_DIM = 33
 FEAT_CHUNK = 512     # fpfh.h: the smallest number of targets one workgroup of the match takes
 
@@ -266,6 +288,17 @@ def load_library(path=LIB_PATH):
     sig("plade_match_features", argtypes=[p, p, u32, p, u32, C.POINTER(FeatureMatchParams), p, p, p, p, C.c_uint64,
                                           C.POINTER(C.c_uint64)])
     sig("plade_match_features_dev", argtypes=[p, p, p, C.POINTER(FeatureMatchParams), p, p, p, p, C.c_uint64, C.POINTER(C.c_uint64)])
+    sig("plade_corr_pose_default_params", argtypes=[C.POINTER(CorrPoseParams)], restype=None)
+    sig("plade_estimate_pose_corr", argtypes=[p, p, u32, u32, p, u32, u32, p, u64, C.POINTER(CorrPoseParams), p, p, p, p, p, p,
+                                              C.POINTER(CorrPoseResult)])
+    sig("plade_estimate_pose_corr_dev", argtypes=[p, p, p, p, u64, C.POINTER(CorrPoseParams), p, p, p, p, p, p, C.POINTER(CorrPoseResult)])
+    sig("plade_corr_pose_moments", argtypes=[p, p, u32, u32, p, u32, u32, p, u64, p, C.c_double, p, p])
+    sig("plade_register_features", argtypes=[p, p, u32, p, u32, C.POINTER(FpfhParams), C.POINTER(FeatureMatchParams),
+                                             C.POINTER(CorrPoseParams), p, C.POINTER(FpfhSummary), C.POINTER(FpfhSummary),
+                                             C.POINTER(CorrPoseResult), p, u64, C.POINTER(u64)])
+    sig("plade_register_features_dev", argtypes=[p, p, p, C.POINTER(FpfhParams), C.POINTER(FeatureMatchParams),
+                                                 C.POINTER(CorrPoseParams), p, C.POINTER(FpfhSummary), C.POINTER(FpfhSummary),
+                                                 C.POINTER(CorrPoseResult), p, u64, C.POINTER(u64)])
     sig("plade_sort_segments", argtypes=[p, p, p, p, u32, C.c_int, p, p])
     sig("plade_set_candidate_shard", argtypes=[p, u32, u32, u32, EXCHANGE_FN, p])
     sig("plade_registration_minsupport", argtypes=[p, p, u32, p, u32, i32, i32, p])
@@ -449,6 +482,40 @@ def feature_match_default_params():
     prm = FeatureMatchParams()
     load_library().plade_feature_match_default_params(C.byref(prm))
     return {k: getattr(prm, k) for k, _ in FeatureMatchParams._fields_}
+
+
+def corr_pose_default_params():
+    """plade_corr_pose_default_params (pure: needs no GPU) as a dict of the plade_corr_pose_params fields."""
+    prm = CorrPoseParams()
+    load_library().plade_corr_pose_default_params(C.byref(prm))
+    return {k: getattr(prm, k) for k, _ in CorrPoseParams._fields_ if k != "reserved"}
+
+
+def _corr_pose_params(inlier_dist, kw):
+    prm = CorrPoseParams()
+    load_library().plade_corr_pose_default_params(C.byref(prm))
+    prm.inlier_dist = float(inlier_dist)
+    known = {k for k, _ in CorrPoseParams._fields_} - {"reserved", "inlier_dist"}
+    for k, v in kw.items():
+        if k not in known:
+            raise TypeError(f"unknown pose parameter {k!r} (known: {sorted(known)})")
+        if v is not None:
+            setattr(prm, k, v)
+    return prm
+
+
+def _corr_pose_info(res):
+    """the fields of a plade_corr_pose_result as a dict; its T as the (3, 4) float64 array T64"""
+    info = {k: getattr(res, k) for k, _ in CorrPoseResult._fields_ if k not in ("reserved", "T")}
+    info["T64"] = np.array(res.T[:], np.float64).reshape(3, 4)
+    return info
+
+
+def _corr_list(corr, what):
+    c = _i32(corr)
+    if c.ndim != 2 or c.shape[1] != 2:
+        raise ValueError(f"{what}: an (M, 2) int32 array of (source, target) indices is required, got shape {c.shape}")
+    return c
 
 
 def _fpfh_params(radius, min_pairs):
@@ -1344,6 +1411,87 @@ class Context:
         """plade_match_features_dev: match_features on two resident tables (fpfh_dev(..., resident=True)); bit-identical results."""
         return self._match_features(lambda prm, *out: self.L.plade_match_features_dev(self.h, src_features.h, tgt_features.h, prm, *out),
                                     src_features.n, tgt_features.n, mutual, max_ratio, cap)
+
+    # ---- a pose from correspondences (RANSAC), and FPFH -> match -> pose in one call -------------------------------
+    def _estimate_pose(self, call, m, inlier_dist, seams, pose_params):
+        prm = _corr_pose_params(inlier_dist, pose_params)
+        H = max(int(prm.hypotheses), 1)
+        T = np.empty((4, 4), np.float32)
+        inlier = np.zeros(m, np.uint8)
+        triple = np.empty((H, 3), np.int32) if seams else None
+        status = np.empty(H, np.uint8) if seams else None
+        count = np.empty(H, np.uint32) if seams else None
+        Th = np.empty((H, 3, 4), np.float64) if seams else None
+        res = CorrPoseResult()
+        rc = self._check(call(C.byref(prm), _ptr(T), _ptr(inlier), _ptr(triple), _ptr(status), _ptr(count), _ptr(Th), C.byref(res)),
+                         allow=(PLADE_EFAIL,))
+        info = _corr_pose_info(res)
+        info.update(ok=rc == 0, reason=CORR_POSE_FAILURES.get(res.failure), inlier=inlier.view(np.bool_))
+        if seams and not (rc != 0 and res.failure == PLADE_CORR_POSE_TOO_FEW):
+            info.update(triple=triple, status=status, count=count, hyp_T=Th)
+        return T, info
+
+    def estimate_pose(self, src_xyz, tgt_xyz, corr, inlier_dist, seams=False, **pose_params):
+        """plade_estimate_pose_corr: the rigid source -> target pose from M correspondences (an (M, 2) int32 array of (source,
+        target) rows into the two (N, >= 3) float32 arrays) by RANSAC over triples with an edge-length prerejection, an exhaustive
+        inlier count (d < inlier_dist) and a least-squares refit.  pose_params: hypotheses, edge_similarity, min_inliers,
+        refine_iterations, seed.  Returns (T, info): T (4, 4) float32 (the identity when it failed), info = the
+        plade_corr_pose_result fields plus ok, reason (None, "fewer than 3 correspondences", "nothing scored", "too few inliers"),
+        inlier (M bools) and -- with seams -- per hypothesis triple (H, 3), status (H), count (H) and hyp_T (H, 3, 4) float64; T64: the (3, 4) float64 iterate T is rounded from."""
+        s, ns, ss = _xyz_view(src_xyz)
+        t, nt, ts = _xyz_view(tgt_xyz)
+        c = _corr_list(corr, "estimate_pose")
+        return self._estimate_pose(lambda prm, *out: self.L.plade_estimate_pose_corr(self.h, _ptr(s), ns, ss, _ptr(t), nt, ts, _ptr(c),
+                                                                                     len(c), prm, *out), len(c), inlier_dist, seams,
+                                   pose_params)
+
+    def estimate_pose_dev(self, src_cloud, tgt_cloud, corr, inlier_dist, seams=False, **pose_params):
+        """plade_estimate_pose_corr_dev: estimate_pose on two resident clouds; bit-identical results."""
+        c = _corr_list(corr, "estimate_pose_dev")
+        return self._estimate_pose(lambda prm, *out: self.L.plade_estimate_pose_corr_dev(self.h, src_cloud.h, tgt_cloud.h, _ptr(c), len(c),
+                                                                                         prm, *out), len(c), inlier_dist, seams, pose_params)
+
+    def corr_pose_moments(self, src_xyz, tgt_xyz, corr, T, inlier_dist):
+        """plade_corr_pose_moments (test seam): one refinement pass without the solve under the fp64 T (3 x 4 or 4 x 4).  Returns
+        (flags, moments): flags (M bools), moments (17,) float64 = n, mean S, mean Q, C row-major, sum d2 over the flagged."""
+        s, ns, ss = _xyz_view(src_xyz)
+        t, nt, ts = _xyz_view(tgt_xyz)
+        c = _corr_list(corr, "corr_pose_moments")
+        T12 = np.ascontiguousarray(np.asarray(T, dtype=np.float64)[:3, :4])
+        flags = np.zeros(len(c), np.uint8)
+        mom = np.empty(CORR_MOMENTS, np.float64)
+        self._check(self.L.plade_corr_pose_moments(self.h, _ptr(s), ns, ss, _ptr(t), nt, ts, _ptr(c), len(c), _ptr(T12),
+                                                   float(inlier_dist), _ptr(flags), _ptr(mom)))
+        return flags.view(np.bool_), mom
+
+    def _register_features(self, call, ns, radius, inlier_dist, min_pairs, mutual, max_ratio, pose_params):
+        fp, mp, pp = _fpfh_params(radius, min_pairs), _feature_match_params(mutual, max_ratio), _corr_pose_params(inlier_dist, pose_params)
+        T = np.empty((4, 4), np.float32)
+        s_src, s_tgt, res = FpfhSummary(), FpfhSummary(), CorrPoseResult()
+        corr = np.empty((max(ns, 1), 2), np.int32)
+        total = C.c_uint64()
+        rc = self._check(call(C.byref(fp), C.byref(mp), C.byref(pp), _ptr(T), C.byref(s_src), C.byref(s_tgt), C.byref(res), _ptr(corr), ns,
+                              C.byref(total)), allow=(PLADE_EFAIL,))
+        info = _corr_pose_info(res)
+        info.update(ok=rc == 0, reason=CORR_POSE_FAILURES.get(res.failure), n_corr=total.value, corr=corr[:total.value].copy(),
+                    fpfh_src={k: getattr(s_src, k) for k, _ in FpfhSummary._fields_ if k != "reserved"},
+                    fpfh_tgt={k: getattr(s_tgt, k) for k, _ in FpfhSummary._fields_ if k != "reserved"})
+        return T, info
+
+    def register_features(self, tgt, src, radius, inlier_dist, min_pairs=None, mutual=True, max_ratio=0.0, **pose_params):
+        """plade_register_features: FPFH of both (N, 6) clouds at `radius`, their match and the pose from the correspondences in one
+        call, with nothing leaving the device in between; the bits of fpfh, match_features and estimate_pose chained.  Returns
+        (T, info): T the 4 x 4 source -> target pose (the identity when it failed), info = the pose result's fields plus ok, reason,
+        n_corr, corr ((n_corr, 2) int32) and the two FPFH summaries fpfh_src, fpfh_tgt."""
+        tgt, src = _f32(tgt), _f32(src)
+        self._check_cloud(tgt, "register_features"); self._check_cloud(src, "register_features")
+        return self._register_features(lambda *a: self.L.plade_register_features(self.h, _ptr(tgt), len(tgt), _ptr(src), len(src), *a),
+                                       len(src), radius, inlier_dist, min_pairs, mutual, max_ratio, pose_params)
+
+    def register_features_dev(self, tgt_cloud, src_cloud, radius, inlier_dist, min_pairs=None, mutual=True, max_ratio=0.0, **pose_params):
+        """plade_register_features_dev: register_features on two resident clouds; bit-identical results."""
+        return self._register_features(lambda *a: self.L.plade_register_features_dev(self.h, tgt_cloud.h, src_cloud.h, *a), src_cloud.n,
+                                       radius, inlier_dist, min_pairs, mutual, max_ratio, pose_params)
 
     # ---- merging registered clouds ---------------------------------------------------------------
     @staticmethod

@@ -66,6 +66,14 @@ HD float flann_d2(f3 q, f3 p) {
 // pcl::KdTreeFLANN::radiusSearch squared radius (kdtree_flann.hpp:193)
 inline float pcl_r2(double radius) { return static_cast<float>(radius * radius); }
 
+// the splitmix64 finaliser behind every random draw of the library (the shape sampler of ransac.hip, the triples of k_corr_pose.hip)
+HD uint64_t mix64(uint64_t z) {
+    z += 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
 // ---------------------------------------------------------------------------
 struct Err {
     int code;

@@ -60,3 +60,13 @@ struct plade_features {
     plade::DBuf<float> desc;
     uint32_t n = 0;
 };
+
+namespace plade {
+// The steps plade_register_features chains (k_corr_pose.hip), device to device: the descriptors of n device rows x y z nx ny nz with
+// a known bounding box into `out` (grow-only; the bits of plade_cloud_fpfh), and the match of two such tables -- returns the device
+// list of the kept (s, t) pairs (valid until the context's next match) and their number (the bits of plade_match_features).
+void fpfh_table_dev(plade_ctx *ctx, const float *d_rows, uint32_t n, const float bbmin[3], const float bbmax[3],
+                    const plade_fpfh_params &p, plade_features &out, plade_fpfh_summary *summary);
+const int32_t *feature_corr_dev(plade_ctx *ctx, const plade_features &src, const plade_features &tgt, const plade_feature_match_params &p,
+                                uint64_t *n_corr);
+}  // namespace plade

@@ -474,6 +474,26 @@ FpfhWork &work_of(plade_ctx *ctx) {
 }
 
 }  // namespace
+
+// ---- the two steps as plade_register_features chains them (k_corr_pose.hip): nothing leaves the device but the summaries -------
+void fpfh_table_dev(plade_ctx *ctx, const float *d_rows, uint32_t n, const float bbmin[3], const float bbmax[3],
+                    const plade_fpfh_params &p, plade_features &out, plade_fpfh_summary *summary) {
+    check_params(n, p);
+    FpfhWork &W = work_of(ctx);
+    const Outputs none = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    fpfh_dev(ctx, W, d_rows, n, 6, bbmin, bbmax, p, none, summary);
+    out.n = n;
+    out.desc.ensure((size_t)n * FPFH_DIM + 4);
+    HIP_TRY(hipMemcpyAsync(out.desc.p, W.desc.p, (size_t)n * FPFH_DIM * 4, hipMemcpyDeviceToDevice, ctx->stream));
+}
+const int32_t *feature_corr_dev(plade_ctx *ctx, const plade_features &src, const plade_features &tgt, const plade_feature_match_params &p,
+                                uint64_t *n_corr) {
+    check_match(p, src.n, tgt.n);
+    FpfhWork &W = work_of(ctx);
+    match_dev(ctx, W, src.desc.p, src.n, tgt.desc.p, tgt.n, p, nullptr, nullptr, nullptr, nullptr, 0, n_corr);
+    return W.corr.p;
+}
+
 }  // namespace plade
 
 using namespace plade;

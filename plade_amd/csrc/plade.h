@@ -165,6 +165,32 @@ bool describe_cloud(pcl::PointCloud<pcl::PointNormal>::Ptr cloud, double radius,
 bool match_features(const std::vector<float> &source_features, const std::vector<float> &target_features,
                     std::vector<std::pair<int, int>> &correspondences, bool mutual = true, float max_ratio = 0.f);
 
+/** A pose from correspondences (no counterpart in the reference): the fields of plade_corr_pose_result (include/plade_hip.h). */
+struct PoseEstimate {
+    uint64_t correspondences = 0;                                   // the list's length
+    uint32_t hypotheses = 0, scored = 0;                            // drawn; those that passed the prerejection
+    uint32_t best_hypothesis = 0, best_count = 0, inliers = 0;      // the winner, its count, the inliers of the refitted pose
+    int refinements = 0;                                            // accepted least-squares refits
+    double rmse = 0, fitness = 0;                                   // over the inliers; inliers / correspondences
+};
+/** The rigid source -> target pose from (source point, target point) correspondences on the GPU (plade_estimate_pose_corr): RANSAC
+ *  over triples with an edge-length prerejection, an exhaustive count of the correspondences closer than inlier_dist (absolute) per
+ *  surviving hypothesis, and a least-squares refit of the best one.  false: invalid input, no GPU, or no pose with min_inliers
+ *  inliers; a message is printed, `transformation` and `info` are unchanged. */
+bool estimate_pose_from_correspondences(Eigen::Matrix4f &transformation, pcl::PointCloud<pcl::PointNormal>::Ptr target_cloud,
+                                        pcl::PointCloud<pcl::PointNormal>::Ptr source_cloud,
+                                        const std::vector<std::pair<int, int>> &correspondences, double inlier_dist,
+                                        PoseEstimate *info = nullptr, int min_inliers = 3, int hypotheses = 65536, uint64_t seed = 0);
+/** Registers a pair that has no planes from its features, in one call on the GPU (plade_register_features): describe_cloud of both
+ *  clouds at `radius`, their mutual match and estimate_pose_from_correspondences at inlier_dist, with the same bits as the three
+ *  calls chained.  `correspondences` (optional) receives the matched pairs.  false as above, with every output unchanged.  The CLI
+ *  does this for the pairs whose plane registration failed when PLADE_FEATURE_REGISTER=<radius>,<inlier_dist>[,<min_inliers>
+ *  [,<hypotheses>]] is set. */
+bool register_by_features(Eigen::Matrix4f &transformation, pcl::PointCloud<pcl::PointNormal>::Ptr target_cloud,
+                          pcl::PointCloud<pcl::PointNormal>::Ptr source_cloud, double radius, double inlier_dist,
+                          PoseEstimate *info = nullptr, std::vector<std::pair<int, int>> *correspondences = nullptr, int min_inliers = 3,
+                          int hypotheses = 65536, int min_pairs = 5, uint64_t seed = 0);
+
 /** Merging registered clouds (no counterpart in the reference): the fields of plade_merge_summary (include/plade_hip.h). */
 struct CloudMerge {
     uint64_t n_in = 0, n_out = 0, n_shared = 0;   // points in, rows out, rows to which two or more clouds contributed

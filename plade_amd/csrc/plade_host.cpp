@@ -432,6 +432,90 @@ void fpfh_line(plade_ctx *ctx, const float *T16, const float *tg, size_t n_t, co
     con_out() << b << std::endl;
 }
 
+// PLADE_FEATURE_REGISTER=<radius>,<inlier_dist>[,<min_inliers>[,<hypotheses>]] (opt-in, absolute, in the clouds' units): a pair whose
+// plane registration failed goes through plade_register_features -- FPFH of both clouds at <radius>, their mutual match and the
+// RANSAC pose over the correspondences at <inlier_dist> (min_inliers 3 and 65 536 hypotheses when not given).  On success one console
+// line reports the inliers, and the pair is from there on a registered pair: its matrix is written and PLADE_REFINE_ICP / GICP /
+// EVALUATE / M3C2 / FPFH_MATCH / MERGE apply.  On failure the failure path runs as before, plus one line saying that the features
+// did not register the pair either.  A value that does not parse (radius or inlier_dist not positive and finite, min_inliers not an
+// integer >= 3, hypotheses not in 1 .. 2^24, anything behind them) prints one warning and does nothing; unset, nothing changes.
+struct FeatureRegisterSwitch { bool on = false; double radius = 0.0, inlier_dist = 0.0; int min_inliers = 3, hypotheses = 65536; };
+const FeatureRegisterSwitch &feature_register_switch() {
+    static const FeatureRegisterSwitch sw = [] {
+        FeatureRegisterSwitch v, off;
+        const char *w = getenv("PLADE_FEATURE_REGISTER");
+        if (!w) return off;
+        char *end = nullptr;
+        v.radius = strtod(w, &end);
+        const float rf = (float)v.radius;
+        bool ok = end != w && std::isfinite(v.radius) && rf > 0.f && std::isfinite(rf * rf) && rf * rf >= FLT_MIN && *end == ',';
+        if (ok) {
+            const char *a = end + 1;
+            v.inlier_dist = strtod(a, &end);
+            ok = end != a && std::isfinite(v.inlier_dist) && v.inlier_dist > 0.0 && std::isfinite(v.inlier_dist * v.inlier_dist) &&
+                 v.inlier_dist * v.inlier_dist > 0.0;
+            if (ok && *end == ',') {
+                a = end + 1;
+                const long m = strtol(a, &end, 10);
+                ok = end != a && m >= 3 && m <= INT32_MAX;
+                v.min_inliers = (int)m;
+                if (ok && *end == ',') {
+                    a = end + 1;
+                    const long h = strtol(a, &end, 10);
+                    ok = end != a && h >= 1 && h <= (1L << 24);
+                    v.hypotheses = (int)h;
+                }
+            }
+        }
+        if (!ok || *end != '\0') {
+            std::cerr << "warning: PLADE_FEATURE_REGISTER=" << w
+                      << " is not <radius>,<inlier_dist>[,<min_inliers>[,<hypotheses>]] with radius > 0, inlier_dist > 0, min_inliers >= 3"
+                         " and 1 <= hypotheses <= 16777216; no feature registration"
+                      << std::endl;
+            return off;
+        }
+        v.on = true;
+        return v;
+    }();
+    return sw;
+}
+// FPFH, match and pose of a packed pair in one call.  rc: the library's status (PLADE_EFAIL: the pose failed, T16 = identity)
+int register_features_packed(plade_ctx *ctx, float *T16, const float *tg, size_t n_t, const float *sr, size_t n_s, double radius,
+                             int min_pairs, double inlier_dist, int min_inliers, int hypotheses, uint64_t seed,
+                             plade_corr_pose_result &res, std::vector<int32_t> *corr, uint64_t &m) {
+    plade_fpfh_params fp;
+    plade_fpfh_default_params(&fp);
+    fp.radius = radius; fp.min_pairs = min_pairs;
+    plade_corr_pose_params pp;
+    plade_corr_pose_default_params(&pp);
+    pp.inlier_dist = inlier_dist; pp.min_inliers = min_inliers; pp.hypotheses = hypotheses; pp.seed = seed;
+    plade_fpfh_summary ss, st;
+    if (corr) corr->resize(2 * n_s);
+    trace("feature registration: describing, matching, estimating");
+    const int rc = plade_register_features(ctx, tg, (uint32_t)n_t, sr, (uint32_t)n_s, &fp, nullptr, &pp, T16, &ss, &st, &res,
+                                           corr ? corr->data() : nullptr, n_s, &m);
+    trace("feature registration: done");
+    if (corr) corr->resize(rc == PLADE_OK || rc == PLADE_EFAIL ? 2 * (size_t)m : 0);
+    return rc;
+}
+// the second chance of a pair without planes; true: T16 holds the pose and the pair counts as registered
+bool feature_register(plade_ctx *ctx, float *T16, const float *tg, size_t n_t, const float *sr, size_t n_s) {
+    const FeatureRegisterSwitch &sw = feature_register_switch();
+    if (!sw.on || !ctx) return false;
+    plade_corr_pose_result res;
+    uint64_t m = 0;
+    const int rc = register_features_packed(ctx, T16, tg, n_t, sr, n_s, sw.radius, 5, sw.inlier_dist, sw.min_inliers, sw.hypotheses, 0, res,
+                                            nullptr, m);
+    if (rc != PLADE_OK) {
+        con_err() << "feature registration failed as well: " << plade_last_error(ctx) << std::endl;
+        return false;
+    }
+    char b[200];
+    snprintf(b, sizeof(b), "feature registration: %u of %llu correspondences, rmse %.6g", res.inliers, (unsigned long long)m, res.rmse);
+    con_out() << b << std::endl;
+    return true;
+}
+
 // PLADE_REMOVE_OUTLIERS=<k>[,<alpha>] (opt-in, 0 / unset = off): both clouds of a pair pass the statistical outlier filter on the
 // GPU (plade_filter_outliers: k nearest neighbours, threshold mu + alpha sigma, alpha 1 when not given) after they are read and
 // before PLADE_ESTIMATE_NORMALS; one console line per cloud.  A value that does not parse (k not an integer in [1, 64], alpha
@@ -812,10 +896,11 @@ bool register_packed(Eigen::Matrix<float, 4, 4> &transformation, const float *tg
     int rc = plade_registration(ctx, tg, (uint32_t)n_t, sr, (uint32_t)n_s, T16);
     if (rc != PLADE_OK) {
         con_err() << plade_last_error(ctx) << std::endl;
-        fpfh_line(ctx, nullptr, tg, n_t, sr, n_s);
-        return false;
-    }
-    con_out() << "done. time: " << w.str() << std::endl;
+        if (!feature_register(ctx, T16, tg, n_t, sr, n_s)) {      // (PLADE_FEATURE_REGISTER: a pair without planes)
+            fpfh_line(ctx, nullptr, tg, n_t, sr, n_s);
+            return false;
+        }
+    } else con_out() << "done. time: " << w.str() << std::endl;
     refine_selected(ctx, T16, tg, n_t, sr, n_s);
     if (evaluate_dist() > 0.f) evaluate_line(ctx, T16, tg, n_t, sr, n_s);
     m3c2_line(ctx, T16, tg, n_t, sr, n_s);
@@ -981,11 +1066,12 @@ void registration_group(size_t count, Eigen::Matrix<float, 4, 4> *transformation
         if (rc != PLADE_OK || status[q] != PLADE_OK) {
             const plade_ctx *pc = ctx ? (rc != PLADE_OK ? ctx : plade_pair_ctx(ctx, q)) : nullptr;
             if (pc) con_err() << plade_last_error(pc) << std::endl;
-            fpfh_line(ctx, nullptr, it.tg, it.n_t, it.sr, it.n_s);
-            con_err() << "registration failed" << std::endl;
-            continue;
-        }
-        con_out() << "done. time: " << w.str() << std::endl;
+            if (!feature_register(ctx, T16 + 16 * q, it.tg, it.n_t, it.sr, it.n_s)) {
+                fpfh_line(ctx, nullptr, it.tg, it.n_t, it.sr, it.n_s);
+                con_err() << "registration failed" << std::endl;
+                continue;
+            }
+        } else con_out() << "done. time: " << w.str() << std::endl;
         refine_selected(ctx, T16 + 16 * q, it.tg, it.n_t, it.sr, it.n_s);
         if (evaluate_dist() > 0.f) evaluate_line(ctx, T16 + 16 * q, it.tg, it.n_t, it.sr, it.n_s);
         m3c2_line(ctx, T16 + 16 * q, it.tg, it.n_t, it.sr, it.n_s);
@@ -1144,6 +1230,67 @@ bool match_features(const std::vector<float> &source_features, const std::vector
     std::vector<std::pair<int, int>> out(corr.size() / 2);
     for (size_t k = 0; k < out.size(); ++k) out[k] = {corr[2 * k], corr[2 * k + 1]};
     correspondences.swap(out);
+    return true;
+}
+
+// the pose from correspondences, and FPFH -> match -> pose in one call: see plade.h
+namespace {
+void fill_pose_estimate(PoseEstimate *info, const plade_corr_pose_result &r, uint64_t m) {
+    if (!info) return;
+    info->correspondences = m;
+    info->hypotheses = r.hypotheses; info->scored = r.scored; info->best_hypothesis = r.best_hypothesis; info->best_count = r.best_count;
+    info->inliers = r.inliers; info->refinements = r.refinements; info->rmse = r.rmse; info->fitness = r.fitness;
+}
+}  // namespace
+bool estimate_pose_from_correspondences(Eigen::Matrix4f &transformation, pcl::PointCloud<pcl::PointNormal>::Ptr target_cloud,
+                                        pcl::PointCloud<pcl::PointNormal>::Ptr source_cloud,
+                                        const std::vector<std::pair<int, int>> &correspondences, double inlier_dist, PoseEstimate *info,
+                                        int min_inliers, int hypotheses, uint64_t seed) {
+    plade_ctx *ctx = context();
+    if (!ctx) return false;
+    if (!target_cloud || !source_cloud) { con_err() << "estimate_pose_from_correspondences: null cloud" << std::endl; return false; }
+    std::vector<float> tg = flatten(*target_cloud), sr = flatten(*source_cloud);
+    std::vector<int32_t> corr(2 * correspondences.size());
+    for (size_t k = 0; k < correspondences.size(); ++k) { corr[2 * k] = correspondences[k].first; corr[2 * k + 1] = correspondences[k].second; }
+    plade_corr_pose_params pp;
+    plade_corr_pose_default_params(&pp);
+    pp.inlier_dist = inlier_dist; pp.min_inliers = min_inliers; pp.hypotheses = hypotheses; pp.seed = seed;
+    plade_corr_pose_result res;
+    float T16[16];
+    const int rc = plade_estimate_pose_corr(ctx, sr.data(), (uint32_t)source_cloud->size(), 6, tg.data(), (uint32_t)target_cloud->size(), 6,
+                                            corr.data(), correspondences.size(), &pp, T16, nullptr, nullptr, nullptr, nullptr, nullptr, &res);
+    if (rc != PLADE_OK) {
+        con_err() << "pose estimation failed: " << plade_last_error(ctx) << std::endl;
+        return false;
+    }
+    to_matrix(T16, transformation);
+    fill_pose_estimate(info, res, correspondences.size());
+    return true;
+}
+bool register_by_features(Eigen::Matrix4f &transformation, pcl::PointCloud<pcl::PointNormal>::Ptr target_cloud,
+                          pcl::PointCloud<pcl::PointNormal>::Ptr source_cloud, double radius, double inlier_dist, PoseEstimate *info,
+                          std::vector<std::pair<int, int>> *correspondences, int min_inliers, int hypotheses, int min_pairs, uint64_t seed) {
+    plade_ctx *ctx = context();
+    if (!ctx) return false;
+    if (!target_cloud || !source_cloud) { con_err() << "register_by_features: null cloud" << std::endl; return false; }
+    std::vector<float> tg = flatten(*target_cloud), sr = flatten(*source_cloud);
+    plade_corr_pose_result res;
+    std::vector<int32_t> corr;
+    uint64_t m = 0;
+    float T16[16];
+    const int rc = register_features_packed(ctx, T16, tg.data(), target_cloud->size(), sr.data(), source_cloud->size(), radius, min_pairs,
+                                            inlier_dist, min_inliers, hypotheses, seed, res, correspondences ? &corr : nullptr, m);
+    if (rc != PLADE_OK) {
+        con_err() << "feature registration failed: " << plade_last_error(ctx) << std::endl;
+        return false;
+    }
+    to_matrix(T16, transformation);
+    fill_pose_estimate(info, res, m);
+    if (correspondences) {
+        std::vector<std::pair<int, int>> out(corr.size() / 2);
+        for (size_t k = 0; k < out.size(); ++k) out[k] = {corr[2 * k], corr[2 * k + 1]};
+        correspondences->swap(out);
+    }
     return true;
 }
 

@@ -429,12 +429,7 @@ __global__ __launch_bounds__(K1_TPB) void k_tile_boxes(const TileBoxArgs A) {
 
 // ------------------------------------------------------------------------------------------------
 // shared device helpers
-__device__ __forceinline__ uint64_t mix64(uint64_t z) {
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
+// (mix64: common.h)
 struct Rng {
     uint64_t s;
     __device__ uint32_t next() { s = mix64(s); return (uint32_t)(s >> 32); }

@@ -930,7 +930,11 @@ int plade_cloud_download(plade_ctx *ctx, const plade_cloud *cloud, float *rows, 
  * cand, slot_f, slot_u, slot_w} (no tag after plade_extract_planes; layout: ExtractTrace in plade_amd/csrc/ransac.h). */
 int plade_dump_get(plade_ctx *ctx, const char *name, const void **ptr, int64_t *nbytes);
 /* Per-stage GPU/host seconds and byte counts of the last registration:
- * names is a ';'-separated list, values has one double per name. */
+ * names is a ';'-separated list, values has one double per name.
+ * The cloud tools that search a point grid also report the grid of their last call: <tool>_grid_dx, _grid_dy, _grid_dz (cells per
+ * axis) and <tool>_grid_cell (the cell size, which is larger than the one the tool asked for when the cap on the grid's size
+ * applied), <tool> = normals, outliers, distances, smooth, components, fpfh, m3c2_a and m3c2_b (the grids over the reference and
+ * the compared cloud), icp and gicp (the first, widest stage; the linearize seams: their one stage). */
 int plade_stats_get(plade_ctx *ctx, const char **names, const double **values, int32_t *count);
 /* ---- diagnostic: the device-wide stable radix sort every grid of the path is built with ----------------
  * (radix_sort.hip; no reference counterpart -- it stands where PCL sorts voxel indices with std::sort,

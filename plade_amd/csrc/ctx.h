@@ -34,6 +34,12 @@ struct Stats {
         names.push_back(n);
         values.push_back(v);
     }
+    void set(const std::string &n, double v) {   // a value that is no sum: the latest one stands
+        for (size_t i = 0; i < names.size(); ++i)
+            if (names[i] == n) { values[i] = v; return; }
+        names.push_back(n);
+        values.push_back(v);
+    }
     void merge(const Stats &o) { for (size_t i = 0; i < o.names.size(); ++i) add(o.names[i], o.values[i]); }
 };
 

@@ -36,6 +36,16 @@ inline GridView view_of(const TargetGrid &G, const char *who) {
     return g;
 }
 
+// The grid a tool met, for its stats: "<tool>_grid_dx", "_dy", "_dz" (cells) and "_grid_cell" (1 / inv: build() may have enlarged
+// the cell that was asked for).  Called where the tool publishes its other stats, with the grid it built
+inline void grid_stats(plade_ctx *ctx, const char *tool, const TargetGrid &G) {
+    const std::string t(tool);
+    ctx->stats.set(t + "_grid_dx", G.gp.dx);
+    ctx->stats.set(t + "_grid_dy", G.gp.dy);
+    ctx->stats.set(t + "_grid_dz", G.gp.dz);
+    ctx->stats.set(t + "_grid_cell", 1.0 / (double)G.gp.inv);
+}
+
 // the largest |coordinate| of a bounding box
 inline double amax_of(const float mn[3], const float mx[3]) {
     double a = 0.0;

@@ -257,6 +257,7 @@ uint32_t components_dev(plade_ctx *ctx, ComponentWork &W, const float *d_rows, u
     ctx->stats.add("components_compact_s", W.spans.seconds(3));
     ctx->stats.add("components_count", C);
     ctx->stats.add("components_kept", total);
+    grid_stats(ctx, "components", W.grid);
     return total;
 }
 

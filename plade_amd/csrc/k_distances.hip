@@ -303,6 +303,7 @@ void distances_dev(plade_ctx *ctx, DistWork &W, const float *d_tgt, uint32_t n_t
     ctx->stats.add("distances_ring_s", W.spans.seconds(3));
     ctx->stats.add("distances_summary_s", W.spans.seconds(4));
     ctx->stats.add("distances_ring_queries", W.h_count);
+    grid_stats(ctx, "distances", G);
 }
 
 DistWork &work_of(plade_ctx *ctx) {

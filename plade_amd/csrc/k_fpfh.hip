@@ -408,6 +408,7 @@ void fpfh_dev(plade_ctx *ctx, FpfhWork &W, const float *d_rows, uint32_t n, uint
     ctx->stats.add("fpfh_spfh_s", W.spans.seconds(1));
     ctx->stats.add("fpfh_weight_s", W.spans.seconds(2));
     ctx->stats.add("fpfh_described", (double)W.h_u[0]);
+    grid_stats(ctx, "fpfh", W.grid);
 }
 
 // nn / d2 of every query over the targets (device tables of 33 floats per row)

@@ -155,6 +155,7 @@ int refine_dev(plade_ctx *ctx, IcpWork &W, const float *d_tgt, uint32_t n_t, con
     ctx->stats.add("icp_loop_s", W.spans.seconds(2));
     ctx->stats.add("icp_iterations", s.iter);
     ctx->stats.add("icp_stages", c.n_stages);
+    grid_stats(ctx, "icp", W.grids[0]);              // the first (widest) stage
     if (s.failure) {
         memmove(T_out16, T_in, sizeof(T_in));
         ctx->last_error = s.failure == PLADE_ICP_TOO_FEW ? "refine_icp: too few correspondences"
@@ -247,6 +248,7 @@ extern "C" int plade_icp_linearize(plade_ctx *ctx, const float *tgt_pos_nrm, uin
         HIP_TRY(hipMemcpyAsync(moments_out, sa.moments, ICP_MOMENTS * 8, hipMemcpyDeviceToHost, ctx->stream));
         if (corr_out) HIP_TRY(hipMemcpyAsync(corr_out, a.corr, (size_t)n_s * 4, hipMemcpyDeviceToHost, ctx->stream));
         ctx->sync();
+        grid_stats(ctx, "icp", W.grids[0]);
         return PLADE_OK;
     });
 }

@@ -312,6 +312,8 @@ void m3c2_dev(plade_ctx *ctx, M3c2Work &W, const float *d_core, uint32_t m, uint
     ctx->stats.add("m3c2_walk_s", W.spans.seconds(1));
     ctx->stats.add("m3c2_reduce_s", W.spans.seconds(2));
     ctx->stats.add("m3c2_valid", W.h_u[0]);
+    grid_stats(ctx, "m3c2_a", W.grid_a);
+    grid_stats(ctx, "m3c2_b", W.grid_b);
 }
 
 M3c2Work &work_of(plade_ctx *ctx) {

@@ -216,6 +216,7 @@ void normals_stats(plade_ctx *ctx, NormalsWork &W) {
     ctx->stats.add("normals_search_s", W.spans.seconds(1));
     ctx->stats.add("normals_grid_builds", W.builds);
     ctx->stats.add("normals_ring_queries", W.h_count);
+    grid_stats(ctx, "normals", W.grid);
 }
 
 }  // namespace plade

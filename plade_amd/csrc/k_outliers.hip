@@ -307,6 +307,7 @@ uint32_t filter_dev(plade_ctx *ctx, OutlierWork &W, const float *d_rows, uint32_
     ctx->stats.add("outliers_compact_s", W.spans.seconds(3));
     ctx->stats.add("outliers_grid_builds", W.builds);
     ctx->stats.add("outliers_ring_queries", W.h_count);
+    if (W.builds) grid_stats(ctx, "outliers", G);
     ctx->stats.add("outliers_kept", total);
     return total;
 }

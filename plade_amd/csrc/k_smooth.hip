@@ -217,6 +217,7 @@ void smooth_dev(plade_ctx *ctx, SmoothWork &W, const float *d_rows, uint32_t n, 
     ctx->stats.add("smooth_fit_s", W.spans.seconds(1));
     ctx->stats.add("smooth_reduce_s", W.spans.seconds(2));
     ctx->stats.add("smooth_fitted", W.h_u[0]);
+    grid_stats(ctx, "smooth", W.grid);
 }
 
 SmoothWork &work_of(plade_ctx *ctx) {

@@ -29,7 +29,7 @@ void normals_work_destroy(NormalsWork *w);
 void estimate_normals_dev(plade_ctx *ctx, NormalsWork &W, const float *d_xyz, uint32_t n, uint32_t stride, const float bbmin[3],
                           const float bbmax[3], int k, const float view[3], float *d_out, float *d_curv, int32_t *d_nbr);
 // after the caller's sync: stats "normals_grid_s" (grid builds, including the host waits of the cell adaptation), "normals_search_s",
-// "normals_grid_builds", "normals_ring_queries"
+// "normals_grid_builds", "normals_ring_queries" and the grid of the last build (grid_stats of grid_walk.h)
 void normals_stats(plade_ctx *ctx, NormalsWork &W);
 
 // argument checks of the entry points (PLADE_EINVAL): n >= 1, stride >= 3, k in [3, 64], a finite viewpoint (bbox_host checks

@@ -887,6 +887,84 @@ int plade_register_features_dev(plade_ctx *ctx, plade_cloud *tgt, plade_cloud *s
                                 plade_fpfh_summary *src_summary, plade_fpfh_summary *tgt_summary, plade_corr_pose_result *result,
                                 int32_t *corr_out, uint64_t cap, uint64_t *n_corr);
 
+/* ---- keypoints: Intrinsic Shape Signatures (Zhong 2009, the scatter of PCL's ISSKeypoint3D; no reference counterpart) ---------------
+ * Semantics (plade_amd/csrc/keypoints.h).  The few per cent of a cloud's points whose neighbourhood varies in
+ * all three directions: what goes into the feature match in place of every point.  Input: n >= 1 rows of `stride` >= 3 floats, x y z
+ * first, all finite; normals are not used.
+ *   distance     d(i, j) = the fp32 squared distance of plade_smooth_cloud; rs2 = (float)rs * (float)rs, rn2 likewise (rn = 0: rs).
+ *   scatter      N_i = { j : d(i, j) < rs2 } (strict; the point itself belongs to it), c_i = |N_i|, an exact integer.
+ *                q_j = double(p_j) - double(p_i); M_i = sum q_a q_b: six fp64 sums xx xy xz yy yz zz in the fixed order of the grid
+ *                walk, no atomics; C_i = M_i / double(c_i) entry by entry -- the scatter about the query point, not the centroid.
+ *   eigenvalues  l1 >= l2 >= l3 of C_i by the trigonometric closed form of the normals' eigen-solve: q = tr / 3, p2 the squared
+ *                norm of C - q I, pp = sqrt(p2 / 6), r = det((C - q I) / pp) / 2 clamped to [-1, 1], phi = acos(r) / 3;
+ *                l_max = q + 2 pp cos(phi), l_min = q + 2 pp cos(phi + 2 pi / 3), l_mid = tr - l_max - l_min, then ordered with
+ *                fmin / fmax; p2 = 0: all three are q.
+ *   salient      c_i >= 3 && l1 > 0 && l2 < gamma21 * l1 && l3 < gamma32 * l2 && l3 > 1e-9 * l1, products and comparisons in fp64
+ *                (a collinear or coplanar neighbourhood is flat by arithmetic, not by the sign of a rounding error).
+ *                saliency_i = l3 when salient, else 0.
+ *   suppression  B_i = { j : d(i, j) < rn2 }, i included, m_i = |B_i|.  i is a keypoint iff it is salient, m_i - 1 >= min_neighbours
+ *                and no j in B_i, j != i, has saliency_j > saliency_i, or saliency_j == saliency_i with j < i: an exact function of
+ *                the points and the saliencies.
+ *   output       by original index; each array may be NULL.  keypoint_out: n bytes 0 / 1; index_out: cap uint32, the keypoints'
+ *                indices ascending; *n_keypoints: their exact number -- PLADE_ECAP when index_out is given and *n_keypoints > cap
+ *                (the first cap entries are written); saliency_out: n doubles; eigenvalues_out: n x 3 doubles, descending;
+ *                count_out: n uint32 (c_i); nms_count_out: n uint32 (m_i); scatter_out: n x 6 doubles (M_i) -- a test seam.
+ *                summary: n, salient, keypoints, the largest c_i.
+ * c, m and, given the saliencies, the flags depend on the point set and the radii only; the last bits of M follow the grid (another
+ * bounding box, a permutation of the input).  The same input gives the same bits on every run, on every context and from
+ * plade_cloud_keypoints_iss_dev.  Keypoints of two independent samplings of a surface repeat badly at moderate densities: match the
+ * keypoints of ONE cloud against every described point of the other (plade_register_keypoints), not keypoints against keypoints.
+ * Errors: PLADE_EINVAL for a NULL cloud, params or summary, n = 0, stride < 3, a non-finite coordinate, salient_radius <= 0 or not
+ * finite (or its fp32 square not finite or below FLT_MIN), non_max_radius neither 0 nor such a radius, a gamma outside (0, 1],
+ * min_neighbours < 1; the context stays usable.  plade_stats_get then reports iss_grid_s, iss_scatter_s, iss_nms_s (HIP events on
+ * the context's stream; the last one includes the list and the summary), iss_salient and iss_keypoints. */
+typedef struct plade_iss_params {
+    double salient_radius;       /* rs: must be set (> 0), absolute, in the cloud's units */
+    double non_max_radius;       /* rn; 0: salient_radius */
+    double gamma21, gamma32;     /* (0, 1]: the bounds on l2 / l1 and l3 / l2 */
+    int32_t min_neighbours;      /* >= 1: the smallest m_i - 1 of a keypoint */
+    int32_t reserved;            /* 0 */
+} plade_iss_params;
+typedef struct plade_iss_summary {
+    uint64_t n, salient, keypoints;
+    uint32_t max_count;          /* the largest c_i */
+    uint32_t reserved;           /* 0 */
+} plade_iss_summary;
+/* The defaults: salient_radius = 0 (unset), non_max_radius = 0 (= salient_radius), gamma21 = gamma32 = 0.975, min_neighbours = 5.
+ * Needs no GPU. */
+void plade_iss_default_params(plade_iss_params *p);
+int plade_cloud_keypoints_iss(plade_ctx *ctx, const float *rows, uint32_t n, uint32_t stride, const plade_iss_params *params,
+                              uint8_t *keypoint_out, uint32_t *index_out, uint64_t cap, uint64_t *n_keypoints, double *saliency_out,
+                              double *eigenvalues_out, uint32_t *count_out, uint32_t *nms_count_out, double *scatter_out,
+                              plade_iss_summary *summary);
+/* The same on a resident cloud: the point data makes no host round trip, the outputs (host arrays) are the bits of
+ * plade_cloud_keypoints_iss on the cloud's rows. */
+int plade_cloud_keypoints_iss_dev(plade_ctx *ctx, plade_cloud *cloud, const plade_iss_params *params, uint8_t *keypoint_out,
+                                  uint32_t *index_out, uint64_t cap, uint64_t *n_keypoints, double *saliency_out,
+                                  double *eigenvalues_out, uint32_t *count_out, uint32_t *nms_count_out, double *scatter_out,
+                                  plade_iss_summary *summary);
+/* Rows index[0 .. k - 1] of a resident descriptor table (plade_cloud_fpfh_dev) as a NEW resident table of k rows, bit for bit, for
+ * plade_match_features_dev; release it with plade_features_free.  PLADE_EINVAL for a NULL argument, k = 0 or an index >= the
+ * table's rows. */
+int plade_features_select(plade_ctx *ctx, plade_features *features, const uint32_t *index, uint32_t k, plade_features **out);
+/* plade_register_features with a keypoint detector in front of the match: ISS on the source's x y z, FPFH of both full clouds, the
+ * source rows at the keypoints matched against the WHOLE target table (mutual as given), the pose from the correspondences -- with
+ * nothing but the summaries and the two list lengths leaving the device in between.  The list (corr_out, *n_corr; original source
+ * indices) and the pose carry the bits of plade_cloud_keypoints_iss, plade_cloud_fpfh, plade_features_select,
+ * plade_match_features_dev and plade_estimate_pose_corr chained by hand.  Fewer than three correspondences (no keypoint included)
+ * fail as there: PLADE_EFAIL, the identity, PLADE_CORR_POSE_TOO_FEW.  Errors: those of the calls it chains. */
+int plade_register_keypoints(plade_ctx *ctx, const float *tgt_pos_nrm, uint32_t n_t, const float *src_pos_nrm, uint32_t n_s,
+                             const plade_iss_params *iss, const plade_fpfh_params *fpfh, const plade_feature_match_params *match,
+                             const plade_corr_pose_params *pose, float *T16, plade_iss_summary *iss_summary,
+                             plade_fpfh_summary *src_summary, plade_fpfh_summary *tgt_summary, plade_corr_pose_result *result,
+                             int32_t *corr_out, uint64_t cap, uint64_t *n_corr);
+/* The same on two resident clouds: bit-identical results. */
+int plade_register_keypoints_dev(plade_ctx *ctx, plade_cloud *tgt, plade_cloud *src, const plade_iss_params *iss,
+                                 const plade_fpfh_params *fpfh, const plade_feature_match_params *match,
+                                 const plade_corr_pose_params *pose, float *T16, plade_iss_summary *iss_summary,
+                                 plade_fpfh_summary *src_summary, plade_fpfh_summary *tgt_summary, plade_corr_pose_result *result,
+                                 int32_t *corr_out, uint64_t cap, uint64_t *n_corr);
+
 /* ---- merging registered clouds: the step a scan-to-scan chain ends with (no reference counterpart) -----------------------------
  * Semantics (plade_amd/csrc/merge.h).  k clouds, 1 <= k <= 16; cloud c: n_c >= 1 rows x y z nx ny nz with
  * finite coordinates (the normals may be NaN); T: k row-major fp32 4 x 4 matrices, cloud c -> the output frame (NULL: identities,
@@ -933,7 +1011,7 @@ int plade_dump_get(plade_ctx *ctx, const char *name, const void **ptr, int64_t *
  * names is a ';'-separated list, values has one double per name.
  * The cloud tools that search a point grid also report the grid of their last call: <tool>_grid_dx, _grid_dy, _grid_dz (cells per
  * axis) and <tool>_grid_cell (the cell size, which is larger than the one the tool asked for when the cap on the grid's size
- * applied), <tool> = normals, outliers, distances, smooth, components, fpfh, m3c2_a and m3c2_b (the grids over the reference and
+ * applied), <tool> = normals, outliers, distances, smooth, components, fpfh, iss, m3c2_a and m3c2_b (the grids over the reference and
  * the compared cloud), icp and gicp (the first, widest stage; the linearize seams: their one stage). */
 int plade_stats_get(plade_ctx *ctx, const char **names, const double **values, int32_t *count);
 /* ---- diagnostic: the device-wide stable radix sort every grid of the path is built with ----------------

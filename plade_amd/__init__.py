@@ -39,6 +39,8 @@ ABI_SYMBOLS = [
     "plade_feature_match_default_params", "plade_match_features", "plade_match_features_dev",
     "plade_corr_pose_default_params", "plade_estimate_pose_corr", "plade_estimate_pose_corr_dev", "plade_corr_pose_moments",
     "plade_register_features", "plade_register_features_dev",
+    "plade_iss_default_params", "plade_cloud_keypoints_iss", "plade_cloud_keypoints_iss_dev", "plade_features_select",
+    "plade_register_keypoints", "plade_register_keypoints_dev",
     "plade_penetration_filter",
 ]
 
@@ -181,6 +183,19 @@ class CorrPoseResult(C.Structure):
                 ("rmse", C.c_double), ("fitness", C.c_double), ("T", C.c_double * 12)]
 
 
+class IssParams(C.Structure):
+    """plade_iss_params: salient_radius (absolute, no default), non_max_radius (0: salient_radius), the eigenvalue ratio bounds
+    gamma21 and gamma32, min_neighbours within non_max_radius of a keypoint."""
+    _fields_ = [("salient_radius", C.c_double), ("non_max_radius", C.c_double), ("gamma21", C.c_double), ("gamma32", C.c_double),
+                ("min_neighbours", C.c_int32), ("reserved", C.c_int32)]
+
+
+class IssSummary(C.Structure):
+    """plade_iss_summary: n, salient, keypoints, max_count (the largest neighbourhood within salient_radius)."""
+    _fields_ = [("n", C.c_uint64), ("salient", C.c_uint64), ("keypoints", C.c_uint64), ("max_count", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
 PLADE_CORR_POSE_TOO_FEW, PLADE_CORR_POSE_NONE_SCORED, PLADE_CORR_POSE_FEW_INLIERS = 1, 2, 3
 CORR_POSE_FAILURES = {0: None, PLADE_CORR_POSE_TOO_FEW: "fewer than 3 correspondences", PLADE_CORR_POSE_NONE_SCORED: "nothing scored",
                       PLADE_CORR_POSE_FEW_INLIERS: "too few inliers"}
@@ -299,6 +314,19 @@ def load_library(path=LIB_PATH):
     sig("plade_register_features_dev", argtypes=[p, p, p, C.POINTER(FpfhParams), C.POINTER(FeatureMatchParams),
                                                  C.POINTER(CorrPoseParams), p, C.POINTER(FpfhSummary), C.POINTER(FpfhSummary),
                                                  C.POINTER(CorrPoseResult), p, u64, C.POINTER(u64)])
+    sig("plade_iss_default_params", argtypes=[C.POINTER(IssParams)], restype=None)
+    sig("plade_cloud_keypoints_iss", argtypes=[p, p, u32, u32, C.POINTER(IssParams), p, p, u64, C.POINTER(u64), p, p, p, p, p,
+                                               C.POINTER(IssSummary)])
+    sig("plade_cloud_keypoints_iss_dev", argtypes=[p, p, C.POINTER(IssParams), p, p, u64, C.POINTER(u64), p, p, p, p, p,
+                                                   C.POINTER(IssSummary)])
+    sig("plade_features_select", argtypes=[p, p, p, u32, C.POINTER(p)])
+    sig("plade_register_keypoints", argtypes=[p, p, u32, p, u32, C.POINTER(IssParams), C.POINTER(FpfhParams),
+                                              C.POINTER(FeatureMatchParams), C.POINTER(CorrPoseParams), p, C.POINTER(IssSummary),
+                                              C.POINTER(FpfhSummary), C.POINTER(FpfhSummary), C.POINTER(CorrPoseResult), p, u64,
+                                              C.POINTER(u64)])
+    sig("plade_register_keypoints_dev", argtypes=[p, p, p, C.POINTER(IssParams), C.POINTER(FpfhParams), C.POINTER(FeatureMatchParams),
+                                                  C.POINTER(CorrPoseParams), p, C.POINTER(IssSummary), C.POINTER(FpfhSummary),
+                                                  C.POINTER(FpfhSummary), C.POINTER(CorrPoseResult), p, u64, C.POINTER(u64)])
     sig("plade_sort_segments", argtypes=[p, p, p, p, u32, C.c_int, p, p])
     sig("plade_set_candidate_shard", argtypes=[p, u32, u32, u32, EXCHANGE_FN, p])
     sig("plade_registration_minsupport", argtypes=[p, p, u32, p, u32, i32, i32, p])
@@ -489,6 +517,26 @@ def corr_pose_default_params():
     prm = CorrPoseParams()
     load_library().plade_corr_pose_default_params(C.byref(prm))
     return {k: getattr(prm, k) for k, _ in CorrPoseParams._fields_ if k != "reserved"}
+
+
+def iss_default_params():
+    """plade_iss_default_params (pure: needs no GPU) as a dict of the plade_iss_params fields."""
+    prm = IssParams()
+    load_library().plade_iss_default_params(C.byref(prm))
+    return {k: getattr(prm, k) for k, _ in IssParams._fields_ if k != "reserved"}
+
+
+def _iss_params(salient_radius, non_max_radius, gamma21, gamma32, min_neighbours):
+    prm = IssParams()
+    load_library().plade_iss_default_params(C.byref(prm))
+    prm.salient_radius, prm.non_max_radius = float(salient_radius), float(non_max_radius)
+    if gamma21 is not None:
+        prm.gamma21 = float(gamma21)
+    if gamma32 is not None:
+        prm.gamma32 = float(gamma32)
+    if min_neighbours is not None:
+        prm.min_neighbours = int(min_neighbours)
+    return prm
 
 
 def _corr_pose_params(inlier_dist, kw):
@@ -687,6 +735,10 @@ class Features:
 
     def __init__(self, ctx, n, handle):
         self.ctx, self.n, self.h = ctx, n, handle
+
+    def select(self, index):
+        """plade_features_select: the rows `index` (ints below n) as a new resident table (free() it too)."""
+        return self.ctx.select_features(self, index)
 
     def free(self):
         if self.h:
@@ -1492,6 +1544,92 @@ class Context:
         """plade_register_features_dev: register_features on two resident clouds; bit-identical results."""
         return self._register_features(lambda *a: self.L.plade_register_features_dev(self.h, tgt_cloud.h, src_cloud.h, *a), src_cloud.n,
                                        radius, inlier_dist, min_pairs, mutual, max_ratio, pose_params)
+
+    # ---- keypoints (ISS), and ISS -> FPFH -> match of the keypoints -> pose in one call ---------------------------
+    def _iss(self, call, n, prm, per_point, seams, cap):
+        key = np.zeros(n, np.uint8) if per_point else None
+        sal = np.empty(n, np.float64) if per_point else None
+        eig = np.empty((n, 3), np.float64) if per_point else None
+        count = np.empty(n, np.uint32) if per_point else None
+        nms = np.empty(n, np.uint32) if per_point else None
+        scatter = np.empty((n, 6), np.float64) if seams else None
+        cap = n if cap is None else int(cap)
+        index = np.empty(max(cap, 1), np.uint32)
+        total, summ = C.c_uint64(), IssSummary()
+        rc = self._check(call(C.byref(prm), _ptr(key), _ptr(index), cap, C.byref(total), _ptr(sal), _ptr(eig), _ptr(count), _ptr(nms),
+                              _ptr(scatter), C.byref(summ)), allow=(PLADE_ECAP,))
+        info = {k: getattr(summ, k) for k, _ in IssSummary._fields_ if k != "reserved"}
+        info.update(n_keypoints=total.value, complete=rc == 0)
+        if per_point:
+            info.update(keypoint=key.view(np.bool_), saliency=sal, eigenvalues=eig, count=count, nms_count=nms)
+        if seams:
+            info.update(scatter=scatter)
+        return index[:min(cap, total.value)].copy(), info
+
+    def iss_keypoints(self, points, salient_radius, non_max_radius=0.0, gamma21=None, gamma32=None, min_neighbours=None, per_point=True,
+                      seams=False, cap=None):
+        """plade_cloud_keypoints_iss: the ISS keypoints of an (N, >= 3) float32 array whose first columns are x y z.  A point is
+        salient when the eigenvalues l1 >= l2 >= l3 of the scatter of its neighbours within salient_radius (about the point itself)
+        satisfy l2 < gamma21 l1 and l3 < gamma32 l2 (defaults 0.975) and l3 > 1e-9 l1; it is a keypoint when it also has at least
+        min_neighbours (default 5) other points within non_max_radius (0: salient_radius) and none of them has a larger l3.  Returns
+        (index, info): index, the keypoints' rows ascending (uint32; at most cap of them, default N -- then complete is False);
+        info: n, salient, keypoints, max_count, n_keypoints (exact) and -- with per_point -- keypoint (N bools), saliency (N float64:
+        l3 or 0), eigenvalues (N, 3 float64, descending), count and nms_count (N uint32: the points within the two radii, the point
+        itself included), with seams the (N, 6) float64 sums scatter (xx xy xz yy yz zz)."""
+        a, n, stride = _xyz_view(points)
+        prm = _iss_params(salient_radius, non_max_radius, gamma21, gamma32, min_neighbours)
+        return self._iss(lambda *o: self.L.plade_cloud_keypoints_iss(self.h, _ptr(a), n, stride, *o), n, prm, per_point, seams, cap)
+
+    def iss_keypoints_dev(self, cloud, salient_radius, non_max_radius=0.0, gamma21=None, gamma32=None, min_neighbours=None, per_point=True,
+                          seams=False, cap=None):
+        """plade_cloud_keypoints_iss_dev: iss_keypoints on a resident cloud (upload); bit-identical results."""
+        prm = _iss_params(salient_radius, non_max_radius, gamma21, gamma32, min_neighbours)
+        return self._iss(lambda *o: self.L.plade_cloud_keypoints_iss_dev(self.h, cloud.h, *o), cloud.n, prm, per_point, seams, cap)
+
+    def select_features(self, features, index):
+        """plade_features_select: rows `index` of a resident descriptor table (fpfh_dev(..., resident=True)) as a new Features handle
+        (free() it) -- the table of a cloud's keypoints for match_features_dev."""
+        idx = np.ascontiguousarray(np.asarray(index).reshape(-1))
+        if idx.size and (idx.min() < 0 or idx.max() > 0xffffffff):
+            raise ValueError("select_features: an index is negative or does not fit 32 bits")
+        idx = idx.astype(np.uint32)
+        fh = C.c_void_p()
+        self._check(self.L.plade_features_select(self.h, features.h, _ptr(idx), len(idx), C.byref(fh)))
+        return Features(self, len(idx), fh)
+
+    def _register_keypoints(self, call, ns, ip, radius, inlier_dist, min_pairs, mutual, max_ratio, pose_params):
+        fp, mp, pp = _fpfh_params(radius, min_pairs), _feature_match_params(mutual, max_ratio), _corr_pose_params(inlier_dist, pose_params)
+        T = np.empty((4, 4), np.float32)
+        s_iss, s_src, s_tgt, res = IssSummary(), FpfhSummary(), FpfhSummary(), CorrPoseResult()
+        corr = np.empty((max(ns, 1), 2), np.int32)
+        total = C.c_uint64()
+        rc = self._check(call(C.byref(ip), C.byref(fp), C.byref(mp), C.byref(pp), _ptr(T), C.byref(s_iss), C.byref(s_src), C.byref(s_tgt),
+                              C.byref(res), _ptr(corr), ns, C.byref(total)), allow=(PLADE_EFAIL,))
+        info = _corr_pose_info(res)
+        info.update(ok=rc == 0, reason=CORR_POSE_FAILURES.get(res.failure), n_corr=total.value, corr=corr[:total.value].copy(),
+                    iss={k: getattr(s_iss, k) for k, _ in IssSummary._fields_ if k != "reserved"},
+                    fpfh_src={k: getattr(s_src, k) for k, _ in FpfhSummary._fields_ if k != "reserved"},
+                    fpfh_tgt={k: getattr(s_tgt, k) for k, _ in FpfhSummary._fields_ if k != "reserved"})
+        return T, info
+
+    def register_keypoints(self, tgt, src, radius, inlier_dist, salient_radius, non_max_radius=0.0, gamma21=None, gamma32=None,
+                           min_neighbours=None, min_pairs=None, mutual=True, max_ratio=0.0, **pose_params):
+        """plade_register_keypoints: register_features with the ISS detector in front of the match -- the keypoints of the source
+        (iss_keypoints at salient_radius / non_max_radius), FPFH of both (N, 6) clouds at `radius`, the source's keypoint rows
+        matched against every described target point, the pose from the correspondences; the bits of those calls chained by hand.
+        Returns (T, info) as register_features, corr holding original source indices, plus the detector's summary info["iss"]."""
+        tgt, src = _f32(tgt), _f32(src)
+        self._check_cloud(tgt, "register_keypoints"); self._check_cloud(src, "register_keypoints")
+        ip = _iss_params(salient_radius, non_max_radius, gamma21, gamma32, min_neighbours)
+        return self._register_keypoints(lambda *a: self.L.plade_register_keypoints(self.h, _ptr(tgt), len(tgt), _ptr(src), len(src), *a),
+                                        len(src), ip, radius, inlier_dist, min_pairs, mutual, max_ratio, pose_params)
+
+    def register_keypoints_dev(self, tgt_cloud, src_cloud, radius, inlier_dist, salient_radius, non_max_radius=0.0, gamma21=None,
+                               gamma32=None, min_neighbours=None, min_pairs=None, mutual=True, max_ratio=0.0, **pose_params):
+        """plade_register_keypoints_dev: register_keypoints on two resident clouds; bit-identical results."""
+        ip = _iss_params(salient_radius, non_max_radius, gamma21, gamma32, min_neighbours)
+        return self._register_keypoints(lambda *a: self.L.plade_register_keypoints_dev(self.h, tgt_cloud.h, src_cloud.h, *a), src_cloud.n,
+                                        ip, radius, inlier_dist, min_pairs, mutual, max_ratio, pose_params)
 
     # ---- merging registered clouds ---------------------------------------------------------------
     @staticmethod

@@ -14,6 +14,7 @@
 #include "m3c2.h"
 #include "fpfh.h"
 #include "corr_pose.h"
+#include "keypoints.h"
 
 using namespace plade;
 
@@ -153,6 +154,7 @@ extern "C" void plade_ctx_destroy(plade_ctx *ctx) {
     if (ctx->m3c2_work) plade::m3c2_work_destroy(ctx->m3c2_work);
     if (ctx->fpfh_work) plade::fpfh_work_destroy(ctx->fpfh_work);
     if (ctx->corr_pose_work) plade::corr_pose_work_destroy(ctx->corr_pose_work);
+    if (ctx->iss_work) plade::iss_work_destroy(ctx->iss_work);
     (void)hipStreamDestroy(ctx->stream);
     if (ctx->pf.stream) { (void)hipStreamSynchronize(ctx->pf.stream); (void)hipStreamDestroy(ctx->pf.stream); }
     delete ctx;

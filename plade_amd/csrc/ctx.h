@@ -89,7 +89,7 @@ struct plade_cloud {
     std::vector<float> host_copy;  // pos_nrm kept for the small host-side gathers
 };
 
-namespace plade { struct RegistrationWork; struct RansacWork; struct NormalsWork; struct IcpWork; struct DistWork; struct OutlierWork; struct MergeWork; struct ComponentWork; struct SmoothWork; struct GicpWork; struct M3c2Work; struct FpfhWork; struct CorrPoseWork; }
+namespace plade { struct RegistrationWork; struct RansacWork; struct NormalsWork; struct IcpWork; struct DistWork; struct OutlierWork; struct MergeWork; struct ComponentWork; struct SmoothWork; struct GicpWork; struct M3c2Work; struct FpfhWork; struct CorrPoseWork; struct IssWork; }
 namespace plade { void comm_all_gather_dev(plade_comm *c, const void *d_send, void *d_recv, size_t bytes, hipStream_t stream); }
 
 struct plade_ctx {
@@ -473,6 +473,8 @@ struct plade_ctx {
     plade::FpfhWork *fpfh_work = nullptr;
     // packed correspondences, hypothesis tables and state of plade_estimate_pose_corr / plade_corr_pose_moments (behind them too)
     plade::CorrPoseWork *corr_pose_work = nullptr;
+    // grid, per-point outputs, list and partials of plade_cloud_keypoints_iss; the index list of plade_features_select (behind them too)
+    plade::IssWork *iss_work = nullptr;
 
     template <class T>
     void put(const std::string &name, const T *data, size_t count) {

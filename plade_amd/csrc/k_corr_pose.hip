@@ -17,6 +17,7 @@
 //            (CorrState) lives on the device and once it says done every later kernel of the loop returns at once.
 #include "corr_pose.h"
 #include "fpfh.h"
+#include "keypoints.h"
 #include "fixed_reduce.h"
 #include "prims.h"
 #include "voxel.h"
@@ -402,6 +403,7 @@ struct CorrPoseWork {
     DBuf<u64> best_partial;
     DBuf<CorrState> st;
     plade_features feat_s, feat_t;   // plade_register_features: the two descriptor tables (grow-only)
+    plade_features feat_k;           // plade_register_keypoints: the source rows at the keypoints
     CorrState h_st;
     EventSpans<4> spans;             // build, score, refine
 };
@@ -609,6 +611,34 @@ int register_dev(plade_ctx *ctx, CorrPoseWork &W, const float *d_tgt, uint32_t n
     return rc;
 }
 
+// The same with the detector in front of the match: ISS on the source, FPFH of both clouds, the source rows at the keypoints against
+// the whole target table, the list's source column mapped back to original indices, the pose.
+int register_keypoints_dev(plade_ctx *ctx, CorrPoseWork &W, const float *d_tgt, uint32_t nt, const float tmn[3], const float tmx[3],
+                           const float *d_src, uint32_t ns, const float smn[3], const float smx[3], const plade_iss_params &ip,
+                           const plade_fpfh_params &fp, const plade_feature_match_params &mp, const plade_corr_pose_params &pp, float *T16,
+                           plade_iss_summary *sum_iss, plade_fpfh_summary *sum_src, plade_fpfh_summary *sum_tgt,
+                           plade_corr_pose_result *res, int32_t *corr_out, uint64_t cap, uint64_t *n_corr) {
+    check_params(pp);
+    uint32_t k = 0;
+    const uint32_t *d_key = iss_list_dev(ctx, d_src, ns, 6, smn, smx, ip, sum_iss, &k);
+    fpfh_table_dev(ctx, d_src, ns, smn, smx, fp, W.feat_s, sum_src);
+    fpfh_table_dev(ctx, d_tgt, nt, tmn, tmx, fp, W.feat_t, sum_tgt);
+    uint64_t total = 0;
+    const int32_t *d_corr = nullptr;
+    if (k) {                                         // (no keypoint: no match, and the pose fails with too few correspondences)
+        features_select_dev(ctx, W.feat_s, d_key, k, W.feat_k);
+        const int32_t *d_sel = feature_corr_dev(ctx, W.feat_k, W.feat_t, mp, &total);
+        d_corr = corr_map_source_dev(ctx, d_sel, total, d_key);
+    }
+    if (n_corr) *n_corr = total;
+    if (corr_out && std::min(total, cap))
+        HIP_TRY(hipMemcpyAsync(corr_out, d_corr, (size_t)std::min(total, cap) * 8, hipMemcpyDeviceToHost, ctx->stream));
+    const Seams none = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    const int rc = pose_dev(ctx, W, d_src, 6, d_tgt, 6, d_corr, (uint32_t)total, pp, T16, none, res, true);
+    if (total < 3) ctx->sync();                      // (as register_dev)
+    return rc;
+}
+
 }  // namespace
 }  // namespace plade
 
@@ -729,5 +759,41 @@ extern "C" int plade_register_features_dev(plade_ctx *ctx, plade_cloud *tgt, pla
         const CloudDev &t = tgt->dev, &s = src->dev;
         return register_dev(ctx, work_of(ctx), t.aos.p, t.n, t.bbmin, t.bbmax, s.aos.p, s.n, s.bbmin, s.bbmax, *fpfh, mp, *pose, T16,
                             src_summary, tgt_summary, result, corr_out, cap, n_corr);
+    });
+}
+
+extern "C" int plade_register_keypoints(plade_ctx *ctx, const float *tgt_pos_nrm, uint32_t n_t, const float *src_pos_nrm, uint32_t n_s,
+                                        const plade_iss_params *iss, const plade_fpfh_params *fpfh, const plade_feature_match_params *match,
+                                        const plade_corr_pose_params *pose, float *T16, plade_iss_summary *iss_summary,
+                                        plade_fpfh_summary *src_summary, plade_fpfh_summary *tgt_summary, plade_corr_pose_result *result,
+                                        int32_t *corr_out, uint64_t cap, uint64_t *n_corr) {
+    return guarded(ctx, [&]() -> int {
+        PLADE_REQUIRE(tgt_pos_nrm && src_pos_nrm && iss && fpfh && pose && T16 && iss_summary && src_summary && tgt_summary && result,
+                      PLADE_EINVAL, "plade_register_keypoints: NULL cloud, params, T16, summary or result");
+        PLADE_REQUIRE(n_t >= 1 && n_s >= 1, PLADE_EINVAL, "plade_register_keypoints: an empty cloud (n = 0)");
+        plade_feature_match_params mp;
+        if (match) mp = *match; else plade_feature_match_default_params(&mp);
+        CorrPoseWork &W = work_of(ctx);
+        float tmn[3], tmx[3], smn[3], smx[3];
+        upload_rows(ctx, W.in_t, tgt_pos_nrm, n_t, 6, tmn, tmx);         // (the bounding box checks the coordinates)
+        upload_rows(ctx, W.in_s, src_pos_nrm, n_s, 6, smn, smx);
+        return register_keypoints_dev(ctx, W, W.in_t.p, n_t, tmn, tmx, W.in_s.p, n_s, smn, smx, *iss, *fpfh, mp, *pose, T16, iss_summary,
+                                      src_summary, tgt_summary, result, corr_out, cap, n_corr);
+    });
+}
+
+extern "C" int plade_register_keypoints_dev(plade_ctx *ctx, plade_cloud *tgt, plade_cloud *src, const plade_iss_params *iss,
+                                            const plade_fpfh_params *fpfh, const plade_feature_match_params *match,
+                                            const plade_corr_pose_params *pose, float *T16, plade_iss_summary *iss_summary,
+                                            plade_fpfh_summary *src_summary, plade_fpfh_summary *tgt_summary,
+                                            plade_corr_pose_result *result, int32_t *corr_out, uint64_t cap, uint64_t *n_corr) {
+    return guarded(ctx, [&]() -> int {
+        PLADE_REQUIRE(tgt && src && iss && fpfh && pose && T16 && iss_summary && src_summary && tgt_summary && result, PLADE_EINVAL,
+                      "plade_register_keypoints_dev: NULL cloud, params, T16, summary or result");
+        plade_feature_match_params mp;
+        if (match) mp = *match; else plade_feature_match_default_params(&mp);
+        const CloudDev &t = tgt->dev, &s = src->dev;
+        return register_keypoints_dev(ctx, work_of(ctx), t.aos.p, t.n, t.bbmin, t.bbmax, s.aos.p, s.n, s.bbmin, s.bbmax, *iss, *fpfh, mp,
+                                      *pose, T16, iss_summary, src_summary, tgt_summary, result, corr_out, cap, n_corr);
     });
 }

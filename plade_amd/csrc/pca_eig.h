@@ -59,4 +59,29 @@ __device__ __forceinline__ bool pca_eig(double c00, double c01, double c02, doub
     return true;
 }
 
+// The three eigenvalues l1 >= l2 >= l3 of the same matrix by the same closed form (the keypoint detector, k_keypoints.hip): q, p2,
+// pp, r and phi exactly as above; the largest and the smallest root from the cosine, the middle one from the trace; then ordered
+// (rounding can swap two that nearly coincide).  p2 = 0: all three are q.
+__device__ __forceinline__ void sym3_eigenvalues(double c00, double c01, double c02, double c11, double c12, double c22, double &l1,
+                                                 double &l2, double &l3) {
+    const double tr = c00 + c11 + c22, q = tr / 3.0;
+    const double b00 = c00 - q, b11 = c11 - q, b22 = c22 - q;
+    const double p2 = b00 * b00 + b11 * b11 + b22 * b22 + 2.0 * (c01 * c01 + c02 * c02 + c12 * c12);
+    double lmax = q, lmid = q, lmin = q;
+    if (p2 > 0.0) {
+        const double pp = sqrt(p2 / 6.0);
+        const double i00 = b00 / pp, i11 = b11 / pp, i22 = b22 / pp, i01 = c01 / pp, i02 = c02 / pp, i12 = c12 / pp;
+        double r = 0.5 * (i00 * (i11 * i22 - i12 * i12) - i01 * (i01 * i22 - i12 * i02) + i02 * (i01 * i12 - i11 * i02));
+        r = fmin(1.0, fmax(-1.0, r));
+        const double phi = acos(r) / 3.0;
+        lmax = q + 2.0 * pp * cos(phi);
+        lmin = q + 2.0 * pp * cos(phi + 2.0943951023931954923);
+        lmid = tr - lmax - lmin;
+    }
+    const double hi = fmax(lmax, lmid), lo = fmin(lmax, lmid);
+    l1 = fmax(hi, lmin);
+    l3 = fmin(lo, lmin);
+    l2 = fmax(lo, fmin(hi, lmin));
+}
+
 }  // namespace plade

@@ -191,6 +191,30 @@ bool register_by_features(Eigen::Matrix4f &transformation, pcl::PointCloud<pcl::
                           PoseEstimate *info = nullptr, std::vector<std::pair<int, int>> *correspondences = nullptr, int min_inliers = 3,
                           int hypotheses = 65536, int min_pairs = 5, uint64_t seed = 0);
 
+/** Keypoints (no counterpart in the reference): the fields of plade_iss_summary (include/plade_hip.h). */
+struct KeypointDetection {
+    uint64_t n = 0, salient = 0, keypoints = 0;   // points, those that pass the eigenvalue tests, those that survive the suppression
+    uint32_t max_count = 0;                       // the largest number of points within salient_radius of a point
+};
+/** ISS keypoints on the GPU (plade_cloud_keypoints_iss): `keypoints` receives, ascending, the points of `cloud` whose neighbourhood
+ *  within salient_radius (absolute) varies in all three directions -- the eigenvalues l1 >= l2 >= l3 of its scatter about the point
+ *  satisfy l2 < gamma21 l1, l3 < gamma32 l2 and l3 > 1e-9 l1 -- that have at least min_neighbours other points within
+ *  non_max_radius (0: salient_radius) and the largest l3 among them.  Normals are not used.  false: invalid input or no GPU; a
+ *  message is printed, `keypoints` and `info` are unchanged. */
+bool detect_keypoints(pcl::PointCloud<pcl::PointNormal>::Ptr cloud, double salient_radius, std::vector<int> &keypoints,
+                      KeypointDetection *info = nullptr, double non_max_radius = 0.0, int min_neighbours = 5, double gamma21 = 0.975,
+                      double gamma32 = 0.975);
+/** register_by_features with the detector in front of the match, in one call on the GPU (plade_register_keypoints): only the
+ *  source's keypoints are matched, against every described target point, so the match costs a few per cent of the full one.
+ *  `correspondences` (optional) receives the matched pairs in the clouds' own indices, `detection` the detector's summary.  false as
+ *  there, with every output unchanged.  The CLI does this in place of register_by_features when
+ *  PLADE_FEATURE_KEYPOINTS=<salient_radius>[,<non_max_radius>[,<min_neighbours>]] is set next to PLADE_FEATURE_REGISTER. */
+bool register_by_keypoints(Eigen::Matrix4f &transformation, pcl::PointCloud<pcl::PointNormal>::Ptr target_cloud,
+                           pcl::PointCloud<pcl::PointNormal>::Ptr source_cloud, double radius, double inlier_dist, double salient_radius,
+                           PoseEstimate *info = nullptr, KeypointDetection *detection = nullptr,
+                           std::vector<std::pair<int, int>> *correspondences = nullptr, double non_max_radius = 0.0, int min_neighbours = 5,
+                           int min_inliers = 3, int hypotheses = 65536, int min_pairs = 5, uint64_t seed = 0);
+
 /** Merging registered clouds (no counterpart in the reference): the fields of plade_merge_summary (include/plade_hip.h). */
 struct CloudMerge {
     uint64_t n_in = 0, n_out = 0, n_shared = 0;   // points in, rows out, rows to which two or more clouds contributed

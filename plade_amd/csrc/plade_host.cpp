@@ -498,19 +498,93 @@ int register_features_packed(plade_ctx *ctx, float *T16, const float *tg, size_t
     if (corr) corr->resize(rc == PLADE_OK || rc == PLADE_EFAIL ? 2 * (size_t)m : 0);
     return rc;
 }
+
+// PLADE_FEATURE_KEYPOINTS=<salient_radius>[,<non_max_radius>[,<min_neighbours>]] (opt-in, absolute, in the clouds' units; it acts only
+// together with PLADE_FEATURE_REGISTER): the pair whose plane registration failed goes through plade_register_keypoints instead of
+// plade_register_features -- the ISS keypoints of the source (non_max_radius = salient_radius and min_neighbours 5 when not given)
+// are what is matched against the target's descriptors -- and one more console line, in front of the feature registration's, reports
+// the keypoints.  A value that does not parse (a radius not positive and finite, min_neighbours not an integer >= 1, anything behind
+// them) prints one warning and is ignored; unset, nothing changes.
+struct KeypointSwitch { bool on = false; double salient_radius = 0.0, non_max_radius = 0.0; int min_neighbours = 5; };
+const KeypointSwitch &keypoint_switch() {
+    static const KeypointSwitch sw = [] {
+        KeypointSwitch v, off;
+        const char *w = getenv("PLADE_FEATURE_KEYPOINTS");
+        if (!w) return off;
+        const auto radius_ok = [](double r) {
+            const float rf = (float)r;
+            return std::isfinite(r) && rf > 0.f && std::isfinite(rf * rf) && rf * rf >= FLT_MIN;
+        };
+        char *end = nullptr;
+        v.salient_radius = strtod(w, &end);
+        bool ok = end != w && radius_ok(v.salient_radius);
+        if (ok && *end == ',') {
+            const char *a = end + 1;
+            v.non_max_radius = strtod(a, &end);
+            ok = end != a && radius_ok(v.non_max_radius);
+            if (ok && *end == ',') {
+                a = end + 1;
+                const long m = strtol(a, &end, 10);
+                ok = end != a && m >= 1 && m <= INT32_MAX;
+                v.min_neighbours = (int)m;
+            }
+        }
+        if (!ok || *end != '\0') {
+            std::cerr << "warning: PLADE_FEATURE_KEYPOINTS=" << w
+                      << " is not <salient_radius>[,<non_max_radius>[,<min_neighbours>]] with both radii > 0 and min_neighbours >= 1;"
+                         " no keypoints"
+                      << std::endl;
+            return off;
+        }
+        v.on = true;
+        return v;
+    }();
+    return sw;
+}
+// ISS on the source, FPFH of both clouds, the keypoints' match and the pose of a packed pair in one call.  rc as above
+int register_keypoints_packed(plade_ctx *ctx, float *T16, const float *tg, size_t n_t, const float *sr, size_t n_s, double salient_radius,
+                              double non_max_radius, int min_neighbours, double radius, int min_pairs, double inlier_dist, int min_inliers,
+                              int hypotheses, uint64_t seed, plade_iss_summary &ks, plade_corr_pose_result &res, std::vector<int32_t> *corr,
+                              uint64_t &m) {
+    plade_iss_params ip;
+    plade_iss_default_params(&ip);
+    ip.salient_radius = salient_radius; ip.non_max_radius = non_max_radius; ip.min_neighbours = min_neighbours;
+    plade_fpfh_params fp;
+    plade_fpfh_default_params(&fp);
+    fp.radius = radius; fp.min_pairs = min_pairs;
+    plade_corr_pose_params pp;
+    plade_corr_pose_default_params(&pp);
+    pp.inlier_dist = inlier_dist; pp.min_inliers = min_inliers; pp.hypotheses = hypotheses; pp.seed = seed;
+    plade_fpfh_summary ss, st;
+    if (corr) corr->resize(2 * n_s);
+    trace("keypoint registration: detecting, describing, matching, estimating");
+    const int rc = plade_register_keypoints(ctx, tg, (uint32_t)n_t, sr, (uint32_t)n_s, &ip, &fp, nullptr, &pp, T16, &ks, &ss, &st, &res,
+                                            corr ? corr->data() : nullptr, n_s, &m);
+    trace("keypoint registration: done");
+    if (corr) corr->resize(rc == PLADE_OK || rc == PLADE_EFAIL ? 2 * (size_t)m : 0);
+    return rc;
+}
 // the second chance of a pair without planes; true: T16 holds the pose and the pair counts as registered
 bool feature_register(plade_ctx *ctx, float *T16, const float *tg, size_t n_t, const float *sr, size_t n_s) {
     const FeatureRegisterSwitch &sw = feature_register_switch();
+    const KeypointSwitch &kp = keypoint_switch();
     if (!sw.on || !ctx) return false;
     plade_corr_pose_result res;
+    plade_iss_summary ks;
     uint64_t m = 0;
-    const int rc = register_features_packed(ctx, T16, tg, n_t, sr, n_s, sw.radius, 5, sw.inlier_dist, sw.min_inliers, sw.hypotheses, 0, res,
-                                            nullptr, m);
+    const int rc = kp.on ? register_keypoints_packed(ctx, T16, tg, n_t, sr, n_s, kp.salient_radius, kp.non_max_radius, kp.min_neighbours,
+                                                     sw.radius, 5, sw.inlier_dist, sw.min_inliers, sw.hypotheses, 0, ks, res, nullptr, m)
+                         : register_features_packed(ctx, T16, tg, n_t, sr, n_s, sw.radius, 5, sw.inlier_dist, sw.min_inliers, sw.hypotheses,
+                                                    0, res, nullptr, m);
     if (rc != PLADE_OK) {
         con_err() << "feature registration failed as well: " << plade_last_error(ctx) << std::endl;
         return false;
     }
     char b[200];
+    if (kp.on) {
+        snprintf(b, sizeof(b), "keypoints: %llu of %llu source points", (unsigned long long)ks.keypoints, (unsigned long long)ks.n);
+        con_out() << b << std::endl;
+    }
     snprintf(b, sizeof(b), "feature registration: %u of %llu correspondences, rmse %.6g", res.inliers, (unsigned long long)m, res.rmse);
     con_out() << b << std::endl;
     return true;
@@ -1286,6 +1360,64 @@ bool register_by_features(Eigen::Matrix4f &transformation, pcl::PointCloud<pcl::
     }
     to_matrix(T16, transformation);
     fill_pose_estimate(info, res, m);
+    if (correspondences) {
+        std::vector<std::pair<int, int>> out(corr.size() / 2);
+        for (size_t k = 0; k < out.size(); ++k) out[k] = {corr[2 * k], corr[2 * k + 1]};
+        correspondences->swap(out);
+    }
+    return true;
+}
+
+// keypoints, and the registration from the keypoints' features: see plade.h
+bool detect_keypoints(pcl::PointCloud<pcl::PointNormal>::Ptr cloud, double salient_radius, std::vector<int> &keypoints,
+                      KeypointDetection *info, double non_max_radius, int min_neighbours, double gamma21, double gamma32) {
+    plade_ctx *ctx = context();
+    if (!ctx) return false;
+    if (!cloud) { con_err() << "detect_keypoints: null cloud" << std::endl; return false; }
+    std::vector<float> rows = flatten(*cloud);
+    plade_iss_params ip;
+    plade_iss_default_params(&ip);
+    ip.salient_radius = salient_radius; ip.non_max_radius = non_max_radius; ip.min_neighbours = min_neighbours;
+    ip.gamma21 = gamma21; ip.gamma32 = gamma32;
+    std::vector<uint32_t> index(cloud->size());
+    uint64_t k = 0;
+    plade_iss_summary s;
+    trace("keypoints: detecting");
+    const int rc = plade_cloud_keypoints_iss(ctx, rows.data(), (uint32_t)cloud->size(), 6, &ip, nullptr, index.data(), index.size(), &k,
+                                             nullptr, nullptr, nullptr, nullptr, nullptr, &s);
+    trace("keypoints: done");
+    if (rc != PLADE_OK) {
+        con_err() << "keypoint detection failed: " << plade_last_error(ctx) << std::endl;
+        return false;
+    }
+    std::vector<int> out(index.begin(), index.begin() + (size_t)k);
+    keypoints.swap(out);
+    if (info) { info->n = s.n; info->salient = s.salient; info->keypoints = s.keypoints; info->max_count = s.max_count; }
+    return true;
+}
+bool register_by_keypoints(Eigen::Matrix4f &transformation, pcl::PointCloud<pcl::PointNormal>::Ptr target_cloud,
+                           pcl::PointCloud<pcl::PointNormal>::Ptr source_cloud, double radius, double inlier_dist, double salient_radius,
+                           PoseEstimate *info, KeypointDetection *detection, std::vector<std::pair<int, int>> *correspondences,
+                           double non_max_radius, int min_neighbours, int min_inliers, int hypotheses, int min_pairs, uint64_t seed) {
+    plade_ctx *ctx = context();
+    if (!ctx) return false;
+    if (!target_cloud || !source_cloud) { con_err() << "register_by_keypoints: null cloud" << std::endl; return false; }
+    std::vector<float> tg = flatten(*target_cloud), sr = flatten(*source_cloud);
+    plade_corr_pose_result res;
+    plade_iss_summary ks;
+    std::vector<int32_t> corr;
+    uint64_t m = 0;
+    float T16[16];
+    const int rc = register_keypoints_packed(ctx, T16, tg.data(), target_cloud->size(), sr.data(), source_cloud->size(), salient_radius,
+                                             non_max_radius, min_neighbours, radius, min_pairs, inlier_dist, min_inliers, hypotheses, seed, ks,
+                                             res, correspondences ? &corr : nullptr, m);
+    if (rc != PLADE_OK) {
+        con_err() << "keypoint registration failed: " << plade_last_error(ctx) << std::endl;
+        return false;
+    }
+    to_matrix(T16, transformation);
+    fill_pose_estimate(info, res, m);
+    if (detection) { detection->n = ks.n; detection->salient = ks.salient; detection->keypoints = ks.keypoints; detection->max_count = ks.max_count; }
     if (correspondences) {
         std::vector<std::pair<int, int>> out(corr.size() / 2);
         for (size_t k = 0; k < out.size(); ++k) out[k] = {corr[2 * k], corr[2 * k + 1]};

@@ -8,7 +8,8 @@ ARCH  ?= gfx950
 CSRC := plade_amd/csrc
 HIP_SRCS := $(wildcard $(CSRC)/*.hip)
 HIP_OBJS := $(patsubst $(CSRC)/%.hip,build/%.o,$(HIP_SRCS))
-HIP_HDRS := $(wildcard $(CSRC)/*.h) $(wildcard $(CSRC)/*.cuh) include/plade_hip.h
+# (cli_switches.h is the CLI's alone: an edit to it rebuilds no object of the library)
+HIP_HDRS := $(filter-out $(CSRC)/cli_switches.h,$(wildcard $(CSRC)/*.h)) $(wildcard $(CSRC)/*.cuh) include/plade_hip.h
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -Iinclude -I$(CSRC) -Wno-unused-result
 
 all: lib oracle cli
@@ -30,7 +31,7 @@ plade_amd/libplade_hip.so: $(HIP_OBJS) build/ply_reader.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^
 
 HOST_SRCS := $(CSRC)/main.cpp $(CSRC)/plade_host.cpp
-plade_amd/PLADE: $(HOST_SRCS) $(CSRC)/plade.h $(CSRC)/plade_compat.h $(CSRC)/ply_reader.h plade_amd/libplade_hip.so
+plade_amd/PLADE: $(HOST_SRCS) $(CSRC)/plade.h $(CSRC)/plade_compat.h $(CSRC)/ply_reader.h $(CSRC)/cli_switches.h plade_amd/libplade_hip.so
 	$(CXX) -O2 -std=c++17 -pthread -Iinclude -I$(CSRC) $(HOST_SRCS) -o $@ -Lplade_amd -lplade_hip -Wl,-rpath,'$$ORIGIN'
 
 oracle/libplade_oracle.so: oracle/plade_oracle.cpp oracle/plade_oracle.h oracle/orc_math.h

@@ -2,10 +2,10 @@
 // PlaneExtraction::detect, load_ply_cloud) on top of the C ABI of libplade_hip.so.  Console messages,
 // return values and the swap/invert rule follow code/PLADE/plade.cpp:583-706.
 #include "plade.h"
+#include "cli_switches.h"
 #include "plade_hip.h"
 #include "ply_reader.h"
 
-#include <cfloat>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -37,6 +37,15 @@ void trace(const char *what) {
     char b[160];
     snprintf(b, sizeof(b), "[plade %8.3f s] %s\n", trace_now(), what);
     std::cerr << b << std::flush;
+}
+
+// The list-valued switches (cli_switches.h parses them): each is read once per process, where it is first needed, and what the
+// parser has to say about a rejected value goes to std::cerr, not to the calling thread's console.
+using cli_switches::GicpSwitch; using cli_switches::M3c2Switch; using cli_switches::FpfhSwitch; using cli_switches::FeatureRegisterSwitch;
+using cli_switches::KeypointSwitch; using cli_switches::OutlierSwitch; using cli_switches::ComponentSwitch; using cli_switches::SmoothSwitch;
+template <class S> S latched(const cli_switches::Parsed<S> &p) {
+    if (!p.warning.empty()) std::cerr << p.warning << std::endl;
+    return p.value;
 }
 
 plade_ctx *context() {
@@ -90,8 +99,26 @@ std::vector<float> flatten(const pcl::PointCloud<pcl::PointNormal> &c) {
     return a;
 }
 
+void unflatten(const float *rows, size_t n, pcl::PointCloud<pcl::PointNormal> &c) {
+    c.resize(n);
+    for (size_t i = 0; i < n; ++i) {
+        const float *p = rows + 6 * i;
+        c.at(i) = pcl::PointNormal(p[0], p[1], p[2], p[3], p[4], p[5]);
+    }
+}
+
 void to_matrix(const float *T16, Eigen::Matrix<float, 4, 4> &m) {
     for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) m(r, c) = T16[4 * r + c];
+}
+void to_T16(const Eigen::Matrix<float, 4, 4> &m, float *T16) {
+    for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) T16[4 * r + c] = m(r, c);
+}
+
+// the library's correspondence array (source, target, source, target, ...) as the C++ API hands it out
+std::vector<std::pair<int, int>> to_pairs(const std::vector<int32_t> &corr) {
+    std::vector<std::pair<int, int>> out(corr.size() / 2);
+    for (size_t k = 0; k < out.size(); ++k) out[k] = {corr[2 * k], corr[2 * k + 1]};
+    return out;
 }
 
 void pack_planes(const std::vector<PLANE> &planes, std::vector<float> &coef, std::vector<int32_t> &off, std::vector<int32_t> &idx) {
@@ -166,27 +193,9 @@ bool refine_packed(plade_ctx *ctx, float *T16, const float *tg, size_t n_t, cons
 // warning.  A value that does not parse prints one warning and refines nothing.  With PLADE_REFINE_ICP also set, this is the
 // refinement that runs, and one warning says so.  Unset, nothing changes.  The variable is read when the first pair has registered
 // (like PLADE_EVALUATE): the warnings appear there, once per process.
-struct GicpSwitch { bool on = false; double epsilon = 0.0; };
 const GicpSwitch &refine_gicp_switch() {
     static const GicpSwitch sw = [] {
-        GicpSwitch g;
-        const char *w = getenv("PLADE_REFINE_GICP");
-        if (!w) return g;
-        char *end = nullptr;
-        const long on = strtol(w, &end, 10);
-        double eps = 0.0;
-        bool ok = end != w && (on == 0 || on == 1);
-        if (ok && *end == ',') {
-            const char *v = end + 1;
-            eps = strtod(v, &end);
-            ok = end != v && std::isfinite(eps) && eps > 0.0 && eps <= 1.0;
-        }
-        if (!ok || *end != '\0') {
-            std::cerr << "warning: PLADE_REFINE_GICP=" << w << " is not 0, 1 or 1,<epsilon> with 0 < epsilon <= 1; no refinement" << std::endl;
-            return g;
-        }
-        g.on = on == 1;
-        g.epsilon = eps;
+        const GicpSwitch g = latched(cli_switches::parse_refine_gicp(getenv("PLADE_REFINE_GICP")));
         if (g.on && refine_icp_on())
             std::cerr << "warning: PLADE_REFINE_ICP and PLADE_REFINE_GICP are both set; the plane-to-plane refinement runs" << std::endl;
         return g;
@@ -226,18 +235,7 @@ void refine_selected(plade_ctx *ctx, float *T16, const float *tg, size_t n_t, co
 // The pair is evaluated as it was registered (after the target / source switch).  A value that is not a positive finite number
 // prints one warning and evaluates nothing; unset, nothing changes.
 float evaluate_dist() {
-    static const float d = [] {
-        const char *w = getenv("PLADE_EVALUATE");
-        if (!w) return 0.f;
-        char *end = nullptr;
-        const double v = strtod(w, &end);
-        const float f = (float)v;
-        if (end == w || *end != '\0' || !std::isfinite(f) || !(f > 0.f)) {
-            std::cerr << "warning: PLADE_EVALUATE=" << w << " is not a positive finite distance; no evaluation" << std::endl;
-            return 0.f;
-        }
-        return f;
-    }();
+    static const float d = latched(cli_switches::parse_evaluate(getenv("PLADE_EVALUATE")));
     return d;
 }
 bool evaluate_packed(plade_ctx *ctx, const float *T16, const float *tg, size_t n_t, const float *sr, size_t n_s, float max_dist,
@@ -267,40 +265,8 @@ void evaluate_line(plade_ctx *ctx, const float *T16, const float *tg, size_t n_t
 // given) and one console line reports the library's summary.  The pair is compared as it was registered (after the target / source
 // switch).  A value that does not parse (radius or depth not positive and finite, min_points not an integer >= 2, reg_error negative
 // or not finite, anything behind them) prints one warning and compares nothing; unset, nothing changes.
-struct M3c2Switch { bool on = false; double radius = 0.0, depth = 0.0, reg_error = 0.0; int min_points = 4; };
 const M3c2Switch &m3c2_switch() {
-    static const M3c2Switch sw = [] {
-        M3c2Switch v, off;
-        const char *w = getenv("PLADE_M3C2");
-        if (!w) return off;
-        char *end = nullptr;
-        v.radius = strtod(w, &end);
-        bool ok = end != w && std::isfinite(v.radius) && v.radius > 0.0 && std::isfinite(v.radius * v.radius) && *end == ',';
-        if (ok) {
-            const char *a = end + 1;
-            v.depth = strtod(a, &end);
-            ok = end != a && std::isfinite(v.depth) && v.depth > 0.0;
-        }
-        if (ok && *end == ',') {
-            const char *a = end + 1;
-            const long m = strtol(a, &end, 10);
-            ok = end != a && m >= 2 && m <= INT32_MAX;
-            v.min_points = (int)m;
-            if (ok && *end == ',') {
-                a = end + 1;
-                v.reg_error = strtod(a, &end);
-                ok = end != a && std::isfinite(v.reg_error) && v.reg_error >= 0.0;
-            }
-        }
-        if (!ok || *end != '\0') {
-            std::cerr << "warning: PLADE_M3C2=" << w
-                      << " is not <radius>,<depth>[,<min_points>[,<reg_error>]] with radius > 0, depth > 0, min_points >= 2 and reg_error >= 0; no comparison"
-                      << std::endl;
-            return off;
-        }
-        v.on = true;
-        return v;
-    }();
+    static const M3c2Switch sw = latched(cli_switches::parse_m3c2(getenv("PLADE_M3C2")));
     return sw;
 }
 // M3C2 of the packed source under T16 against the packed reference at the given core points (all x y z nx ny nz rows); dist: one
@@ -337,37 +303,8 @@ void m3c2_line(plade_ctx *ctx, const float *T16, const float *tg, size_t n_t, co
 // final transformation (a host loop in fp64).  The pair is described as it was registered (after the target / source switch).  A
 // value that does not parse (radius not positive and finite, min_pairs not an integer >= 1, max_ratio negative or not finite,
 // anything behind them) prints one warning and does nothing; unset, nothing changes.
-struct FpfhSwitch { bool on = false; double radius = 0.0; int min_pairs = 5; float max_ratio = 0.f; };
 const FpfhSwitch &fpfh_switch() {
-    static const FpfhSwitch sw = [] {
-        FpfhSwitch v, off;
-        const char *w = getenv("PLADE_FPFH_MATCH");
-        if (!w) return off;
-        char *end = nullptr;
-        v.radius = strtod(w, &end);
-        const float rf = (float)v.radius;
-        bool ok = end != w && std::isfinite(v.radius) && rf > 0.f && std::isfinite(rf * rf) && rf * rf >= FLT_MIN;
-        if (ok && *end == ',') {
-            const char *a = end + 1;
-            const long m = strtol(a, &end, 10);
-            ok = end != a && m >= 1 && m <= INT32_MAX;
-            v.min_pairs = (int)m;
-            if (ok && *end == ',') {
-                a = end + 1;
-                const double q = strtod(a, &end);
-                ok = end != a && std::isfinite(q) && q >= 0.0 && std::isfinite((float)q * (float)q);
-                v.max_ratio = (float)q;
-            }
-        }
-        if (!ok || *end != '\0') {
-            std::cerr << "warning: PLADE_FPFH_MATCH=" << w
-                      << " is not <radius>[,<min_pairs>[,<max_ratio>]] with radius > 0, min_pairs >= 1 and max_ratio >= 0; no descriptors"
-                      << std::endl;
-            return off;
-        }
-        v.on = true;
-        return v;
-    }();
+    static const FpfhSwitch sw = latched(cli_switches::parse_fpfh_match(getenv("PLADE_FPFH_MATCH")));
     return sw;
 }
 // FPFH of a packed cloud (x y z nx ny nz rows): desc receives n x 33 floats.  false: a message has been printed
@@ -439,45 +376,22 @@ void fpfh_line(plade_ctx *ctx, const float *T16, const float *tg, size_t n_t, co
 // EVALUATE / M3C2 / FPFH_MATCH / MERGE apply.  On failure the failure path runs as before, plus one line saying that the features
 // did not register the pair either.  A value that does not parse (radius or inlier_dist not positive and finite, min_inliers not an
 // integer >= 3, hypotheses not in 1 .. 2^24, anything behind them) prints one warning and does nothing; unset, nothing changes.
-struct FeatureRegisterSwitch { bool on = false; double radius = 0.0, inlier_dist = 0.0; int min_inliers = 3, hypotheses = 65536; };
 const FeatureRegisterSwitch &feature_register_switch() {
-    static const FeatureRegisterSwitch sw = [] {
-        FeatureRegisterSwitch v, off;
-        const char *w = getenv("PLADE_FEATURE_REGISTER");
-        if (!w) return off;
-        char *end = nullptr;
-        v.radius = strtod(w, &end);
-        const float rf = (float)v.radius;
-        bool ok = end != w && std::isfinite(v.radius) && rf > 0.f && std::isfinite(rf * rf) && rf * rf >= FLT_MIN && *end == ',';
-        if (ok) {
-            const char *a = end + 1;
-            v.inlier_dist = strtod(a, &end);
-            ok = end != a && std::isfinite(v.inlier_dist) && v.inlier_dist > 0.0 && std::isfinite(v.inlier_dist * v.inlier_dist) &&
-                 v.inlier_dist * v.inlier_dist > 0.0;
-            if (ok && *end == ',') {
-                a = end + 1;
-                const long m = strtol(a, &end, 10);
-                ok = end != a && m >= 3 && m <= INT32_MAX;
-                v.min_inliers = (int)m;
-                if (ok && *end == ',') {
-                    a = end + 1;
-                    const long h = strtol(a, &end, 10);
-                    ok = end != a && h >= 1 && h <= (1L << 24);
-                    v.hypotheses = (int)h;
-                }
-            }
-        }
-        if (!ok || *end != '\0') {
-            std::cerr << "warning: PLADE_FEATURE_REGISTER=" << w
-                      << " is not <radius>,<inlier_dist>[,<min_inliers>[,<hypotheses>]] with radius > 0, inlier_dist > 0, min_inliers >= 3"
-                         " and 1 <= hypotheses <= 16777216; no feature registration"
-                      << std::endl;
-            return off;
-        }
-        v.on = true;
-        return v;
-    }();
+    static const FeatureRegisterSwitch sw = latched(cli_switches::parse_feature_register(getenv("PLADE_FEATURE_REGISTER")));
     return sw;
+}
+// the library's defaults with the values the C++ API and the switches carry
+plade_corr_pose_params pose_params(double inlier_dist, int min_inliers, int hypotheses, uint64_t seed) {
+    plade_corr_pose_params pp;
+    plade_corr_pose_default_params(&pp);
+    pp.inlier_dist = inlier_dist; pp.min_inliers = min_inliers; pp.hypotheses = hypotheses; pp.seed = seed;
+    return pp;
+}
+plade_iss_params iss_params(double salient_radius, double non_max_radius, int min_neighbours) {
+    plade_iss_params ip;
+    plade_iss_default_params(&ip);
+    ip.salient_radius = salient_radius; ip.non_max_radius = non_max_radius; ip.min_neighbours = min_neighbours;
+    return ip;
 }
 // FPFH, match and pose of a packed pair in one call.  rc: the library's status (PLADE_EFAIL: the pose failed, T16 = identity)
 int register_features_packed(plade_ctx *ctx, float *T16, const float *tg, size_t n_t, const float *sr, size_t n_s, double radius,
@@ -486,9 +400,7 @@ int register_features_packed(plade_ctx *ctx, float *T16, const float *tg, size_t
     plade_fpfh_params fp;
     plade_fpfh_default_params(&fp);
     fp.radius = radius; fp.min_pairs = min_pairs;
-    plade_corr_pose_params pp;
-    plade_corr_pose_default_params(&pp);
-    pp.inlier_dist = inlier_dist; pp.min_inliers = min_inliers; pp.hypotheses = hypotheses; pp.seed = seed;
+    const plade_corr_pose_params pp = pose_params(inlier_dist, min_inliers, hypotheses, seed);
     plade_fpfh_summary ss, st;
     if (corr) corr->resize(2 * n_s);
     trace("feature registration: describing, matching, estimating");
@@ -505,40 +417,8 @@ int register_features_packed(plade_ctx *ctx, float *T16, const float *tg, size_t
 // are what is matched against the target's descriptors -- and one more console line, in front of the feature registration's, reports
 // the keypoints.  A value that does not parse (a radius not positive and finite, min_neighbours not an integer >= 1, anything behind
 // them) prints one warning and is ignored; unset, nothing changes.
-struct KeypointSwitch { bool on = false; double salient_radius = 0.0, non_max_radius = 0.0; int min_neighbours = 5; };
 const KeypointSwitch &keypoint_switch() {
-    static const KeypointSwitch sw = [] {
-        KeypointSwitch v, off;
-        const char *w = getenv("PLADE_FEATURE_KEYPOINTS");
-        if (!w) return off;
-        const auto radius_ok = [](double r) {
-            const float rf = (float)r;
-            return std::isfinite(r) && rf > 0.f && std::isfinite(rf * rf) && rf * rf >= FLT_MIN;
-        };
-        char *end = nullptr;
-        v.salient_radius = strtod(w, &end);
-        bool ok = end != w && radius_ok(v.salient_radius);
-        if (ok && *end == ',') {
-            const char *a = end + 1;
-            v.non_max_radius = strtod(a, &end);
-            ok = end != a && radius_ok(v.non_max_radius);
-            if (ok && *end == ',') {
-                a = end + 1;
-                const long m = strtol(a, &end, 10);
-                ok = end != a && m >= 1 && m <= INT32_MAX;
-                v.min_neighbours = (int)m;
-            }
-        }
-        if (!ok || *end != '\0') {
-            std::cerr << "warning: PLADE_FEATURE_KEYPOINTS=" << w
-                      << " is not <salient_radius>[,<non_max_radius>[,<min_neighbours>]] with both radii > 0 and min_neighbours >= 1;"
-                         " no keypoints"
-                      << std::endl;
-            return off;
-        }
-        v.on = true;
-        return v;
-    }();
+    static const KeypointSwitch sw = latched(cli_switches::parse_feature_keypoints(getenv("PLADE_FEATURE_KEYPOINTS")));
     return sw;
 }
 // ISS on the source, FPFH of both clouds, the keypoints' match and the pose of a packed pair in one call.  rc as above
@@ -546,15 +426,11 @@ int register_keypoints_packed(plade_ctx *ctx, float *T16, const float *tg, size_
                               double non_max_radius, int min_neighbours, double radius, int min_pairs, double inlier_dist, int min_inliers,
                               int hypotheses, uint64_t seed, plade_iss_summary &ks, plade_corr_pose_result &res, std::vector<int32_t> *corr,
                               uint64_t &m) {
-    plade_iss_params ip;
-    plade_iss_default_params(&ip);
-    ip.salient_radius = salient_radius; ip.non_max_radius = non_max_radius; ip.min_neighbours = min_neighbours;
+    const plade_iss_params ip = iss_params(salient_radius, non_max_radius, min_neighbours);
     plade_fpfh_params fp;
     plade_fpfh_default_params(&fp);
     fp.radius = radius; fp.min_pairs = min_pairs;
-    plade_corr_pose_params pp;
-    plade_corr_pose_default_params(&pp);
-    pp.inlier_dist = inlier_dist; pp.min_inliers = min_inliers; pp.hypotheses = hypotheses; pp.seed = seed;
+    const plade_corr_pose_params pp = pose_params(inlier_dist, min_inliers, hypotheses, seed);
     plade_fpfh_summary ss, st;
     if (corr) corr->resize(2 * n_s);
     trace("keypoint registration: detecting, describing, matching, estimating");
@@ -594,29 +470,8 @@ bool feature_register(plade_ctx *ctx, float *T16, const float *tg, size_t n_t, c
 // GPU (plade_filter_outliers: k nearest neighbours, threshold mu + alpha sigma, alpha 1 when not given) after they are read and
 // before PLADE_ESTIMATE_NORMALS; one console line per cloud.  A value that does not parse (k not an integer in [1, 64], alpha
 // negative or not finite, anything behind them) prints one warning and filters nothing; unset, nothing changes.
-struct OutlierSwitch { int k = 0; double alpha = 1.0; };
 const OutlierSwitch &remove_outliers_switch() {
-    static const OutlierSwitch sw = [] {
-        OutlierSwitch v;
-        const char *w = getenv("PLADE_REMOVE_OUTLIERS");
-        if (!w) return v;
-        char *end = nullptr;
-        const long k = strtol(w, &end, 10);
-        bool ok = end != w && k >= 0 && k <= 64;
-        double alpha = 1.0;
-        if (ok && *end == ',') {
-            const char *a = end + 1;
-            alpha = strtod(a, &end);
-            ok = end != a && std::isfinite(alpha) && alpha >= 0.0;
-        }
-        if (!ok || *end != '\0') {
-            std::cerr << "warning: PLADE_REMOVE_OUTLIERS=" << w << " is not <k>[,<alpha>] with k in [1, 64] and alpha >= 0; no outlier removal"
-                      << std::endl;
-            return v;
-        }
-        v.k = (int)k; v.alpha = alpha;
-        return v;
-    }();
+    static const OutlierSwitch sw = latched(cli_switches::parse_remove_outliers(getenv("PLADE_REMOVE_OUTLIERS")));
     return sw;
 }
 // the rows of an x y z nx ny nz array that pass the filter, in place (the normal columns, NaN included, keep their bits)
@@ -656,35 +511,8 @@ bool remove_outliers_in_place(std::vector<float> &buf) {
 // before PLADE_ESTIMATE_NORMALS; one console line per cloud.  A value that does not parse (radius negative or not finite, min_size
 // not an integer >= 1, keep_largest not an integer >= 0, anything behind them) prints one warning and filters nothing; unset,
 // nothing changes.
-struct ComponentSwitch { double radius = 0.0; int min_size = 1, keep_largest = 0; };
 const ComponentSwitch &keep_components_switch() {
-    static const ComponentSwitch sw = [] {
-        ComponentSwitch v, off;
-        const char *w = getenv("PLADE_KEEP_COMPONENTS");
-        if (!w) return off;
-        char *end = nullptr;
-        v.radius = strtod(w, &end);
-        bool ok = end != w && std::isfinite(v.radius) && v.radius >= 0.0 && std::isfinite((float)v.radius * (float)v.radius);
-        if (ok && *end == ',') {
-            const char *a = end + 1;
-            const long m = strtol(a, &end, 10);
-            ok = end != a && m >= 1 && m <= INT32_MAX;
-            v.min_size = (int)m;
-            if (ok && *end == ',') {
-                a = end + 1;
-                const long g = strtol(a, &end, 10);
-                ok = end != a && g >= 0 && g <= INT32_MAX;
-                v.keep_largest = (int)g;
-            }
-        }
-        if (!ok || *end != '\0') {
-            std::cerr << "warning: PLADE_KEEP_COMPONENTS=" << w
-                      << " is not <radius>[,<min_size>[,<keep_largest>]] with radius >= 0, min_size >= 1 and keep_largest >= 0; no component filter"
-                      << std::endl;
-            return off;
-        }
-        return v;
-    }();
+    static const ComponentSwitch sw = latched(cli_switches::parse_keep_components(getenv("PLADE_KEEP_COMPONENTS")));
     return sw;
 }
 // the rows of an x y z nx ny nz array whose component is kept, in place (the normal columns, NaN included, keep their bits)
@@ -725,29 +553,8 @@ bool keep_components_in_place(std::vector<float> &buf) {
 // keep their bits (a file without normals gets the k-NN normals of the smoothed positions); one console line per cloud.  A value
 // that does not parse (radius negative, not finite or so small that its fp32 square is below FLT_MIN, min_neighbours not an
 // integer >= 3, anything behind them) prints one warning and smooths nothing; unset, nothing changes.
-struct SmoothSwitch { double radius = 0.0; int min_neighbours = 6; };
 const SmoothSwitch &smooth_switch() {
-    static const SmoothSwitch sw = [] {
-        SmoothSwitch v, off;
-        const char *w = getenv("PLADE_SMOOTH");
-        if (!w) return off;
-        char *end = nullptr;
-        v.radius = strtod(w, &end);
-        const float r2 = (float)v.radius * (float)v.radius;   // 0 = off; otherwise what plade_smooth_cloud accepts
-        bool ok = end != w && std::isfinite(v.radius) && v.radius >= 0.0 && std::isfinite(r2) && (v.radius == 0.0 || r2 >= FLT_MIN);
-        if (ok && *end == ',') {
-            const char *a = end + 1;
-            const long m = strtol(a, &end, 10);
-            ok = end != a && m >= 3 && m <= INT32_MAX;
-            v.min_neighbours = (int)m;
-        }
-        if (!ok || *end != '\0') {
-            std::cerr << "warning: PLADE_SMOOTH=" << w << " is not <radius>[,<min_neighbours>] with radius >= 0 (its square not below FLT_MIN) and min_neighbours >= 3; no smoothing"
-                      << std::endl;
-            return off;
-        }
-        return v;
-    }();
+    static const SmoothSwitch sw = latched(cli_switches::parse_smooth(getenv("PLADE_SMOOTH")));
     return sw;
 }
 // the x y z columns of an x y z nx ny nz array smoothed in place; nrm: the fit's normals (n x 3) when wanted
@@ -789,18 +596,7 @@ bool smooth_in_place(std::vector<float> &buf) {
 // console line per pair.  The CLI names the result file (plade_set_thread_merge_output).  A value that is not a finite number
 // >= 0 prints one warning and merges nothing; unset, nothing changes.
 float merge_leaf() {   // < 0: off
-    static const float leaf = [] {
-        const char *w = getenv("PLADE_MERGE");
-        if (!w) return -1.f;
-        char *end = nullptr;
-        const double v = strtod(w, &end);
-        const float f = (float)v;
-        if (end == w || *end != '\0' || !std::isfinite(f) || !(f >= 0.f)) {
-            std::cerr << "warning: PLADE_MERGE=" << w << " is not a finite leaf size >= 0; no merge" << std::endl;
-            return -1.f;
-        }
-        return f;
-    }();
+    static const float leaf = latched(cli_switches::parse_merge(getenv("PLADE_MERGE")));
     return leaf;
 }
 thread_local std::string g_merge_result;   // the result file whose name the merged clouds take; empty: no merge
@@ -960,6 +756,21 @@ bool registration(Eigen::Matrix<float, 4, 4> &transformation, pcl::PointCloud<pc
 
 namespace {
 
+// What follows a pair's registration, after its caller has printed the library's error or "done. time:" -- the single-pair path
+// and the group share it.  A pair that did not register gets its second chance (PLADE_FEATURE_REGISTER: a pair without planes);
+// a registered pair the selected refinement and the evaluation, M3C2 and FPFH lines.  false: the pair stays unregistered
+bool pair_tail(plade_ctx *ctx, bool registered, float *T16, const float *tg, size_t n_t, const float *sr, size_t n_s) {
+    if (!registered && !feature_register(ctx, T16, tg, n_t, sr, n_s)) {
+        fpfh_line(ctx, nullptr, tg, n_t, sr, n_s);
+        return false;
+    }
+    refine_selected(ctx, T16, tg, n_t, sr, n_s);
+    evaluate_line(ctx, T16, tg, n_t, sr, n_s);
+    m3c2_line(ctx, T16, tg, n_t, sr, n_s);
+    fpfh_line(ctx, T16, tg, n_t, sr, n_s);
+    return true;
+}
+
 // body of registration(T, target, source) (plade.cpp:638-662) on packed x y z nx ny nz arrays
 bool register_packed(Eigen::Matrix<float, 4, 4> &transformation, const float *tg, size_t n_t, const float *sr, size_t n_s) {
     plade_ctx *ctx = context();
@@ -968,19 +779,18 @@ bool register_packed(Eigen::Matrix<float, 4, 4> &transformation, const float *tg
     float T16[16];
     Watch w;
     int rc = plade_registration(ctx, tg, (uint32_t)n_t, sr, (uint32_t)n_s, T16);
-    if (rc != PLADE_OK) {
-        con_err() << plade_last_error(ctx) << std::endl;
-        if (!feature_register(ctx, T16, tg, n_t, sr, n_s)) {      // (PLADE_FEATURE_REGISTER: a pair without planes)
-            fpfh_line(ctx, nullptr, tg, n_t, sr, n_s);
-            return false;
-        }
-    } else con_out() << "done. time: " << w.str() << std::endl;
-    refine_selected(ctx, T16, tg, n_t, sr, n_s);
-    if (evaluate_dist() > 0.f) evaluate_line(ctx, T16, tg, n_t, sr, n_s);
-    m3c2_line(ctx, T16, tg, n_t, sr, n_s);
-    fpfh_line(ctx, T16, tg, n_t, sr, n_s);
+    if (rc != PLADE_OK) con_err() << plade_last_error(ctx) << std::endl;
+    else con_out() << "done. time: " << w.str() << std::endl;
+    if (!pair_tail(ctx, rc == PLADE_OK, T16, tg, n_t, sr, n_s)) return false;
     to_matrix(T16, transformation);
     return true;
+}
+
+// what every cloud goes through once its file is read: the filters that are switched on, in their order, then the normals of a
+// file that had none (estimate).  false: a message has been printed
+bool prepare_loaded(const std::string &file_name, std::vector<float> &buf, bool estimate) {
+    if (!remove_outliers_in_place(buf) || !keep_components_in_place(buf) || !smooth_in_place(buf)) return false;
+    return !estimate || buf.empty() || estimate_in_place(file_name, buf);
 }
 
 // a PLY file straight into a packed array (no pcl::PointCloud in between: at GPU speeds the 48 B/point
@@ -994,9 +804,7 @@ bool load_packed(const std::string &file_name, std::vector<float> &buf) {
         return false;
     }
     for (auto &w : warnings) con_out() << w << std::endl;
-    if (!remove_outliers_in_place(buf) || !keep_components_in_place(buf) || !smooth_in_place(buf)) return false;
-    if (estimate && !buf.empty() && !estimate_in_place(file_name, buf)) return false;
-    return !buf.empty();
+    return prepare_loaded(file_name, buf, estimate) && !buf.empty();
 }
 
 }  // namespace
@@ -1093,10 +901,7 @@ void registration_group(size_t count, Eigen::Matrix<float, 4, 4> *transformation
     auto report = [&](const Loaded &l, const std::string &file, std::vector<float> &buf) {   // load_packed's messages
         if (!l.ok && !l.err.empty()) con_err() << l.err << std::endl;
         if (l.ok || l.err.empty()) for (auto &w : l.warnings) con_out() << w << std::endl;
-        if (l.ok && (!remove_outliers_in_place(buf) || !keep_components_in_place(buf) || !smooth_in_place(buf))) return false;
-        if (l.ok && buf.empty()) return false;
-        if (l.ok && l.estimate) return estimate_in_place(file, buf);
-        return l.ok;
+        return l.ok && prepare_loaded(file, buf, l.estimate) && !buf.empty();
     };
     for (size_t i = 0; i < count; ++i) {
         ok[i] = false;
@@ -1137,19 +942,15 @@ void registration_group(size_t count, Eigen::Matrix<float, 4, 4> *transformation
     for (uint32_t q = 0; q < k; ++q) {
         const Item &it = items[q];
         plade_set_thread_console(out ? out[it.pair] : nullptr, err ? err[it.pair] : nullptr);
-        if (rc != PLADE_OK || status[q] != PLADE_OK) {
+        const bool registered = rc == PLADE_OK && status[q] == PLADE_OK;
+        if (!registered) {
             const plade_ctx *pc = ctx ? (rc != PLADE_OK ? ctx : plade_pair_ctx(ctx, q)) : nullptr;
             if (pc) con_err() << plade_last_error(pc) << std::endl;
-            if (!feature_register(ctx, T16 + 16 * q, it.tg, it.n_t, it.sr, it.n_s)) {
-                fpfh_line(ctx, nullptr, it.tg, it.n_t, it.sr, it.n_s);
-                con_err() << "registration failed" << std::endl;
-                continue;
-            }
         } else con_out() << "done. time: " << w.str() << std::endl;
-        refine_selected(ctx, T16 + 16 * q, it.tg, it.n_t, it.sr, it.n_s);
-        if (evaluate_dist() > 0.f) evaluate_line(ctx, T16 + 16 * q, it.tg, it.n_t, it.sr, it.n_s);
-        m3c2_line(ctx, T16 + 16 * q, it.tg, it.n_t, it.sr, it.n_s);
-        fpfh_line(ctx, T16 + 16 * q, it.tg, it.n_t, it.sr, it.n_s);
+        if (!pair_tail(ctx, registered, T16 + 16 * q, it.tg, it.n_t, it.sr, it.n_s)) {
+            con_err() << "registration failed" << std::endl;
+            continue;
+        }
         to_matrix(T16 + 16 * q, transformations[it.pair]);
         if (it.switched) transformations[it.pair] = transformations[it.pair].inverse();
         if (merge_leaf() >= 0.f)
@@ -1167,7 +968,7 @@ bool refine_registration(Eigen::Matrix<float, 4, 4> &transformation, pcl::PointC
     if (!ctx) return false;
     std::vector<float> tg = flatten(*target_cloud), sr = flatten(*source_cloud);
     float T16[16];
-    for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) T16[4 * r + c] = transformation(r, c);
+    to_T16(transformation, T16);
     if (!refine_packed(ctx, T16, tg.data(), target_cloud->size(), sr.data(), source_cloud->size())) return false;
     to_matrix(T16, transformation);
     return true;
@@ -1180,7 +981,7 @@ bool refine_registration_gicp(Eigen::Matrix<float, 4, 4> &transformation, pcl::P
     if (!ctx) return false;
     std::vector<float> tg = flatten(*target_cloud), sr = flatten(*source_cloud);
     float T16[16];
-    for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) T16[4 * r + c] = transformation(r, c);
+    to_T16(transformation, T16);
     if (!refine_gicp_packed(ctx, T16, tg.data(), target_cloud->size(), sr.data(), source_cloud->size(), epsilon)) return false;
     to_matrix(T16, transformation);
     return true;
@@ -1193,7 +994,7 @@ bool evaluate_registration(const Eigen::Matrix4f &transformation, pcl::PointClou
     if (!ctx) return false;
     std::vector<float> tg = flatten(*target_cloud), sr = flatten(*source_cloud);
     float T16[16];
-    for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) T16[4 * r + c] = transformation(r, c);
+    to_T16(transformation, T16);
     plade_distance_summary s;
     if (!evaluate_packed(ctx, T16, tg.data(), target_cloud->size(), sr.data(), source_cloud->size(), max_dist, s)) return false;
     out.n = s.n; out.count = s.count; out.plane_count = s.plane_count;
@@ -1209,11 +1010,7 @@ bool remove_outliers(pcl::PointCloud<pcl::PointNormal>::Ptr cloud, pcl::PointClo
     std::vector<float> buf = flatten(*cloud);
     plade_outlier_summary s;
     if (!filter_packed(ctx, buf, k, alpha, s)) return false;
-    filtered.resize((size_t)s.kept);
-    for (size_t i = 0; i < (size_t)s.kept; ++i) {
-        const float *p = &buf[6 * i];
-        filtered.at(i) = pcl::PointNormal(p[0], p[1], p[2], p[3], p[4], p[5]);
-    }
+    unflatten(buf.data(), (size_t)s.kept, filtered);
     if (info) { info->n = s.n; info->kept = s.kept; info->mu = s.mu; info->sigma = s.sigma; info->threshold = s.threshold; }
     return true;
 }
@@ -1226,11 +1023,7 @@ bool keep_components(pcl::PointCloud<pcl::PointNormal>::Ptr cloud, pcl::PointClo
     std::vector<float> buf = flatten(*cloud);
     plade_component_summary s;
     if (!components_packed(ctx, buf, radius, min_size, max_size, keep_largest, s)) return false;
-    filtered.resize((size_t)s.kept);
-    for (size_t i = 0; i < (size_t)s.kept; ++i) {
-        const float *p = &buf[6 * i];
-        filtered.at(i) = pcl::PointNormal(p[0], p[1], p[2], p[3], p[4], p[5]);
-    }
+    unflatten(buf.data(), (size_t)s.kept, filtered);
     if (info) { info->n = s.n; info->components = s.components; info->kept_components = s.kept_components; info->kept = s.kept; info->largest = s.largest; }
     return true;
 }
@@ -1262,7 +1055,7 @@ bool compare_clouds(const Eigen::Matrix4f &transformation, pcl::PointCloud<pcl::
     if (!reference_cloud || !compared_cloud) { con_err() << "compare_clouds: null cloud" << std::endl; return false; }
     std::vector<float> ref = flatten(*reference_cloud), cmp = flatten(*compared_cloud);
     float T16[16];
-    for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) T16[4 * r + c] = transformation(r, c);
+    to_T16(transformation, T16);
     std::vector<double> dist(reference_cloud->size());
     plade_m3c2_summary s;
     if (!m3c2_packed(ctx, T16, ref.data(), reference_cloud->size(), ref.data(), reference_cloud->size(), cmp.data(), compared_cloud->size(),
@@ -1301,9 +1094,7 @@ bool match_features(const std::vector<float> &source_features, const std::vector
     if (!match_packed(ctx, source_features.data(), source_features.size() / 33, target_features.data(), target_features.size() / 33, mutual,
                       max_ratio, corr))
         return false;
-    std::vector<std::pair<int, int>> out(corr.size() / 2);
-    for (size_t k = 0; k < out.size(); ++k) out[k] = {corr[2 * k], corr[2 * k + 1]};
-    correspondences.swap(out);
+    correspondences = to_pairs(corr);
     return true;
 }
 
@@ -1326,9 +1117,7 @@ bool estimate_pose_from_correspondences(Eigen::Matrix4f &transformation, pcl::Po
     std::vector<float> tg = flatten(*target_cloud), sr = flatten(*source_cloud);
     std::vector<int32_t> corr(2 * correspondences.size());
     for (size_t k = 0; k < correspondences.size(); ++k) { corr[2 * k] = correspondences[k].first; corr[2 * k + 1] = correspondences[k].second; }
-    plade_corr_pose_params pp;
-    plade_corr_pose_default_params(&pp);
-    pp.inlier_dist = inlier_dist; pp.min_inliers = min_inliers; pp.hypotheses = hypotheses; pp.seed = seed;
+    const plade_corr_pose_params pp = pose_params(inlier_dist, min_inliers, hypotheses, seed);
     plade_corr_pose_result res;
     float T16[16];
     const int rc = plade_estimate_pose_corr(ctx, sr.data(), (uint32_t)source_cloud->size(), 6, tg.data(), (uint32_t)target_cloud->size(), 6,
@@ -1360,11 +1149,7 @@ bool register_by_features(Eigen::Matrix4f &transformation, pcl::PointCloud<pcl::
     }
     to_matrix(T16, transformation);
     fill_pose_estimate(info, res, m);
-    if (correspondences) {
-        std::vector<std::pair<int, int>> out(corr.size() / 2);
-        for (size_t k = 0; k < out.size(); ++k) out[k] = {corr[2 * k], corr[2 * k + 1]};
-        correspondences->swap(out);
-    }
+    if (correspondences) *correspondences = to_pairs(corr);
     return true;
 }
 
@@ -1375,9 +1160,7 @@ bool detect_keypoints(pcl::PointCloud<pcl::PointNormal>::Ptr cloud, double salie
     if (!ctx) return false;
     if (!cloud) { con_err() << "detect_keypoints: null cloud" << std::endl; return false; }
     std::vector<float> rows = flatten(*cloud);
-    plade_iss_params ip;
-    plade_iss_default_params(&ip);
-    ip.salient_radius = salient_radius; ip.non_max_radius = non_max_radius; ip.min_neighbours = min_neighbours;
+    plade_iss_params ip = iss_params(salient_radius, non_max_radius, min_neighbours);
     ip.gamma21 = gamma21; ip.gamma32 = gamma32;
     std::vector<uint32_t> index(cloud->size());
     uint64_t k = 0;
@@ -1418,11 +1201,7 @@ bool register_by_keypoints(Eigen::Matrix4f &transformation, pcl::PointCloud<pcl:
     to_matrix(T16, transformation);
     fill_pose_estimate(info, res, m);
     if (detection) { detection->n = ks.n; detection->salient = ks.salient; detection->keypoints = ks.keypoints; detection->max_count = ks.max_count; }
-    if (correspondences) {
-        std::vector<std::pair<int, int>> out(corr.size() / 2);
-        for (size_t k = 0; k < out.size(); ++k) out[k] = {corr[2 * k], corr[2 * k + 1]};
-        correspondences->swap(out);
-    }
+    if (correspondences) *correspondences = to_pairs(corr);
     return true;
 }
 
@@ -1450,11 +1229,7 @@ bool merge_clouds(const std::vector<pcl::PointCloud<pcl::PointNormal>::Ptr> &clo
     std::vector<float> rows;
     plade_merge_summary s;
     if (!merge_packed(ctx, (uint32_t)clouds.size(), ptr.data(), n.data(), T16.empty() ? nullptr : T16.data(), leaf, rows, s)) return false;
-    merged.resize((size_t)s.n_out);
-    for (size_t i = 0; i < (size_t)s.n_out; ++i) {
-        const float *p = &rows[6 * i];
-        merged.at(i) = pcl::PointNormal(p[0], p[1], p[2], p[3], p[4], p[5]);
-    }
+    unflatten(rows.data(), (size_t)s.n_out, merged);
     if (info) { info->n_in = s.n_in; info->n_out = s.n_out; info->n_shared = s.n_shared; info->max_count = s.max_count; }
     return true;
 }
@@ -1469,13 +1244,7 @@ bool load_ply_cloud(const std::string &file_name, pcl::PointCloud<pcl::PointNorm
         return false;
     }
     for (auto &w : warnings) con_out() << w << std::endl;
-    if (!remove_outliers_in_place(pos_nrm) || !keep_components_in_place(pos_nrm) || !smooth_in_place(pos_nrm)) return false;
-    if (estimate && !pos_nrm.empty() && !estimate_in_place(file_name, pos_nrm)) return false;
-    const size_t n = pos_nrm.size() / 6;
-    cloud.resize(n);
-    for (size_t i = 0; i < n; ++i) {
-        const float *p = &pos_nrm[6 * i];
-        cloud.at(i) = pcl::PointNormal(p[0], p[1], p[2], p[3], p[4], p[5]);
-    }
+    if (!prepare_loaded(file_name, pos_nrm, estimate)) return false;
+    unflatten(pos_nrm.data(), pos_nrm.size() / 6, cloud);
     return cloud.size() > 0;
 }

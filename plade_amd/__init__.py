@@ -392,30 +392,50 @@ def device_synchronize(device=0):
         raise PladeError(rc, "plade_device_synchronize failed")
 
 
+# the params struct -> the library's function that fills in its defaults
+_DEFAULTS = {Params: "plade_default_params",
+             IcpParams: "plade_icp_default_params",
+             OutlierParams: "plade_outlier_default_params",
+             ComponentParams: "plade_component_default_params",
+             SmoothParams: "plade_smooth_default_params",
+             M3c2Params: "plade_m3c2_default_params",
+             FpfhParams: "plade_fpfh_default_params",
+             FeatureMatchParams: "plade_feature_match_default_params",
+             CorrPoseParams: "plade_corr_pose_default_params",
+             IssParams: "plade_iss_default_params",
+             GicpParams: "plade_gicp_default_params"}
+
+
+def _defaults(struct):
+    prm = struct()
+    getattr(load_library(), _DEFAULTS[struct])(C.byref(prm))
+    return prm
+
+
+def _defaults_dict(struct):
+    """the defaults of a params struct as a dict of its fields (without `reserved`; an array field as a tuple)"""
+    prm = _defaults(struct)
+    vals = ((k, getattr(prm, k)) for k, _ in struct._fields_ if k != "reserved")
+    return {k: tuple(v) if isinstance(v, C.Array) else v for k, v in vals}
+
+
 def default_params():
     """plade_default_params (pure: needs no GPU): the library's shipped defaults = the reference's behaviour."""
-    prm = Params()
-    load_library().plade_default_params(C.byref(prm))
-    return prm
+    return _defaults(Params)
 
 
 def icp_default_params():
     """plade_icp_default_params (pure: needs no GPU) as a dict of the plade_icp_params fields."""
-    prm = IcpParams()
-    load_library().plade_icp_default_params(C.byref(prm))
-    return {k: getattr(prm, k) for k, _ in IcpParams._fields_}
+    return _defaults_dict(IcpParams)
 
 
 def outlier_default_params():
     """plade_outlier_default_params (pure: needs no GPU) as a dict of the plade_outlier_params fields."""
-    prm = OutlierParams()
-    load_library().plade_outlier_default_params(C.byref(prm))
-    return {k: getattr(prm, k) for k, _ in OutlierParams._fields_ if k != "reserved"}
+    return _defaults_dict(OutlierParams)
 
 
 def _outlier_params(mode, k, alpha, radius, min_neighbours):
-    prm = OutlierParams()
-    load_library().plade_outlier_default_params(C.byref(prm))
+    prm = _defaults(OutlierParams)
     if mode not in OUTLIER_MODES:
         raise ValueError(f"mode: 'statistical' or 'radius', got {mode!r}")
     prm.mode = OUTLIER_MODES[mode]
@@ -438,14 +458,11 @@ def _outlier_info(summ, keep):
 
 def component_default_params():
     """plade_component_default_params (pure: needs no GPU) as a dict of the plade_component_params fields."""
-    prm = ComponentParams()
-    load_library().plade_component_default_params(C.byref(prm))
-    return {k: getattr(prm, k) for k, _ in ComponentParams._fields_ if k != "reserved"}
+    return _defaults_dict(ComponentParams)
 
 
 def _component_params(radius, min_size, max_size, keep_largest):
-    prm = ComponentParams()
-    load_library().plade_component_default_params(C.byref(prm))
+    prm = _defaults(ComponentParams)
     prm.radius = float(radius)
     prm.min_size, prm.max_size, prm.keep_largest = int(min_size), int(max_size), int(keep_largest)
     return prm
@@ -463,14 +480,11 @@ def _component_info(summ, label, size, keep):
 
 def smooth_default_params():
     """plade_smooth_default_params (pure: needs no GPU) as a dict of the plade_smooth_params fields."""
-    prm = SmoothParams()
-    load_library().plade_smooth_default_params(C.byref(prm))
-    return {"radius": prm.radius, "min_neighbours": prm.min_neighbours, "viewpoint": tuple(prm.viewpoint)}
+    return _defaults_dict(SmoothParams)
 
 
 def _smooth_params(radius, min_neighbours, viewpoint):
-    prm = SmoothParams()
-    load_library().plade_smooth_default_params(C.byref(prm))
+    prm = _defaults(SmoothParams)
     prm.radius = float(radius)
     if min_neighbours is not None:
         prm.min_neighbours = int(min_neighbours)
@@ -484,14 +498,11 @@ def _smooth_info(summ):
 
 def m3c2_default_params():
     """plade_m3c2_default_params (pure: needs no GPU) as a dict of the plade_m3c2_params fields."""
-    prm = M3c2Params()
-    load_library().plade_m3c2_default_params(C.byref(prm))
-    return {k: getattr(prm, k) for k, _ in M3c2Params._fields_ if k != "reserved"}
+    return _defaults_dict(M3c2Params)
 
 
 def _m3c2_params(radius, depth, min_points, reg_error):
-    prm = M3c2Params()
-    load_library().plade_m3c2_default_params(C.byref(prm))
+    prm = _defaults(M3c2Params)
     prm.radius, prm.depth, prm.reg_error = float(radius), float(depth), float(reg_error)
     if min_points is not None:
         prm.min_points = int(min_points)
@@ -500,35 +511,26 @@ def _m3c2_params(radius, depth, min_points, reg_error):
 
 def fpfh_default_params():
     """plade_fpfh_default_params (pure: needs no GPU) as a dict of the plade_fpfh_params fields."""
-    prm = FpfhParams()
-    load_library().plade_fpfh_default_params(C.byref(prm))
-    return {k: getattr(prm, k) for k, _ in FpfhParams._fields_ if k != "reserved"}
+    return _defaults_dict(FpfhParams)
 
 
 def feature_match_default_params():
     """plade_feature_match_default_params (pure: needs no GPU) as a dict."""
-    prm = FeatureMatchParams()
-    load_library().plade_feature_match_default_params(C.byref(prm))
-    return {k: getattr(prm, k) for k, _ in FeatureMatchParams._fields_}
+    return _defaults_dict(FeatureMatchParams)
 
 
 def corr_pose_default_params():
     """plade_corr_pose_default_params (pure: needs no GPU) as a dict of the plade_corr_pose_params fields."""
-    prm = CorrPoseParams()
-    load_library().plade_corr_pose_default_params(C.byref(prm))
-    return {k: getattr(prm, k) for k, _ in CorrPoseParams._fields_ if k != "reserved"}
+    return _defaults_dict(CorrPoseParams)
 
 
 def iss_default_params():
     """plade_iss_default_params (pure: needs no GPU) as a dict of the plade_iss_params fields."""
-    prm = IssParams()
-    load_library().plade_iss_default_params(C.byref(prm))
-    return {k: getattr(prm, k) for k, _ in IssParams._fields_ if k != "reserved"}
+    return _defaults_dict(IssParams)
 
 
 def _iss_params(salient_radius, non_max_radius, gamma21, gamma32, min_neighbours):
-    prm = IssParams()
-    load_library().plade_iss_default_params(C.byref(prm))
+    prm = _defaults(IssParams)
     prm.salient_radius, prm.non_max_radius = float(salient_radius), float(non_max_radius)
     if gamma21 is not None:
         prm.gamma21 = float(gamma21)
@@ -540,8 +542,7 @@ def _iss_params(salient_radius, non_max_radius, gamma21, gamma32, min_neighbours
 
 
 def _corr_pose_params(inlier_dist, kw):
-    prm = CorrPoseParams()
-    load_library().plade_corr_pose_default_params(C.byref(prm))
+    prm = _defaults(CorrPoseParams)
     prm.inlier_dist = float(inlier_dist)
     known = {k for k, _ in CorrPoseParams._fields_} - {"reserved", "inlier_dist"}
     for k, v in kw.items():
@@ -567,8 +568,7 @@ def _corr_list(corr, what):
 
 
 def _fpfh_params(radius, min_pairs):
-    prm = FpfhParams()
-    load_library().plade_fpfh_default_params(C.byref(prm))
+    prm = _defaults(FpfhParams)
     prm.radius = float(radius)
     if min_pairs is not None:
         prm.min_pairs = int(min_pairs)
@@ -576,8 +576,7 @@ def _fpfh_params(radius, min_pairs):
 
 
 def _feature_match_params(mutual, max_ratio):
-    prm = FeatureMatchParams()
-    load_library().plade_feature_match_default_params(C.byref(prm))
+    prm = _defaults(FeatureMatchParams)
     prm.mutual, prm.max_ratio = int(bool(mutual)), float(max_ratio)
     return prm
 
@@ -591,40 +590,24 @@ def _feature_table(a, what):
 
 def gicp_default_params():
     """plade_gicp_default_params (pure: needs no GPU) as a dict of the plade_gicp_params fields."""
-    prm = GicpParams()
-    load_library().plade_gicp_default_params(C.byref(prm))
-    return {k: getattr(prm, k) for k, _ in GicpParams._fields_}
+    return _defaults_dict(GicpParams)
 
 
-def _gicp_params(kw):
-    prm = GicpParams()
-    load_library().plade_gicp_default_params(C.byref(prm))
+# the two refinements: the params and result structs and the name in the messages
+_ICP, _GICP = (IcpParams, IcpResult, "ICP"), (GicpParams, GicpResult, "GICP")
+
+
+def _refine_params(kw, model):
+    prm = _defaults(model[0])
     for k, v in kw.items():
-        if k not in dict(GicpParams._fields_):
-            raise TypeError(f"unknown GICP parameter {k!r}")
+        if k not in dict(model[0]._fields_):
+            raise TypeError(f"unknown {model[2]} parameter {k!r}")
         setattr(prm, k, v)
     return prm
 
 
-def _gicp_info(res):
-    info = {k: getattr(res, k) for k, _ in GicpResult._fields_}
-    info["converged"] = bool(info["converged"])
-    info["reason"] = ICP_FAILURES.get(info["failure"], "unknown")
-    return info
-
-
-def _icp_params(kw):
-    prm = IcpParams()
-    load_library().plade_icp_default_params(C.byref(prm))
-    for k, v in kw.items():
-        if k not in dict(IcpParams._fields_):
-            raise TypeError(f"unknown ICP parameter {k!r}")
-        setattr(prm, k, v)
-    return prm
-
-
-def _icp_info(res):
-    info = {k: getattr(res, k) for k, _ in IcpResult._fields_}
+def _refine_info(res):
+    info = {k: getattr(res, k) for k, _ in res._fields_}
     info["converged"] = bool(info["converged"])
     info["reason"] = ICP_FAILURES.get(info["failure"], "unknown")
     return info
@@ -1123,13 +1106,13 @@ class Context:
         return Cloud(self, None, handle=(n, h))
 
     # ---- fine alignment ----------------------------------------------------------------------
-    def _refine(self, call, T, icp_params):
+    def _refine(self, call, T, params, model):
         T_in = _f32(T).reshape(4, 4).copy()
-        prm = _icp_params(icp_params)
+        prm = _refine_params(params, model)
         T_out = np.zeros((4, 4), np.float32)
-        res = IcpResult()
+        res = model[1]()
         rc = call(T_in, prm, T_out, res)
-        info = _icp_info(res)
+        info = _refine_info(res)
         if rc != 0:
             err = PladeError(rc, self.L.plade_last_error(self.h).decode(errors="replace"))
             err.info, err.T = info, T_out
@@ -1143,12 +1126,12 @@ class Context:
         tgt, src = _f32(tgt), _f32(src)
         self._check_cloud(tgt, "refine_icp"); self._check_cloud(src, "refine_icp")
         return self._refine(lambda T_in, prm, T_out, res: self.L.plade_refine_icp(
-            self.h, _ptr(tgt), len(tgt), _ptr(src), len(src), _ptr(T_in), C.byref(prm), _ptr(T_out), C.byref(res)), T, icp_params)
+            self.h, _ptr(tgt), len(tgt), _ptr(src), len(src), _ptr(T_in), C.byref(prm), _ptr(T_out), C.byref(res)), T, icp_params, _ICP)
 
     def refine_icp_dev(self, tgt_cloud, src_cloud, T, **icp_params):
         """plade_refine_icp_dev: refine_icp on resident clouds (upload, upload_xyz); bit-identical to refine_icp."""
         return self._refine(lambda T_in, prm, T_out, res: self.L.plade_refine_icp_dev(
-            self.h, tgt_cloud.h, src_cloud.h, _ptr(T_in), C.byref(prm), _ptr(T_out), C.byref(res)), T, icp_params)
+            self.h, tgt_cloud.h, src_cloud.h, _ptr(T_in), C.byref(prm), _ptr(T_out), C.byref(res)), T, icp_params, _ICP)
 
     def icp_linearize(self, tgt, src_xyz, T, dist, center=None):
         """plade_icp_linearize (test seam): one match + linearise pass of the ICP at stage distance `dist` with the fp64 4 x 4 T on
@@ -1166,19 +1149,6 @@ class Context:
                                                _ptr(corr), _ptr(mom)))
         return corr, mom
 
-    def _refine_gicp(self, call, T, gicp_params):
-        T_in = _f32(T).reshape(4, 4).copy()
-        prm = _gicp_params(gicp_params)
-        T_out = np.zeros((4, 4), np.float32)
-        res = GicpResult()
-        rc = call(T_in, prm, T_out, res)
-        info = _gicp_info(res)
-        if rc != 0:
-            err = PladeError(rc, self.L.plade_last_error(self.h).decode(errors="replace"))
-            err.info, err.T = info, T_out
-            raise err
-        return T_out, info
-
     def refine_gicp(self, tgt, src, T, **gicp_params):
         """plade_refine_gicp: plane-to-plane (generalized) ICP of the (N, 6) source onto the (M, 6) target from the 4 x 4 source ->
         target T; both clouds' normals are read.  Parameters: those of refine_icp and epsilon (1: point-to-point ICP).  Returns
@@ -1186,13 +1156,13 @@ class Context:
         A failed refinement raises PladeError (code PLADE_EFAIL, with .info and .T = T_in)."""
         tgt, src = _f32(tgt), _f32(src)
         self._check_cloud(tgt, "refine_gicp"); self._check_cloud(src, "refine_gicp")
-        return self._refine_gicp(lambda T_in, prm, T_out, res: self.L.plade_refine_gicp(
-            self.h, _ptr(tgt), len(tgt), _ptr(src), len(src), _ptr(T_in), C.byref(prm), _ptr(T_out), C.byref(res)), T, gicp_params)
+        return self._refine(lambda T_in, prm, T_out, res: self.L.plade_refine_gicp(
+            self.h, _ptr(tgt), len(tgt), _ptr(src), len(src), _ptr(T_in), C.byref(prm), _ptr(T_out), C.byref(res)), T, gicp_params, _GICP)
 
     def refine_gicp_dev(self, tgt_cloud, src_cloud, T, **gicp_params):
         """plade_refine_gicp_dev: refine_gicp on resident clouds (upload, upload_xyz); bit-identical to refine_gicp."""
-        return self._refine_gicp(lambda T_in, prm, T_out, res: self.L.plade_refine_gicp_dev(
-            self.h, tgt_cloud.h, src_cloud.h, _ptr(T_in), C.byref(prm), _ptr(T_out), C.byref(res)), T, gicp_params)
+        return self._refine(lambda T_in, prm, T_out, res: self.L.plade_refine_gicp_dev(
+            self.h, tgt_cloud.h, src_cloud.h, _ptr(T_in), C.byref(prm), _ptr(T_out), C.byref(res)), T, gicp_params, _GICP)
 
     def gicp_linearize(self, tgt, src, T, dist, epsilon=0.0, center=None):
         """plade_gicp_linearize (test seam): one match + linearise pass of the plane-to-plane ICP at stage distance `dist` with the

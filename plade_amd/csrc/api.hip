@@ -144,13 +144,13 @@ extern "C" void plade_ctx_destroy(plade_ctx *ctx) {
     if (ctx->reg_work) plade::registration_work_destroy(ctx->reg_work);
     if (ctx->ransac_work) plade::ransac_work_destroy(ctx->ransac_work);
     if (ctx->normals_work) plade::normals_work_destroy(ctx->normals_work);
-    if (ctx->icp_work) plade::icp_work_destroy(ctx->icp_work);
+    if (ctx->icp_work) plade::refine_work_destroy(ctx->icp_work);
     if (ctx->dist_work) plade::dist_work_destroy(ctx->dist_work);
     if (ctx->outlier_work) plade::outlier_work_destroy(ctx->outlier_work);
     if (ctx->merge_work) plade::merge_work_destroy(ctx->merge_work);
     if (ctx->component_work) plade::component_work_destroy(ctx->component_work);
     if (ctx->smooth_work) plade::smooth_work_destroy(ctx->smooth_work);
-    if (ctx->gicp_work) plade::gicp_work_destroy(ctx->gicp_work);
+    if (ctx->gicp_work) plade::refine_work_destroy(ctx->gicp_work);
     if (ctx->m3c2_work) plade::m3c2_work_destroy(ctx->m3c2_work);
     if (ctx->fpfh_work) plade::fpfh_work_destroy(ctx->fpfh_work);
     if (ctx->corr_pose_work) plade::corr_pose_work_destroy(ctx->corr_pose_work);

@@ -89,7 +89,7 @@ struct plade_cloud {
     std::vector<float> host_copy;  // pos_nrm kept for the small host-side gathers
 };
 
-namespace plade { struct RegistrationWork; struct RansacWork; struct NormalsWork; struct IcpWork; struct DistWork; struct OutlierWork; struct MergeWork; struct ComponentWork; struct SmoothWork; struct GicpWork; struct M3c2Work; struct FpfhWork; struct CorrPoseWork; struct IssWork; }
+namespace plade { struct RegistrationWork; struct RansacWork; struct NormalsWork; struct RefineWork; struct DistWork; struct OutlierWork; struct MergeWork; struct ComponentWork; struct SmoothWork; struct M3c2Work; struct FpfhWork; struct CorrPoseWork; struct IssWork; }
 namespace plade { void comm_all_gather_dev(plade_comm *c, const void *d_send, void *d_recv, size_t bytes, hipStream_t stream); }
 
 struct plade_ctx {
@@ -97,13 +97,13 @@ struct plade_ctx {
     plade::RegistrationWork *reg_work = nullptr;
     plade::RansacWork *ransac_work = nullptr;
     plade::NormalsWork *normals_work = nullptr;   // grid and lists of plade_estimate_normals / plade_cloud_upload_xyz
-    plade::IcpWork *icp_work = nullptr;           // stage grids, sample and state of plade_refine_icp / plade_icp_linearize
+    plade::RefineWork *icp_work = nullptr;        // stage grids, sample and state of plade_refine_icp / plade_icp_linearize
     plade::DistWork *dist_work = nullptr;         // grid, probes and partials of plade_cloud_distances
     plade::OutlierWork *outlier_work = nullptr;   // grid, lists and partials of plade_filter_outliers
     plade::MergeWork *merge_work = nullptr;       // concatenation, keys, runs and fused rows of plade_merge_clouds
     plade::ComponentWork *component_work = nullptr;   // grid, parents, labels and lists of plade_label_components
     plade::SmoothWork *smooth_work = nullptr;     // grid, per-point outputs and partials of plade_smooth_cloud
-    plade::GicpWork *gicp_work = nullptr;         // stage grids and state of plade_refine_gicp / plade_gicp_linearize
+    plade::RefineWork *gicp_work = nullptr;       // stage grids and state of plade_refine_gicp / plade_gicp_linearize
     plade_ctx *peers[PLADE_GROUP_MAX - 1] = {};   // the contexts of pairs 1.. of a group (plade_registration_pairs): stream, aux, work areas
     hipEvent_t ev_group = nullptr;   // end of a group's joint plane extraction on `stream` (the peers' streams wait for it)
     bool in_group = false;      // this context carries one pair of a group of several (register_group)

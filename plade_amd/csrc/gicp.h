@@ -46,8 +46,4 @@ namespace plade {
 
 constexpr int GICP_MOMENTS = 30;     // 21 J^T M J, 6 J^T M e, sum e^T M e, sum |e|^2, count
 
-struct GicpWork;
-GicpWork *gicp_work_create();
-void gicp_work_destroy(GicpWork *w);
-
 }  // namespace plade

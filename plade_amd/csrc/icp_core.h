@@ -1,19 +1,29 @@
-// plade_amd/csrc/icp_core.h -- what the point-to-plane ICP (k_icp.hip, icp.h) and the plane-to-plane ICP (k_gicp.hip, gicp.h) have
-// in common: the device state of a refinement, the fp64 mean of the sample, the fixed-order reduction of the moments, the solve /
-// update / schedule / failure rules of lane 0, and on the host the resolved parameters and the stage grids.  The two loops differ in
-// their match-and-linearise kernel and in the number of moments, which is a template argument here; nothing in this header depends
-// on what a moment means beyond the slots named below.
+// plade_amd/csrc/icp_core.h -- the refinement that the point-to-plane ICP (k_icp.hip, icp.h) and the plane-to-plane ICP (k_gicp.hip,
+// gicp.h) are two variants of: the device state, the fp64 mean of the sample, the match kernel around the variant's linearisation,
+// the fixed-order reduction of the moments, the solve / update / schedule / failure rules of lane 0, and on the host the resolved
+// parameters, the stage grids, the work area, the loop (refine_dev), the test seam (linearize_seam) and the bodies of the entry
+// points.  All of it is written once, as templates over a model M that each .hip file defines:
+//   NM, R2, AUX          the number of moments and the slots of k_icp_solve (NM - 1 = the count)
+//   STRIDE               floats per row of the sample
+//   prefix, who, seam, seam_grid, seam_empty   the stats prefix and the names that open the messages
+//   slot                 the context's pointer to this variant's work area
+//   params, result, defaults()   the public types (include/plade_hip.h)
+//   Args                 the match kernel's arguments: g, tgt, src, n, st, partial, corr and what the variant adds
+//   source(a, rows, stride)   the rows to match into a;  row(a, i): row i on the device
+//   epsilon_of(p), extra(a, epsilon, who)   the variant's own parameter into a, checked after the common ones
+//   sample(...)          the source's sample on the device: its size and rows
+//   finish(r, s)         the variant's own result field
+//   linearise(a, x, y, z, s, t, st, m)   the moments of one correspondence; false when the variant's normal test refuses it
+// Nothing here depends on what a moment means beyond the slots named above.
 //
-// Included by those two .hip files only.  Everything sits in an unnamed namespace: each file gets kernels of its own.
+// Included by those two .hip files only.  What is not named by ctx.h sits in an unnamed namespace: each file gets kernels of its own.
 #pragma once
 #include "icp.h"
 #include "fixed_reduce.h"
 #include "grid_walk.h"
+#include "voxel.h"
 
 namespace plade {
-namespace {
-
-constexpr int CORR_TPB = 256;
 
 // the device state of one refinement (one allocation, uploaded once per call)
 struct IcpState {
@@ -27,6 +37,22 @@ struct IcpState {
     double sum_r2;       // the moment in slot R2 of the last linearisation
     double sum_aux;      // the moment in slot AUX (plane-to-plane: sum e^T M e; point-to-plane: unused)
 };
+
+// the work area of one variant (plade_ctx holds one per variant, made on first use)
+struct RefineWork {
+    TargetGrid grids[ICP_MAX_STAGES];
+    VoxelWork vox;                 // the point-to-plane sample (grow-only device buffers: a variant that never runs it holds none)
+    DBuf<float> in_t, in_s;        // the host-pointer entry points' device copies (grow-only)
+    DBuf<double> partial, out;
+    DBuf<IcpState> st;
+    DBuf<int32_t> corr;
+    EventSpans<4> spans;        // sample, grid, loop
+    IcpState h_init, h_st;      // the upload's source and the read-back's destination (never the same memory in flight)
+};
+
+namespace {
+
+constexpr int CORR_TPB = 256;
 
 struct IcpGridArgs {
     GridView g;
@@ -62,6 +88,36 @@ __device__ __forceinline__ u64 nearest_key(const GridView &g, const f3 q) {
 template <int NM>
 __device__ __forceinline__ void reduce_moments(const double (&m)[NM], double (&s_red)[CORR_TPB / 64][NM], double *partial) {
     block_reduce<CORR_TPB>(m, s_red, partial, SumOp());
+}
+
+// match and linearise: one lane per sample point.  The lane forms p' in fp32 with Tf, takes the exact (d, j) argmin key over the
+// current stage's grid and -- below the stage distance -- hands the two rows to the variant's linearisation; the moments then go
+// through the fixed-order reduction.  Once the state says done, the kernel returns at once.
+template <class M>
+__global__ __launch_bounds__(CORR_TPB) void k_corr_lin(const typename M::Args a) {
+    __shared__ double s_red[CORR_TPB / 64][M::NM];
+    const IcpState *st = a.st;
+    if (st->done) return;                              // (uniform)
+    const IcpGridArgs &G = a.g[st->stage];
+    const uint32_t i = blockIdx.x * CORR_TPB + threadIdx.x;
+    double m[M::NM];
+#pragma unroll
+    for (int k = 0; k < M::NM; ++k) m[k] = 0.0;
+    if (i < a.n) {
+        const float *s = M::row(a, i);
+        const float x = s[0], y = s[1], z = s[2];
+        const float *Tf = st->Tf;
+        const f3 q(((Tf[0] * x + Tf[1] * y) + Tf[2] * z) + Tf[3], ((Tf[4] * x + Tf[5] * y) + Tf[6] * z) + Tf[7],
+                   ((Tf[8] * x + Tf[9] * y) + Tf[10] * z) + Tf[11]);
+        const u64 best = nearest_key(G.g, q);
+        int32_t jout = -1;
+        if (best != EMPTY && key_d(best) < G.d2) {
+            const uint32_t j = (uint32_t)best;
+            if (M::linearise(a, x, y, z, s, a.tgt + (size_t)j * 6, st, m)) jout = (int32_t)j;
+        }
+        if (a.corr) a.corr[i] = jout;
+    }
+    reduce_moments<M::NM>(m, s_red, a.partial);
 }
 
 // the fp64 sums of the sample's x y z (`stride` floats apart), one partial per workgroup (the fixed order of reduce_moments)
@@ -218,10 +274,9 @@ inline void check_param(double v, const std::string &who, const char *what) {
     PLADE_REQUIRE(std::isfinite(v) && v >= 0.0, PLADE_EINVAL, who + ": " + what + " must be finite and >= 0");
 }
 
-// the resolved parameters of the seven common fields (prm NULL: the defaults)
-inline IcpConfig resolve(const plade_icp_params *prm, const float tmn[3], const float tmx[3], const std::string &who) {
-    plade_icp_params p;
-    if (prm) p = *prm; else plade_icp_default_params(&p);
+// the resolved parameters of the seven common fields, which plade_icp_params and plade_gicp_params name alike
+template <class P>
+IcpConfig resolve(const P &p, const float tmn[3], const float tmx[3], const std::string &who) {
     check_param(p.source_leaf, who, "source_leaf"); check_param(p.max_dist, who, "max_dist"); check_param(p.min_dist, who, "min_dist");
     check_param(p.eps_rotation, who, "eps_rotation"); check_param(p.eps_translation, who, "eps_translation");
     PLADE_REQUIRE(p.max_iterations >= 0 && p.min_correspondences >= 0, PLADE_EINVAL,
@@ -268,8 +323,183 @@ inline void init_state(IcpState &s, const double T[16], const double *center) {
     if (center) for (int k = 0; k < 3; ++k) s.c[k] = center[k];
 }
 
+
 inline void check_T(const float *T16, const std::string &who) {
     for (int k = 0; k < 16; ++k) PLADE_REQUIRE(std::isfinite(T16[k]), PLADE_EINVAL, who + ": T_in must be finite");
+}
+
+template <class M>
+RefineWork &work_of(plade_ctx *ctx) {
+    RefineWork *&w = ctx->*M::slot;
+    if (!w) w = new RefineWork;
+    return *w;
+}
+
+// what the loop and the seam begin alike: the state and the partials for `blocks` workgroups, the state's upload from T (and the
+// given centre), and the arguments of k_icp_solve that do not depend on the schedule
+template <class M>
+IcpSolveArgs begin(plade_ctx *ctx, RefineWork &W, typename M::Args &a, uint32_t blocks, const double T[16], const double *center) {
+    a.st = W.st.ensure(1);
+    a.partial = W.partial.ensure((size_t)blocks * M::NM);
+    init_state(W.h_init, T, center);
+    HIP_TRY(hipMemcpyAsync(W.st.p, &W.h_init, sizeof(IcpState), hipMemcpyHostToDevice, ctx->stream));
+    IcpSolveArgs sa;
+    memset(&sa, 0, sizeof(sa));
+    sa.st = a.st; sa.partial = a.partial; sa.blocks = blocks;
+    return sa;
+}
+
+template <class M>
+void launch_pair(plade_ctx *ctx, const typename M::Args &a, const IcpSolveArgs &sa) {
+    hipLaunchKernelGGL(k_corr_lin<M>, dim3(sa.blocks), dim3(CORR_TPB), 0, ctx->stream, a);
+    hipLaunchKernelGGL((k_icp_solve<M::NM, M::R2, M::AUX>), dim3(1), dim3(64), 0, ctx->stream, sa);
+}
+
+// the refinement on device clouds: target n_t x 6, source n_s x 6, bounding boxes known
+template <class M>
+int refine_dev(plade_ctx *ctx, RefineWork &W, const float *d_tgt, uint32_t n_t, const float tmn[3], const float tmx[3], const float *d_src,
+               uint32_t n_s, const float smn[3], const float smx[3], const float *T_in16, const typename M::params *prm, float *T_out16,
+               typename M::result *res) {
+    typename M::params p;
+    if (prm) p = *prm; else M::defaults(&p);
+    const IcpConfig c = resolve(p, tmn, tmx, M::who);
+    typename M::Args a;
+    memset(&a, 0, sizeof(a));
+    M::extra(a, M::epsilon_of(p), M::who);
+    float T_in[16];
+    memcpy(T_in, T_in16, sizeof(T_in));
+    W.spans.mark(ctx, 0);
+    // the sample (waits for its size)
+    const float *d_sample = nullptr;
+    const uint32_t n = M::sample(ctx, W, d_src, n_s, (float)c.leaf, smn, smx, &d_sample);
+    W.spans.mark(ctx, 1);
+    for (int s = 0; s < c.n_stages; ++s) a.g[s] = stage_grid(ctx, W.grids[s], d_tgt, n_t, tmn, tmx, c.dist[s], M::who);
+    W.spans.mark(ctx, 2);
+    const uint32_t blocks = std::max(1u, cdiv(n, CORR_TPB));
+    a.tgt = d_tgt; a.n = n;
+    M::source(a, d_sample, M::STRIDE);
+    double T[16];
+    for (int k = 0; k < 16; ++k) T[k] = T_in[k];
+    IcpSolveArgs sa = begin<M>(ctx, W, a, blocks, T, nullptr);
+    hipLaunchKernelGGL(k_icp_mean_part, dim3(blocks), dim3(CORR_TPB), 0, ctx->stream, a.src, (uint32_t)M::STRIDE, n, a.partial);
+    hipLaunchKernelGGL(k_icp_mean, dim3(1), dim3(64), 0, ctx->stream, a.st, (const double *)a.partial, blocks, n);
+    sa.n_stages = c.n_stages; sa.max_iter = c.max_iter; sa.min_corr = c.min_corr; sa.eps_rot = c.eps_rot; sa.eps_trans = c.eps_trans;
+    for (int it = 0; it < c.max_iter; ++it) launch_pair<M>(ctx, a, sa);
+    HIP_TRY(hipGetLastError());
+    W.spans.mark(ctx, 3);
+    HIP_TRY(hipMemcpyAsync(&W.h_st, W.st.p, sizeof(IcpState), hipMemcpyDeviceToHost, ctx->stream));
+    ctx->sync();
+    const IcpState &s = W.h_st;
+    typename M::result r;
+    memset(&r, 0, sizeof(r));
+    r.iterations = s.iter;
+    r.stages = s.lin_stage + 1;
+    r.converged = s.converged;
+    r.failure = s.failure;
+    r.correspondences = s.count;
+    r.samples = n;
+    r.rmse = s.count ? std::sqrt(s.sum_r2 / (double)s.count) : 0.0;
+    r.fitness = n ? (double)s.count / (double)n : 0.0;
+    r.final_dist = c.dist[s.lin_stage];
+    M::finish(r, s);
+    if (res) *res = r;
+    W.spans.collect();
+    const std::string pre = M::prefix;
+    ctx->stats.clear();
+    ctx->stats.add(pre + "_sample_s", W.spans.seconds(0));
+    ctx->stats.add(pre + "_grid_s", W.spans.seconds(1));
+    ctx->stats.add(pre + "_loop_s", W.spans.seconds(2));
+    ctx->stats.add(pre + "_iterations", s.iter);
+    ctx->stats.add(pre + "_stages", c.n_stages);
+    grid_stats(ctx, M::prefix, W.grids[0]);          // the first (widest) stage
+    if (s.failure) {
+        memmove(T_out16, T_in, sizeof(T_in));
+        ctx->last_error = std::string(M::who) + (s.failure == PLADE_ICP_TOO_FEW ? ": too few correspondences"
+                                                                                 : ": degenerate geometry (the system is singular)");
+        return PLADE_EFAIL;
+    }
+    for (int k = 0; k < 12; ++k) T_out16[k] = (float)s.T[k];
+    T_out16[12] = 0.f; T_out16[13] = 0.f; T_out16[14] = 0.f; T_out16[15] = 1.f;
+    return PLADE_OK;
+}
+
+// ---- the bodies of the entry points (include/plade_hip.h) ----------------------------------------------------------------------
+template <class M>
+int refine_host(plade_ctx *ctx, const float *tgt_pos_nrm, uint32_t n_t, const float *src_pos_nrm, uint32_t n_s, const float *T_in16,
+                const typename M::params *params, float *T_out16, typename M::result *result) {
+    return guarded(ctx, [&]() -> int {
+        const std::string name = std::string("plade_") + M::who;
+        PLADE_REQUIRE(tgt_pos_nrm && src_pos_nrm && T_in16 && T_out16, PLADE_EINVAL, name + ": bad argument");
+        PLADE_REQUIRE(n_t >= 1 && n_s >= 1, PLADE_EINVAL, name + ": empty cloud");
+        check_T(T_in16, M::who);
+        RefineWork &W = work_of<M>(ctx);
+        float tmn[3], tmx[3], smn[3], smx[3];
+        upload_rows(ctx, W.in_t, tgt_pos_nrm, n_t, 6, tmn, tmx);
+        upload_rows(ctx, W.in_s, src_pos_nrm, n_s, 6, smn, smx);
+        return refine_dev<M>(ctx, W, W.in_t.p, n_t, tmn, tmx, W.in_s.p, n_s, smn, smx, T_in16, params, T_out16, result);
+    });
+}
+
+template <class M>
+int refine_resident(plade_ctx *ctx, plade_cloud *tgt, plade_cloud *src, const float *T_in16, const typename M::params *params,
+                    float *T_out16, typename M::result *result) {
+    return guarded(ctx, [&]() -> int {
+        const std::string name = std::string("plade_") + M::who + "_dev";
+        PLADE_REQUIRE(tgt && src && T_in16 && T_out16, PLADE_EINVAL, name + ": bad argument");
+        PLADE_REQUIRE(tgt->dev.n >= 1 && src->dev.n >= 1, PLADE_EINVAL, name + ": empty cloud");
+        check_T(T_in16, M::who);
+        const CloudDev &t = tgt->dev, &s = src->dev;
+        return refine_dev<M>(ctx, work_of<M>(ctx), t.aos.p, t.n, t.bbmin, t.bbmax, s.aos.p, s.n, s.bbmin, s.bbmax, T_in16, params,
+                             T_out16, result);
+    });
+}
+
+// the test seam: one match + linearise pass at stage distance `dist` with the fp64 T on every row of the source (no sample), about
+// the given centre; the summed moments and, if asked for, j or -1 per row
+template <class M>
+int linearize_seam(plade_ctx *ctx, const float *tgt_pos_nrm, uint32_t n_t, const float *src, uint32_t n_s, uint32_t stride,
+                   const double *T16, const double *center, float dist, double epsilon, int32_t *corr_out, double *moments_out) {
+    return guarded(ctx, [&]() -> int {
+        const std::string name = M::seam;
+        PLADE_REQUIRE(tgt_pos_nrm && src && T16 && center && moments_out, PLADE_EINVAL, name + ": bad argument");
+        PLADE_REQUIRE(n_t >= 1 && n_s >= 1 && stride >= 3, PLADE_EINVAL, name + ": " + M::seam_empty);
+        PLADE_REQUIRE(std::isfinite(dist) && dist > 0.f, PLADE_EINVAL, name + ": dist must be finite and > 0");
+        for (int k = 0; k < 16; ++k) PLADE_REQUIRE(std::isfinite(T16[k]), PLADE_EINVAL, name + ": T must be finite");
+        for (int k = 0; k < 3; ++k) PLADE_REQUIRE(std::isfinite(center[k]), PLADE_EINVAL, name + ": center must be finite");
+        typename M::Args a;
+        memset(&a, 0, sizeof(a));
+        M::extra(a, epsilon, M::seam);
+        RefineWork &W = work_of<M>(ctx);
+        float tmn[3], tmx[3], smn[3], smx[3];
+        upload_rows(ctx, W.in_t, tgt_pos_nrm, n_t, 6, tmn, tmx);
+        upload_rows(ctx, W.in_s, src, n_s, stride, smn, smx);
+        a.g[0] = stage_grid(ctx, W.grids[0], W.in_t.p, n_t, tmn, tmx, (double)dist, M::seam_grid);
+        a.g[0].d2 = dist * dist;
+        a.tgt = W.in_t.p; a.n = n_s;
+        M::source(a, W.in_s.p, stride);
+        a.corr = W.corr.ensure(n_s);
+        IcpSolveArgs sa = begin<M>(ctx, W, a, cdiv(n_s, CORR_TPB), T16, center);
+        sa.moments = W.out.ensure(M::NM);
+        launch_pair<M>(ctx, a, sa);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(moments_out, sa.moments, M::NM * 8, hipMemcpyDeviceToHost, ctx->stream));
+        if (corr_out) HIP_TRY(hipMemcpyAsync(corr_out, a.corr, (size_t)n_s * 4, hipMemcpyDeviceToHost, ctx->stream));
+        ctx->sync();
+        grid_stats(ctx, M::prefix, W.grids[0]);
+        return PLADE_OK;
+    });
+}
+
+// the seven fields that plade_icp_params and plade_gicp_params name alike (0 = the automatic value of icp.h)
+template <class P>
+void default_common(P *p) {
+    p->source_leaf = 0.0;           // 0.005 D
+    p->max_dist = 0.0;              // 0.025 D
+    p->min_dist = 0.0;              // 0.0025 D
+    p->eps_rotation = 1e-6;
+    p->eps_translation = 0.0;       // 1e-6 D
+    p->max_iterations = 60;
+    p->min_correspondences = 100;
 }
 
 }  // namespace

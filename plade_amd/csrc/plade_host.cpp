@@ -168,23 +168,31 @@ bool refine_icp_on() {
     static const bool on = [] { const char *w = getenv("PLADE_REFINE_ICP"); return w && atoi(w) != 0; }();
     return on;
 }
-// T16 (source -> target of the packed arrays) refined in place; false (T16 unchanged, a warning printed) when the refinement fails
-bool refine_packed(plade_ctx *ctx, float *T16, const float *tg, size_t n_t, const float *sr, size_t n_s) {
-    plade_icp_result res;
+// T16 (source -> target of the packed arrays) refined in place by `call`; false (T16 unchanged, a warning printed) when the
+// refinement fails.  `tag` opens the trace lines, `name` the console's; `cost`: the result's field of that name, if it has one
+template <class Result, class Call>
+bool refine_by(plade_ctx *ctx, float *T16, const std::string &tag, const char *name, const double Result::*cost, Call call) {
+    Result res;
     float out[16];
-    trace("icp: refining");
-    const int rc = plade_refine_icp(ctx, tg, (uint32_t)n_t, sr, (uint32_t)n_s, T16, nullptr, out, &res);
-    trace("icp: done");
+    trace((tag + ": refining").c_str());
+    const int rc = call(out, &res);
+    trace((tag + ": done").c_str());
     if (rc != PLADE_OK) {
-        con_err() << "warning: ICP refinement failed (" << plade_last_error(ctx) << "); PLADE's transformation is kept" << std::endl;
+        con_err() << "warning: " << name << " refinement failed (" << plade_last_error(ctx) << "); PLADE's transformation is kept" << std::endl;
         return false;
     }
     memcpy(T16, out, sizeof(out));
-    char b[200];
-    snprintf(b, sizeof(b), "ICP refinement: %d iterations, %s, rmse %.6g, fitness %.4f", res.iterations,
-             res.converged ? "converged" : "not converged", res.rmse, res.fitness);
+    char b[240], extra[64] = "";
+    if (cost) snprintf(extra, sizeof(extra), "cost %.6g, ", res.*cost);
+    snprintf(b, sizeof(b), "%s refinement: %d iterations, %s, rmse %.6g, %sfitness %.4f", name, res.iterations,
+             res.converged ? "converged" : "not converged", res.rmse, extra, res.fitness);
     con_out() << b << std::endl;
     return true;
+}
+bool refine_packed(plade_ctx *ctx, float *T16, const float *tg, size_t n_t, const float *sr, size_t n_s) {
+    return refine_by<plade_icp_result>(ctx, T16, "icp", "ICP", nullptr, [&](float *out, plade_icp_result *res) {
+        return plade_refine_icp(ctx, tg, (uint32_t)n_t, sr, (uint32_t)n_s, T16, nullptr, out, res);
+    });
 }
 
 // PLADE_REFINE_GICP=1[,<epsilon>] (opt-in, 0 / unset = off): every pair that registered is refined by plane-to-plane ICP on the GPU
@@ -202,26 +210,13 @@ const GicpSwitch &refine_gicp_switch() {
     }();
     return sw;
 }
-// T16 (source -> target of the packed arrays) refined in place; false (T16 unchanged, a warning printed) when the refinement fails
 bool refine_gicp_packed(plade_ctx *ctx, float *T16, const float *tg, size_t n_t, const float *sr, size_t n_s, double epsilon) {
     plade_gicp_params prm;
     plade_gicp_default_params(&prm);
     if (epsilon != 0.0) prm.epsilon = epsilon;
-    plade_gicp_result res;
-    float out[16];
-    trace("gicp: refining");
-    const int rc = plade_refine_gicp(ctx, tg, (uint32_t)n_t, sr, (uint32_t)n_s, T16, &prm, out, &res);
-    trace("gicp: done");
-    if (rc != PLADE_OK) {
-        con_err() << "warning: GICP refinement failed (" << plade_last_error(ctx) << "); PLADE's transformation is kept" << std::endl;
-        return false;
-    }
-    memcpy(T16, out, sizeof(out));
-    char b[240];
-    snprintf(b, sizeof(b), "GICP refinement: %d iterations, %s, rmse %.6g, cost %.6g, fitness %.4f", res.iterations,
-             res.converged ? "converged" : "not converged", res.rmse, res.cost, res.fitness);
-    con_out() << b << std::endl;
-    return true;
+    return refine_by<plade_gicp_result>(ctx, T16, "gicp", "GICP", &plade_gicp_result::cost, [&](float *out, plade_gicp_result *res) {
+        return plade_refine_gicp(ctx, tg, (uint32_t)n_t, sr, (uint32_t)n_s, T16, &prm, out, res);
+    });
 }
 // the refinement the environment selects, if any
 void refine_selected(plade_ctx *ctx, float *T16, const float *tg, size_t n_t, const float *sr, size_t n_s) {

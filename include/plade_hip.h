@@ -615,6 +615,48 @@ int plade_label_components(plade_ctx *ctx, const float *rows, uint32_t n, uint32
 int plade_cloud_filter_components_dev(plade_ctx *ctx, plade_cloud *cloud, const plade_component_params *params, plade_cloud **out,
                                       int32_t *label_out, uint32_t *kept_index_out, plade_component_summary *summary);
 
+/* ---- subsampling to a minimum point spacing: a subset of the cloud's OWN points (no reference counterpart; CloudCompare ships it
+ * as "Subsample -> Space" and takes M3C2's core points from it) ------------------------------------------------------------------
+ * Semantics (plade_amd/csrc/subsample.h).  Input: n >= 1 points, rows of `stride` >= 3 floats, x y z first,
+ * all coordinates finite.  d(i, j) = the fp32 FLANN L2 of (p_i, p_j), ((dx*dx + dy*dy) + dz*dz); r2 = (float)spacing * (float)spacing.
+ *   priority     point i has the key (mix64(mix64(seed) ^ i), i), mix64 = the splitmix64 finaliser (z += 0x9E3779B97F4A7C15;
+ *                z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^ z >> 31); keys compare
+ *                lexicographically, no two are equal.
+ *   kept set     walk the points in ascending key order: a point is kept if and only if no already-kept point j has d(i, j) < r2
+ *                (the strict `<` of the radius filter: of duplicates exactly one is kept, a pair at exactly d = r2 keeps both).  No
+ *                two kept points are closer than spacing, every dropped point has a kept point closer than spacing, and the set --
+ *                the lexicographically first maximal independent set of the graph "closer than spacing" -- is unique.
+ *   rounds       the same set as the fixed point of synchronous rounds: in round t every undecided point looks at its neighbours
+ *                with d < r2 and a smaller key as they stood at the end of round t - 1; one of them kept: dropped; otherwise none
+ *                of them undecided: kept; otherwise it waits.  round[i] = the round that decided i, rounds = the largest.
+ *   output       each array may be NULL.  keep_out: n bytes 0 / 1; kept_index_out: the kept original indices, ascending (room for
+ *                n); rows_out: the kept rows in that order, every float copied bit for bit (room for n rows; may be `rows` itself);
+ *                round_out: n uint32; summary: n, kept, rounds.  The result depends on the points, spacing and seed only, and is
+ *                the same bits on every run.
+ * Errors: PLADE_EINVAL for n = 0 (or n >= 2^31), stride < 3, a NULL cloud, a non-finite coordinate, a spacing that is not finite and > 0 or whose
+ * fp32 square is not finite or below FLT_MIN; the context stays usable.  At least one point is always kept.  A spacing that is tiny
+ * against the cloud's extent is not refused: the grid's cell grows until 48e6 cells hold the cloud (the result is the same).
+ * plade_stats_get then reports subsample_grid_s, subsample_rounds_s, subsample_compact_s (scatter to the original order, scan, kept
+ * list and row gather; HIP events on the context's stream), subsample_rounds, subsample_kept and subsample_grid_dx / _dy / _dz /
+ * _cell. */
+typedef struct plade_subsample_params {
+    double spacing;              /* must be set (> 0): there is no automatic value */
+    uint64_t seed;               /* of the priority keys */
+} plade_subsample_params;
+typedef struct plade_subsample_summary {
+    uint32_t n, kept, rounds;
+} plade_subsample_summary;
+/* The defaults: spacing = 0 (unset), seed = 0.  Needs no GPU. */
+void plade_subsample_default_params(plade_subsample_params *p);
+int plade_subsample_spacing(plade_ctx *ctx, const float *rows, uint32_t n, uint32_t stride, const plade_subsample_params *params,
+                            uint8_t *keep_out, uint32_t *kept_index_out, float *rows_out, uint32_t *round_out,
+                            plade_subsample_summary *summary);
+/* The same on a resident cloud (plade_cloud_upload / plade_cloud_upload_xyz; rows x y z nx ny nz) into a NEW resident cloud of the
+ * kept points, a resident cloud like any other: the point data makes no host round trip.  The same keep, kept_index and summary
+ * bits as plade_subsample_spacing on the cloud's rows.  Free both clouds with plade_cloud_free. */
+int plade_cloud_subsample_dev(plade_ctx *ctx, plade_cloud *cloud, const plade_subsample_params *params, plade_cloud **out,
+                              uint8_t *keep_out, uint32_t *kept_index_out, plade_subsample_summary *summary);
+
 /* ---- smoothing: moving-least-squares plane projection, the step between outlier removal and normals (no reference counterpart;
  * PCL ships it as MovingLeastSquares, Open3D users expect it) -----------------------------------------------------------------------
  * Semantics (plade_amd/csrc/smooth.h).  Input: n >= 1 points, rows of `stride` >= 3 floats, x y z first, all

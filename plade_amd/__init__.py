@@ -32,6 +32,7 @@ ABI_SYMBOLS = [
     "plade_outlier_default_params", "plade_filter_outliers", "plade_cloud_filter_outliers_dev",
     "plade_merge_clouds", "plade_merge_clouds_dev", "plade_cloud_download",
     "plade_component_default_params", "plade_label_components", "plade_cloud_filter_components_dev",
+    "plade_subsample_default_params", "plade_subsample_spacing", "plade_cloud_subsample_dev",
     "plade_smooth_default_params", "plade_smooth_cloud", "plade_cloud_smooth_dev",
     "plade_gicp_default_params", "plade_refine_gicp", "plade_refine_gicp_dev", "plade_gicp_linearize",
     "plade_m3c2_default_params", "plade_cloud_m3c2", "plade_cloud_m3c2_dev",
@@ -124,6 +125,16 @@ class ComponentSummary(C.Structure):
     """plade_component_summary: n, components, kept_components, kept (points), largest (size)."""
     _fields_ = [("n", C.c_uint64), ("components", C.c_uint64), ("kept_components", C.c_uint64), ("kept", C.c_uint64),
                 ("largest", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class SubsampleParams(C.Structure):
+    """plade_subsample_params: the minimum spacing of the kept points (absolute, no default) and the seed of the priority keys."""
+    _fields_ = [("spacing", C.c_double), ("seed", C.c_uint64)]
+
+
+class SubsampleSummary(C.Structure):
+    """plade_subsample_summary: n, kept, rounds (the synchronous rounds until every point was decided)."""
+    _fields_ = [("n", C.c_uint32), ("kept", C.c_uint32), ("rounds", C.c_uint32)]
 
 
 class SmoothParams(C.Structure):
@@ -288,6 +299,9 @@ def load_library(path=LIB_PATH):
     sig("plade_component_default_params", argtypes=[C.POINTER(ComponentParams)], restype=None)
     sig("plade_label_components", argtypes=[p, p, u32, u32, C.POINTER(ComponentParams), p, p, p, p, p, C.POINTER(ComponentSummary)])
     sig("plade_cloud_filter_components_dev", argtypes=[p, p, C.POINTER(ComponentParams), C.POINTER(p), p, p, C.POINTER(ComponentSummary)])
+    sig("plade_subsample_default_params", argtypes=[C.POINTER(SubsampleParams)], restype=None)
+    sig("plade_subsample_spacing", argtypes=[p, p, u32, u32, C.POINTER(SubsampleParams), p, p, p, p, C.POINTER(SubsampleSummary)])
+    sig("plade_cloud_subsample_dev", argtypes=[p, p, C.POINTER(SubsampleParams), C.POINTER(p), p, p, C.POINTER(SubsampleSummary)])
     sig("plade_smooth_default_params", argtypes=[C.POINTER(SmoothParams)], restype=None)
     sig("plade_smooth_cloud", argtypes=[p, p, u32, u32, C.POINTER(SmoothParams), p, p, p, p, p, p, p, C.POINTER(SmoothSummary)])
     sig("plade_cloud_smooth_dev", argtypes=[p, p, C.POINTER(SmoothParams), i32, C.POINTER(p), C.POINTER(SmoothSummary)])
@@ -397,6 +411,7 @@ _DEFAULTS = {Params: "plade_default_params",
              IcpParams: "plade_icp_default_params",
              OutlierParams: "plade_outlier_default_params",
              ComponentParams: "plade_component_default_params",
+             SubsampleParams: "plade_subsample_default_params",
              SmoothParams: "plade_smooth_default_params",
              M3c2Params: "plade_m3c2_default_params",
              FpfhParams: "plade_fpfh_default_params",
@@ -475,6 +490,27 @@ def _component_info(summ, label, size, keep):
         info["size"] = size[:summ.components].copy()
     if keep is not None:
         info["keep"] = keep.view(np.bool_)
+    return info
+
+
+def subsample_default_params():
+    """plade_subsample_default_params (pure: needs no GPU) as a dict of the plade_subsample_params fields."""
+    return _defaults_dict(SubsampleParams)
+
+
+def _subsample_params(spacing, seed):
+    prm = _defaults(SubsampleParams)
+    prm.spacing = float(spacing)
+    prm.seed = int(seed)
+    return prm
+
+
+def _subsample_info(summ, keep, rnd):
+    info = {k: getattr(summ, k) for k, _ in SubsampleSummary._fields_}
+    if keep is not None:
+        info["keep"] = keep.view(np.bool_)
+    if rnd is not None:
+        info["round"] = rnd
     return info
 
 
@@ -1283,6 +1319,38 @@ class Context:
                                                              C.byref(summ)))
         out = Cloud(self, None, handle=(int(summ.kept), h))
         return (out, kept[:summ.kept].copy(), _component_info(summ, label, None, None)) if info else out
+
+    # ---- subsampling to a minimum spacing ---------------------------------------------------------
+    def subsample(self, points, spacing, seed=0, per_point=True):
+        """plade_subsample_spacing: the subset of an (N, >= 3) float32 array (first three columns x y z) in which no two kept points
+        are closer than spacing (fp32 squared distance, strict <) and every dropped point has a kept point closer than spacing:
+        the greedy walk in the order of the hashed keys (mix64(mix64(seed) ^ i), i), an exact set that depends on the points,
+        spacing and seed only.  Returns (subset, kept_index, info): the kept rows in their original order with every column copied
+        bit for bit, their original indices (uint32, ascending), and a dict with n, kept, rounds and -- with per_point -- keep (N
+        bools) and round (N uint32: the synchronous round that decided each point)."""
+        a, n, stride = _xyz_view(points)
+        prm = _subsample_params(spacing, seed)
+        keep = np.zeros(n, np.uint8) if per_point else None
+        rnd = np.empty(n, np.uint32) if per_point else None
+        kept = np.empty(n, np.uint32)
+        rows = np.empty((n, stride), np.float32)
+        summ = SubsampleSummary()
+        self._check(self.L.plade_subsample_spacing(self.h, _ptr(a), n, stride, C.byref(prm), _ptr(keep), _ptr(kept), _ptr(rows),
+                                                   _ptr(rnd), C.byref(summ)))
+        return rows[:summ.kept].copy(), kept[:summ.kept].copy(), _subsample_info(summ, keep, rnd)
+
+    def subsample_dev(self, cloud, spacing, seed=0, info=False):
+        """plade_cloud_subsample_dev: subsample on a resident cloud (upload, upload_xyz) into a new resident Cloud of the kept
+        points; the point data makes no host round trip.  With info also (kept_index, info dict) as subsample gives them (keep,
+        no round array): the same bits.  At least one point is always kept."""
+        prm = _subsample_params(spacing, seed)
+        keep = np.zeros(cloud.n, np.uint8) if info else None
+        kept = np.empty(cloud.n, np.uint32) if info else None
+        summ = SubsampleSummary()
+        h = C.c_void_p()
+        self._check(self.L.plade_cloud_subsample_dev(self.h, cloud.h, C.byref(prm), C.byref(h), _ptr(keep), _ptr(kept), C.byref(summ)))
+        out = Cloud(self, None, handle=(int(summ.kept), h))
+        return (out, kept[:summ.kept].copy(), _subsample_info(summ, keep, None)) if info else out
 
     # ---- smoothing ---------------------------------------------------------------------------------
     def smooth_cloud(self, points, radius, min_neighbours=None, viewpoint=(0.0, 0.0, 0.0), normals=True, per_point=True, moments=False):

@@ -15,6 +15,7 @@
 #include "fpfh.h"
 #include "corr_pose.h"
 #include "keypoints.h"
+#include "subsample.h"
 
 using namespace plade;
 
@@ -155,6 +156,7 @@ extern "C" void plade_ctx_destroy(plade_ctx *ctx) {
     if (ctx->fpfh_work) plade::fpfh_work_destroy(ctx->fpfh_work);
     if (ctx->corr_pose_work) plade::corr_pose_work_destroy(ctx->corr_pose_work);
     if (ctx->iss_work) plade::iss_work_destroy(ctx->iss_work);
+    if (ctx->subsample_work) plade::subsample_work_destroy(ctx->subsample_work);
     (void)hipStreamDestroy(ctx->stream);
     if (ctx->pf.stream) { (void)hipStreamSynchronize(ctx->pf.stream); (void)hipStreamDestroy(ctx->pf.stream); }
     delete ctx;

@@ -39,6 +39,8 @@ inline bool smooth_radius(double r) {
     const float r2 = (float)r * (float)r;
     return non_negative(r) && std::isfinite(r2) && (r == 0.0 || r2 >= FLT_MIN);
 }
+// the spacing of a subsample: 0 = off, otherwise what plade_subsample_spacing accepts
+inline bool spacing_or_off(double r) { return r == 0.0 || radius_sq32(r); }
 // the RANSAC pose's inlier distance: its fp64 square is finite and > 0
 inline bool inlier_dist(double v) { return positive(v) && std::isfinite(v * v) && v * v > 0.0; }
 inline bool epsilon(double v) { return positive(v) && v <= 1.0; }
@@ -185,6 +187,27 @@ inline Parsed<SmoothSwitch> parse_smooth(const char *text) {
     Value v[2] = {{}, {0.0, p.value.min_neighbours}};
     if (parse(spec, text, v, p.warning)) { p.value.radius = v[0].r; p.value.min_neighbours = (int)v[1].i; }
     return p;
+}
+
+// <spacing>[,<seed>] of PLADE_SUBSAMPLE and PLADE_M3C2_CORE: spacing 0 = off
+struct SubsampleSwitch { double spacing = 0.0; uint64_t seed = 0; };
+inline Parsed<SubsampleSwitch> parse_spacing_seed(const Spec &spec, const char *text) {
+    Parsed<SubsampleSwitch> p;
+    Value v[2] = {};
+    if (parse(spec, text, v, p.warning)) { p.value.spacing = v[0].r; p.value.seed = (uint64_t)v[1].i; }
+    return p;
+}
+constexpr Field spacing_seed_fields[] = {real(spacing_or_off), integer(0, LONG_MAX)};
+inline Parsed<SubsampleSwitch> parse_subsample(const char *text) {
+    static const Spec spec = {"PLADE_SUBSAMPLE", spacing_seed_fields, 2, 1,
+                              " is not <spacing>[,<seed>] with spacing >= 0 (its square not below FLT_MIN) and seed an integer >= 0; no subsampling"};
+    return parse_spacing_seed(spec, text);
+}
+inline Parsed<SubsampleSwitch> parse_m3c2_core(const char *text) {
+    static const Spec spec = {"PLADE_M3C2_CORE", spacing_seed_fields, 2, 1,
+                              " is not <spacing>[,<seed>] with spacing >= 0 (its square not below FLT_MIN) and seed an integer >= 0;"
+                              " the whole target as core points"};
+    return parse_spacing_seed(spec, text);
 }
 
 inline Parsed<float> parse_merge(const char *text) {   // < 0: off

@@ -110,6 +110,21 @@ struct ComponentFilter {
 bool keep_components(pcl::PointCloud<pcl::PointNormal>::Ptr cloud, pcl::PointCloud<pcl::PointNormal> &filtered, double radius,
                      int min_size = 1, int max_size = 0, int keep_largest = 0, ComponentFilter *info = nullptr);
 
+/** Subsampling (no counterpart in the reference): the fields of plade_subsample_summary (include/plade_hip.h). */
+struct CloudSubsample {
+    uint32_t n = 0, kept = 0, rounds = 0;   // points in, points kept, synchronous rounds until every point was decided
+};
+/** Thins a cloud to a subset of its own points at a minimum spacing (absolute, in the cloud's units; fp32 squared distance, strict
+ *  <) on the GPU (plade_subsample_spacing): no two kept points are closer than spacing, every dropped point has a kept point closer
+ *  than spacing.  The set is the greedy walk in the order of the hashed keys of (seed, index): it depends on the points, spacing and
+ *  seed only.  `subset` receives the kept points in their original order, coordinates and normals copied bit for bit (it may be
+ *  *cloud).  false: invalid input or no GPU; a message is printed and `subset` is unchanged.  The CLI and the file overload of
+ *  registration() thin both clouds of a pair as the last preparation step, after PLADE_ESTIMATE_NORMALS, when
+ *  PLADE_SUBSAMPLE=<spacing>[,<seed>] is set, and print one line per cloud; PLADE_M3C2_CORE=<spacing>[,<seed>] makes the subsample
+ *  of the target the core points of PLADE_M3C2. */
+bool subsample_cloud(pcl::PointCloud<pcl::PointNormal>::Ptr cloud, pcl::PointCloud<pcl::PointNormal> &subset, double spacing,
+                     uint64_t seed = 0, CloudSubsample *info = nullptr);
+
 /** Smoothing (no counterpart in the reference): the fields of plade_smooth_summary (include/plade_hip.h). */
 struct CloudSmoothing {
     uint64_t n = 0, fitted = 0;   // points in, points that were fitted and projected

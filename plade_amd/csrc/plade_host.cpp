@@ -43,6 +43,7 @@ void trace(const char *what) {
 // parser has to say about a rejected value goes to std::cerr, not to the calling thread's console.
 using cli_switches::GicpSwitch; using cli_switches::M3c2Switch; using cli_switches::FpfhSwitch; using cli_switches::FeatureRegisterSwitch;
 using cli_switches::KeypointSwitch; using cli_switches::OutlierSwitch; using cli_switches::ComponentSwitch; using cli_switches::SmoothSwitch;
+using cli_switches::SubsampleSwitch;
 template <class S> S latched(const cli_switches::Parsed<S> &p) {
     if (!p.warning.empty()) std::cerr << p.warning << std::endl;
     return p.value;
@@ -254,6 +255,46 @@ void evaluate_line(plade_ctx *ctx, const float *T16, const float *tg, size_t n_t
     con_out() << b << std::endl;
 }
 
+// PLADE_SUBSAMPLE=<spacing>[,<seed>] (opt-in, 0 / unset = off; the spacing absolute, in the clouds' units): both clouds of a pair are
+// thinned to a subset of their own points in which no two are closer than spacing and every dropped point has a kept one closer than
+// spacing (plade_subsample_spacing; seed 0 when not given), as the LAST preparation step -- after the filters and after
+// PLADE_ESTIMATE_NORMALS, so the normals come from the full density; one console line per cloud.  A value that does not parse (spacing
+// negative, not finite or so small that its fp32 square is below FLT_MIN, seed not an integer >= 0, anything behind them) prints one
+// warning and thins nothing; unset, nothing changes.
+const SubsampleSwitch &subsample_switch() {
+    static const SubsampleSwitch sw = latched(cli_switches::parse_subsample(getenv("PLADE_SUBSAMPLE")));
+    return sw;
+}
+// the rows of an x y z nx ny nz array that the subsample keeps (the normal columns, NaN included, keep their bits): into `out`,
+// which may be `rows` itself
+bool subsample_packed(plade_ctx *ctx, const float *rows, size_t n, double spacing, uint64_t seed, float *out, plade_subsample_summary &s) {
+    plade_subsample_params prm;
+    plade_subsample_default_params(&prm);
+    prm.spacing = spacing; prm.seed = seed;
+    trace("subsample: thinning");
+    // (in place: the upload of the rows precedes the read-back of the kept ones on the context's stream)
+    const int rc = plade_subsample_spacing(ctx, rows, (uint32_t)n, 6, &prm, nullptr, nullptr, out, nullptr, &s);
+    trace("subsample: done");
+    if (rc != PLADE_OK) {
+        con_err() << "subsampling failed: " << plade_last_error(ctx) << std::endl;
+        return false;
+    }
+    return true;
+}
+bool subsample_in_place(std::vector<float> &buf) {
+    const SubsampleSwitch &sw = subsample_switch();
+    if (!(sw.spacing > 0.0) || buf.empty()) return true;
+    plade_ctx *ctx = context();
+    if (!ctx) return false;
+    plade_subsample_summary s;
+    if (!subsample_packed(ctx, buf.data(), buf.size() / 6, sw.spacing, sw.seed, buf.data(), s)) return false;
+    buf.resize((size_t)s.kept * 6);
+    char b[200];
+    snprintf(b, sizeof(b), "subsample: kept %u of %u points (spacing %g, %u rounds)", s.kept, s.n, sw.spacing, s.rounds);
+    con_out() << b << std::endl;
+    return true;
+}
+
 // PLADE_M3C2=<radius>,<depth>[,<min_points>[,<reg_error>]] (opt-in, absolute, in the clouds' units): every pair that registered -- after
 // the ICP / GICP refinement when that is on -- is compared by M3C2 distances on the GPU (plade_cloud_m3c2: core points = reference
 // = the target with its normals, compared = the source under the final transformation; min_points 4 and reg_error 0 when not
@@ -281,10 +322,30 @@ bool m3c2_packed(plade_ctx *ctx, const float *T16, const float *core, size_t m, 
     }
     return true;
 }
+// PLADE_M3C2_CORE=<spacing>[,<seed>] (opt-in, 0 / unset = off; absolute, in the clouds' units; it acts only together with PLADE_M3C2):
+// the core points of the comparison are the minimum-spacing subsample of the target (plade_subsample_spacing; seed 0 when not given),
+// with their normals, instead of the whole target; the m3c2 line's core-point count shows it.  A value that does not parse (spacing
+// negative, not finite or so small that its fp32 square is below FLT_MIN, seed not an integer >= 0, anything behind them) prints one
+// warning and the whole target stays the core points; unset, nothing changes.
+const SubsampleSwitch &m3c2_core_switch() {
+    static const SubsampleSwitch sw = latched(cli_switches::parse_m3c2_core(getenv("PLADE_M3C2_CORE")));
+    return sw;
+}
 void m3c2_line(plade_ctx *ctx, const float *T16, const float *tg, size_t n_t, const float *sr, size_t n_s) {
     const M3c2Switch &sw = m3c2_switch();
+    if (!sw.on) return;
+    const SubsampleSwitch &cs = m3c2_core_switch();
+    std::vector<float> core;
+    const float *cp = tg;
+    size_t m = n_t;
+    if (cs.spacing > 0.0 && n_t) {
+        core.resize(n_t * 6);
+        plade_subsample_summary ss;
+        if (!subsample_packed(ctx, tg, n_t, cs.spacing, cs.seed, core.data(), ss)) return;
+        cp = core.data(); m = ss.kept;
+    }
     plade_m3c2_summary s;
-    if (!sw.on || !m3c2_packed(ctx, T16, tg, n_t, tg, n_t, sr, n_s, sw.radius, sw.depth, sw.min_points, sw.reg_error, nullptr, s)) return;
+    if (!m3c2_packed(ctx, T16, cp, m, tg, n_t, sr, n_s, sw.radius, sw.depth, sw.min_points, sw.reg_error, nullptr, s)) return;
     char b[280];
     snprintf(b, sizeof(b), "m3c2: %llu of %llu core points valid, %llu significant (mean %.6g, rms %.6g, max %.6g)", (unsigned long long)s.valid,
              (unsigned long long)s.m, (unsigned long long)s.significant, s.mean, s.rms, s.max);
@@ -782,10 +843,11 @@ bool register_packed(Eigen::Matrix<float, 4, 4> &transformation, const float *tg
 }
 
 // what every cloud goes through once its file is read: the filters that are switched on, in their order, then the normals of a
-// file that had none (estimate).  false: a message has been printed
+// file that had none (estimate), then the subsample when that is switched on.  false: a message has been printed
 bool prepare_loaded(const std::string &file_name, std::vector<float> &buf, bool estimate) {
     if (!remove_outliers_in_place(buf) || !keep_components_in_place(buf) || !smooth_in_place(buf)) return false;
-    return !estimate || buf.empty() || estimate_in_place(file_name, buf);
+    if (estimate && !buf.empty() && !estimate_in_place(file_name, buf)) return false;
+    return subsample_in_place(buf);
 }
 
 // a PLY file straight into a packed array (no pcl::PointCloud in between: at GPU speeds the 48 B/point
@@ -1020,6 +1082,19 @@ bool keep_components(pcl::PointCloud<pcl::PointNormal>::Ptr cloud, pcl::PointClo
     if (!components_packed(ctx, buf, radius, min_size, max_size, keep_largest, s)) return false;
     unflatten(buf.data(), (size_t)s.kept, filtered);
     if (info) { info->n = s.n; info->components = s.components; info->kept_components = s.kept_components; info->kept = s.kept; info->largest = s.largest; }
+    return true;
+}
+
+// subsampling: see plade.h
+bool subsample_cloud(pcl::PointCloud<pcl::PointNormal>::Ptr cloud, pcl::PointCloud<pcl::PointNormal> &subset, double spacing, uint64_t seed,
+                     CloudSubsample *info) {
+    plade_ctx *ctx = context();
+    if (!ctx) return false;
+    std::vector<float> buf = flatten(*cloud);
+    plade_subsample_summary s;
+    if (!subsample_packed(ctx, buf.data(), cloud->size(), spacing, seed, buf.data(), s)) return false;
+    unflatten(buf.data(), (size_t)s.kept, subset);
+    if (info) { info->n = s.n; info->kept = s.kept; info->rounds = s.rounds; }
     return true;
 }
 

@@ -657,6 +657,63 @@ int plade_subsample_spacing(plade_ctx *ctx, const float *rows, uint32_t n, uint3
 int plade_cloud_subsample_dev(plade_ctx *ctx, plade_cloud *cloud, const plade_subsample_params *params, plade_cloud **out,
                               uint8_t *keep_out, uint32_t *kept_index_out, plade_subsample_summary *summary);
 
+/* ---- consistent normal orientation: one side of the surface everywhere, without a viewpoint per point (no reference counterpart;
+ * Open3D ships it as orient_normals_consistent_tangent_plane, CloudCompare as its MST orientation; Hoppe et al. 1992) ---------------
+ * Semantics (plade_amd/csrc/orient.h).  Input: n >= 1 rows x y z nx ny nz, n < 2^31, all coordinates finite.
+ * d(i, j) = the fp32 FLANN L2 of (p_i, p_j), ((dx*dx + dy*dy) + dz*dz); r2 = (float)radius * (float)radius.
+ *   valid point  its three normal components are finite and each |component| <= 1e18f.  Every other point is left bit for bit as it
+ *                is, gets flip = 0 and label = -1 and is counted in `unoriented`.
+ *   graph        the vertices are the valid points; i ~ j when i != j and d(i, j) < r2 (the strict `<` of the radius filter).
+ *   edge weight  dot32 = (nx_i*nx_j + ny_i*ny_j) + nz_i*nz_j in fp32 without contraction; key32 = 0x7F800000u - bits(fabsf(dot32)):
+ *                the smaller key is the flatter pair.  Edges are ordered by (key32, min(i,j), max(i,j)); no two are equal.
+ *   tree, flips  the minimum spanning forest under that order (unique).  s_ij = 1 when dot32 < 0.0f, else 0; along every forest edge
+ *                flip_i ^ flip_j = s_ij.  That fixes a component's flips up to one bit, which its anchor fixes:
+ *   mode PLADE_ORIENT_VOTE     anchored provisionally at flip = 0 on the component's valid point of smallest index, the flip test of
+ *                plade_estimate_normals, t_i = ((vx - px) * nx + (vy - py) * ny) + (vz - pz) * nz in fp64 (v = viewpoint), is taken
+ *                on every provisionally flipped normal; when strictly more points have t_i < 0 than t_i > 0 the whole component is
+ *                toggled.  A tie toggles nothing.
+ *   mode PLADE_ORIENT_EXTREME  e_i = ((double)x*dx + (double)y*dy) + (double)z*dz (d = direction); the anchor is the component's valid
+ *                point with the largest (e_i, then the smaller index); it is flipped when the same form g on its normal is < 0.
+ *   inward = 1   inverts the decision of either mode (a room scanned from the inside: EXTREME with inward = 1).
+ *   output       each array may be NULL.  rows_out: the n rows, a flipped point's three normal floats with their sign bit toggled,
+ *                every other float copied bit for bit (may be pos_nrm itself); flip_out: n bytes 0 / 1; label_out: n int32, the
+ *                component of the graph, ids ascending in the order of each component's smallest index, -1 for invalid points;
+ *                summary: n, unoriented, components, flipped, tree_edges (= valid points - components), rounds (of the GPU's
+ *                Boruvka iteration, at most ceil(log2 n) + 1; the only field that is not part of the definition) and tree_key_sum
+ *                (the sum of key32 over the forest's edges).  The result depends on the rows and the parameters only, and is the
+ *                same bits on every run.
+ * Two parallel sheets of opposite orientation that are closer than `radius` get the same side: inherent to the method; keep
+ * `radius` below the thinnest wall.
+ * Errors: PLADE_EINVAL for n = 0 (or n >= 2^31), a NULL cloud, a non-finite coordinate, a radius that is not finite and > 0 or whose
+ * fp32 square is not finite or below FLT_MIN, a non-finite viewpoint or direction, direction = 0, a mode other than 0 or 1, inward
+ * not 0 or 1; the context stays usable.  A cloud without any valid point is PLADE_OK with everything copied.  A radius that is tiny
+ * against the cloud's extent is not refused: the grid's cell grows until 48e6 cells hold the cloud (the result is the same).
+ * plade_stats_get then reports orient_grid_s, orient_rounds_s (every launch of the rounds with the read-backs between them),
+ * orient_finish_s (anchors, ids, scatter to the original order; HIP events on the context's stream), orient_rounds,
+ * orient_components, orient_flipped and orient_grid_dx / _dy / _dz / _cell. */
+#define PLADE_ORIENT_VOTE 0
+#define PLADE_ORIENT_EXTREME 1
+typedef struct plade_orient_params {
+    double radius;               /* must be set (> 0), absolute, in the cloud's units: there is no automatic value */
+    int32_t mode;                /* PLADE_ORIENT_VOTE (default) or PLADE_ORIENT_EXTREME */
+    int32_t inward;              /* 0 (default) or 1 */
+    float viewpoint[3];          /* of PLADE_ORIENT_VOTE; default the origin */
+    float direction[3];          /* of PLADE_ORIENT_EXTREME; default (0, 0, 1); not zero */
+} plade_orient_params;
+typedef struct plade_orient_summary {
+    uint32_t n, unoriented, components, flipped, tree_edges, rounds;
+    uint64_t tree_key_sum;
+} plade_orient_summary;
+/* The defaults: radius = 0 (unset), mode = PLADE_ORIENT_VOTE, inward = 0, viewpoint (0, 0, 0), direction (0, 0, 1).  Needs no GPU. */
+void plade_orient_default_params(plade_orient_params *p);
+int plade_orient_normals(plade_ctx *ctx, const float *pos_nrm, uint32_t n, const plade_orient_params *params, float *rows_out,
+                         uint8_t *flip_out, int32_t *label_out, plade_orient_summary *summary);
+/* The same on a resident cloud (plade_cloud_upload / plade_cloud_upload_xyz) into a NEW resident cloud of the same n points, a
+ * resident cloud like any other: the point data makes no host round trip.  The same rows, flip, label and summary bits as
+ * plade_orient_normals on the cloud's rows.  Free both clouds with plade_cloud_free. */
+int plade_cloud_orient_normals_dev(plade_ctx *ctx, plade_cloud *cloud, const plade_orient_params *params, plade_cloud **out,
+                                   uint8_t *flip_out, int32_t *label_out, plade_orient_summary *summary);
+
 /* ---- smoothing: moving-least-squares plane projection, the step between outlier removal and normals (no reference counterpart;
  * PCL ships it as MovingLeastSquares, Open3D users expect it) -----------------------------------------------------------------------
  * Semantics (plade_amd/csrc/smooth.h).  Input: n >= 1 points, rows of `stride` >= 3 floats, x y z first, all

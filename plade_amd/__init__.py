@@ -33,6 +33,7 @@ ABI_SYMBOLS = [
     "plade_merge_clouds", "plade_merge_clouds_dev", "plade_cloud_download",
     "plade_component_default_params", "plade_label_components", "plade_cloud_filter_components_dev",
     "plade_subsample_default_params", "plade_subsample_spacing", "plade_cloud_subsample_dev",
+    "plade_orient_default_params", "plade_orient_normals", "plade_cloud_orient_normals_dev",
     "plade_smooth_default_params", "plade_smooth_cloud", "plade_cloud_smooth_dev",
     "plade_gicp_default_params", "plade_refine_gicp", "plade_refine_gicp_dev", "plade_gicp_linearize",
     "plade_m3c2_default_params", "plade_cloud_m3c2", "plade_cloud_m3c2_dev",
@@ -135,6 +136,23 @@ class SubsampleParams(C.Structure):
 class SubsampleSummary(C.Structure):
     """plade_subsample_summary: n, kept, rounds (the synchronous rounds until every point was decided)."""
     _fields_ = [("n", C.c_uint32), ("kept", C.c_uint32), ("rounds", C.c_uint32)]
+
+
+ORIENT_VOTE, ORIENT_EXTREME = 0, 1
+
+
+class OrientParams(C.Structure):
+    """plade_orient_params: the radius of the neighbour graph (absolute, no default), the anchor mode (ORIENT_VOTE with `viewpoint`,
+    ORIENT_EXTREME with `direction`) and `inward`, which inverts the anchor's decision."""
+    _fields_ = [("radius", C.c_double), ("mode", C.c_int32), ("inward", C.c_int32), ("viewpoint", C.c_float * 3),
+                ("direction", C.c_float * 3)]
+
+
+class OrientSummary(C.Structure):
+    """plade_orient_summary: n, unoriented (invalid normals, left as they are), components, flipped, tree_edges, rounds and the
+    sum of the forest's edge keys."""
+    _fields_ = [("n", C.c_uint32), ("unoriented", C.c_uint32), ("components", C.c_uint32), ("flipped", C.c_uint32),
+                ("tree_edges", C.c_uint32), ("rounds", C.c_uint32), ("tree_key_sum", C.c_uint64)]
 
 
 class SmoothParams(C.Structure):
@@ -302,6 +320,9 @@ def load_library(path=LIB_PATH):
     sig("plade_subsample_default_params", argtypes=[C.POINTER(SubsampleParams)], restype=None)
     sig("plade_subsample_spacing", argtypes=[p, p, u32, u32, C.POINTER(SubsampleParams), p, p, p, p, C.POINTER(SubsampleSummary)])
     sig("plade_cloud_subsample_dev", argtypes=[p, p, C.POINTER(SubsampleParams), C.POINTER(p), p, p, C.POINTER(SubsampleSummary)])
+    sig("plade_orient_default_params", argtypes=[C.POINTER(OrientParams)], restype=None)
+    sig("plade_orient_normals", argtypes=[p, p, u32, C.POINTER(OrientParams), p, p, p, C.POINTER(OrientSummary)])
+    sig("plade_cloud_orient_normals_dev", argtypes=[p, p, C.POINTER(OrientParams), C.POINTER(p), p, p, C.POINTER(OrientSummary)])
     sig("plade_smooth_default_params", argtypes=[C.POINTER(SmoothParams)], restype=None)
     sig("plade_smooth_cloud", argtypes=[p, p, u32, u32, C.POINTER(SmoothParams), p, p, p, p, p, p, p, C.POINTER(SmoothSummary)])
     sig("plade_cloud_smooth_dev", argtypes=[p, p, C.POINTER(SmoothParams), i32, C.POINTER(p), C.POINTER(SmoothSummary)])
@@ -412,6 +433,7 @@ _DEFAULTS = {Params: "plade_default_params",
              OutlierParams: "plade_outlier_default_params",
              ComponentParams: "plade_component_default_params",
              SubsampleParams: "plade_subsample_default_params",
+             OrientParams: "plade_orient_default_params",
              SmoothParams: "plade_smooth_default_params",
              M3c2Params: "plade_m3c2_default_params",
              FpfhParams: "plade_fpfh_default_params",
@@ -511,6 +533,29 @@ def _subsample_info(summ, keep, rnd):
         info["keep"] = keep.view(np.bool_)
     if rnd is not None:
         info["round"] = rnd
+    return info
+
+
+def orient_default_params():
+    """plade_orient_default_params (pure: needs no GPU) as a dict of the plade_orient_params fields."""
+    return _defaults_dict(OrientParams)
+
+
+def _orient_params(radius, mode, inward, viewpoint, direction):
+    prm = _defaults(OrientParams)
+    prm.radius = float(radius)
+    prm.mode = int(mode)
+    prm.inward = int(inward)
+    prm.viewpoint[:] = [float(x) for x in _viewpoint(viewpoint)]
+    prm.direction[:] = [float(x) for x in _viewpoint(direction)]
+    return prm
+
+
+def _orient_info(summ, flip, label):
+    info = {k: getattr(summ, k) for k, _ in OrientSummary._fields_}
+    if flip is not None:
+        info["flip"] = flip.view(np.bool_)
+        info["label"] = label
     return info
 
 
@@ -1351,6 +1396,43 @@ class Context:
         self._check(self.L.plade_cloud_subsample_dev(self.h, cloud.h, C.byref(prm), C.byref(h), _ptr(keep), _ptr(kept), C.byref(summ)))
         out = Cloud(self, None, handle=(int(summ.kept), h))
         return (out, kept[:summ.kept].copy(), _subsample_info(summ, keep, None)) if info else out
+
+    # ---- consistent normal orientation ------------------------------------------------------------
+    def orient_consistent(self, pos_nrm, radius, mode=ORIENT_VOTE, inward=0, viewpoint=(0.0, 0.0, 0.0), direction=(0.0, 0.0, 1.0),
+                          per_point=True):
+        """plade_orient_normals: the rows of an (N, 6) float32 array x y z nx ny nz with their normals on one side of the surface
+        per component of the graph "closer than radius" (fp32 squared distance, strict <): the flips follow the minimum spanning
+        forest of the edge keys 0x7F800000 - bits(|n_i . n_j|) ordered by (key, min index, max index); the side is the majority
+        of the viewpoint test (mode ORIENT_VOTE) or the normal of the extreme point along `direction` having a component along it
+        (ORIENT_EXTREME); inward=1 inverts it.  Points whose normal is not finite (or above 1e18) are left as they are.  Returns
+        (rows, info): the rows with the flipped normals' sign bits toggled and every other float copied bit for bit, and a dict with
+        n, unoriented, components, flipped, tree_edges, rounds, tree_key_sum and -- with per_point -- flip (N bools) and label (N
+        int32, the component, -1 where the normal is invalid)."""
+        a = _f32(pos_nrm)
+        if a.ndim != 2 or a.shape[1] != 6:
+            raise ValueError(f"an (N, 6) array x y z nx ny nz is required, got shape {a.shape}")
+        n = len(a)
+        prm = _orient_params(radius, mode, inward, viewpoint, direction)
+        rows = np.empty((n, 6), np.float32)
+        flip = np.zeros(n, np.uint8) if per_point else None
+        label = np.empty(n, np.int32) if per_point else None
+        summ = OrientSummary()
+        self._check(self.L.plade_orient_normals(self.h, _ptr(a), n, C.byref(prm), _ptr(rows), _ptr(flip), _ptr(label), C.byref(summ)))
+        return rows, _orient_info(summ, flip, label)
+
+    def orient_consistent_dev(self, cloud, radius, mode=ORIENT_VOTE, inward=0, viewpoint=(0.0, 0.0, 0.0), direction=(0.0, 0.0, 1.0),
+                              info=False):
+        """plade_cloud_orient_normals_dev: orient_consistent on a resident cloud (upload, upload_xyz) into a new resident Cloud of
+        the same points; the point data makes no host round trip.  With info also the info dict as orient_consistent gives it: the
+        same bits."""
+        prm = _orient_params(radius, mode, inward, viewpoint, direction)
+        flip = np.zeros(cloud.n, np.uint8) if info else None
+        label = np.empty(cloud.n, np.int32) if info else None
+        summ = OrientSummary()
+        h = C.c_void_p()
+        self._check(self.L.plade_cloud_orient_normals_dev(self.h, cloud.h, C.byref(prm), C.byref(h), _ptr(flip), _ptr(label), C.byref(summ)))
+        out = Cloud(self, None, handle=(int(summ.n), h))
+        return (out, _orient_info(summ, flip, label)) if info else out
 
     # ---- smoothing ---------------------------------------------------------------------------------
     def smooth_cloud(self, points, radius, min_neighbours=None, viewpoint=(0.0, 0.0, 0.0), normals=True, per_point=True, moments=False):

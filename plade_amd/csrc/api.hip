@@ -16,6 +16,7 @@
 #include "corr_pose.h"
 #include "keypoints.h"
 #include "subsample.h"
+#include "orient.h"
 
 using namespace plade;
 
@@ -157,6 +158,7 @@ extern "C" void plade_ctx_destroy(plade_ctx *ctx) {
     if (ctx->corr_pose_work) plade::corr_pose_work_destroy(ctx->corr_pose_work);
     if (ctx->iss_work) plade::iss_work_destroy(ctx->iss_work);
     if (ctx->subsample_work) plade::subsample_work_destroy(ctx->subsample_work);
+    if (ctx->orient_work) plade::orient_work_destroy(ctx->orient_work);
     (void)hipStreamDestroy(ctx->stream);
     if (ctx->pf.stream) { (void)hipStreamSynchronize(ctx->pf.stream); (void)hipStreamDestroy(ctx->pf.stream); }
     delete ctx;

@@ -39,7 +39,8 @@ inline bool smooth_radius(double r) {
     const float r2 = (float)r * (float)r;
     return non_negative(r) && std::isfinite(r2) && (r == 0.0 || r2 >= FLT_MIN);
 }
-// the spacing of a subsample: 0 = off, otherwise what plade_subsample_spacing accepts
+// the spacing of a subsample and the radius of the consistent orientation: 0 = off, otherwise what plade_subsample_spacing and
+// plade_orient_normals accept
 inline bool spacing_or_off(double r) { return r == 0.0 || radius_sq32(r); }
 // the RANSAC pose's inlier distance: its fp64 square is finite and > 0
 inline bool inlier_dist(double v) { return positive(v) && std::isfinite(v * v) && v * v > 0.0; }
@@ -208,6 +209,19 @@ inline Parsed<SubsampleSwitch> parse_m3c2_core(const char *text) {
                               " is not <spacing>[,<seed>] with spacing >= 0 (its square not below FLT_MIN) and seed an integer >= 0;"
                               " the whole target as core points"};
     return parse_spacing_seed(spec, text);
+}
+
+// <radius>[,<mode>[,<inward>]] of PLADE_CONSISTENT_NORMALS: radius 0 = off; mode 0 = vote against the origin, 1 = extreme point along +z
+struct OrientSwitch { double radius = 0.0; int mode = 0, inward = 0; };
+inline Parsed<OrientSwitch> parse_consistent_normals(const char *text) {
+    static const Field f[] = {real(spacing_or_off), integer(0, 1), integer(0, 1)};
+    static const Spec spec = {"PLADE_CONSISTENT_NORMALS", f, 3, 1,
+                              " is not <radius>[,<mode>[,<inward>]] with radius >= 0 (its square not below FLT_MIN), mode 0 or 1 and inward 0 or 1;"
+                              " no orientation"};
+    Parsed<OrientSwitch> p;
+    Value v[3] = {};
+    if (parse(spec, text, v, p.warning)) { p.value.radius = v[0].r; p.value.mode = (int)v[1].i; p.value.inward = (int)v[2].i; }
+    return p;
 }
 
 inline Parsed<float> parse_merge(const char *text) {   // < 0: off

@@ -89,7 +89,7 @@ struct plade_cloud {
     std::vector<float> host_copy;  // pos_nrm kept for the small host-side gathers
 };
 
-namespace plade { struct RegistrationWork; struct RansacWork; struct NormalsWork; struct RefineWork; struct DistWork; struct OutlierWork; struct MergeWork; struct ComponentWork; struct SmoothWork; struct M3c2Work; struct FpfhWork; struct CorrPoseWork; struct IssWork; struct SubsampleWork; }
+namespace plade { struct RegistrationWork; struct RansacWork; struct NormalsWork; struct RefineWork; struct DistWork; struct OutlierWork; struct MergeWork; struct ComponentWork; struct SmoothWork; struct M3c2Work; struct FpfhWork; struct CorrPoseWork; struct IssWork; struct SubsampleWork; struct OrientWork; }
 namespace plade { void comm_all_gather_dev(plade_comm *c, const void *d_send, void *d_recv, size_t bytes, hipStream_t stream); }
 
 struct plade_ctx {
@@ -477,6 +477,8 @@ struct plade_ctx {
     plade::IssWork *iss_work = nullptr;
     // grid, state words, active lists and kept list of plade_subsample_spacing (behind them too)
     plade::SubsampleWork *subsample_work = nullptr;
+    // grid, snapshot, hook words, per-root minima, records, active lists and anchors of plade_orient_normals (behind them too)
+    plade::OrientWork *orient_work = nullptr;
 
     template <class T>
     void put(const std::string &name, const T *data, size_t count) {

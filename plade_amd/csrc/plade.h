@@ -125,6 +125,26 @@ struct CloudSubsample {
 bool subsample_cloud(pcl::PointCloud<pcl::PointNormal>::Ptr cloud, pcl::PointCloud<pcl::PointNormal> &subset, double spacing,
                      uint64_t seed = 0, CloudSubsample *info = nullptr);
 
+/** Consistent normal orientation (no counterpart in the reference): the fields of plade_orient_summary (include/plade_hip.h). */
+struct NormalOrientation {
+    uint32_t n = 0, unoriented = 0, components = 0, flipped = 0, tree_edges = 0, rounds = 0;
+    uint64_t tree_key_sum = 0;
+};
+/** Puts the normals of a cloud on one side of the surface on the GPU (plade_orient_normals), per connected component of the graph
+ *  "closer than radius" (absolute, in the cloud's units; fp32 squared distance, strict <): the flips follow the minimum spanning forest
+ *  of the flattest neighbour pairs (Hoppe et al. 1992), so no viewpoint per point is needed -- merged clouds, moved scans and files with
+ *  unoriented normals.  mode 0: every component takes the side on which more of its normals face `reference`, a viewpoint of three
+ *  floats (nullptr: the origin); mode 1: the normal of the component's extreme point along `reference`, a direction of three floats
+ *  that must not be zero (nullptr: +z), gets a component along it.  inward inverts either decision.  Normals that
+ *  are not finite stay as they are.  `oriented` receives the same points in the same order, flipped normals with their sign bits
+ *  toggled (it may be *cloud).  Two parallel sheets closer than radius get the same side: keep radius below the thinnest wall.
+ *  false: invalid input or no GPU; a message is printed and `oriented` is unchanged.  The CLI and the file overload of registration()
+ *  orient both clouds of a pair after PLADE_ESTIMATE_NORMALS when PLADE_CONSISTENT_NORMALS=<radius>[,<mode>[,<inward>]] is set
+ *  (reference: the origin / +z), and print one line per cloud.  This is not the `orient_normals` parameter of the registration,
+ *  which only makes the planes' normals agree with their points' (DESIGN.md section 2). */
+bool orient_cloud_normals(pcl::PointCloud<pcl::PointNormal>::Ptr cloud, pcl::PointCloud<pcl::PointNormal> &oriented, double radius,
+                          int mode = 0, bool inward = false, const float *reference = nullptr, NormalOrientation *info = nullptr);
+
 /** Smoothing (no counterpart in the reference): the fields of plade_smooth_summary (include/plade_hip.h). */
 struct CloudSmoothing {
     uint64_t n = 0, fitted = 0;   // points in, points that were fitted and projected

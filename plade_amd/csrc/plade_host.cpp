@@ -43,7 +43,7 @@ void trace(const char *what) {
 // parser has to say about a rejected value goes to std::cerr, not to the calling thread's console.
 using cli_switches::GicpSwitch; using cli_switches::M3c2Switch; using cli_switches::FpfhSwitch; using cli_switches::FeatureRegisterSwitch;
 using cli_switches::KeypointSwitch; using cli_switches::OutlierSwitch; using cli_switches::ComponentSwitch; using cli_switches::SmoothSwitch;
-using cli_switches::SubsampleSwitch;
+using cli_switches::SubsampleSwitch; using cli_switches::OrientSwitch;
 template <class S> S latched(const cli_switches::Parsed<S> &p) {
     if (!p.warning.empty()) std::cerr << p.warning << std::endl;
     return p.value;
@@ -253,6 +253,49 @@ void evaluate_line(plade_ctx *ctx, const float *T16, const float *tg, size_t n_t
     snprintf(b, sizeof(b), "evaluation: fitness %.4f, rmse %.6g, %llu of %llu source points within %g", s.fitness, s.rmse,
              (unsigned long long)s.count, (unsigned long long)s.n, (double)d);
     con_out() << b << std::endl;
+}
+
+// PLADE_CONSISTENT_NORMALS=<radius>[,<mode>[,<inward>]] (opt-in, 0 / unset = off; the radius absolute, in the clouds' units): the normals
+// of both clouds of a pair are put on one side of the surface per component of the graph "closer than radius" (plade_orient_normals:
+// the flips follow the minimum spanning forest of the flattest neighbour pairs; mode 0, the default, lets every component vote
+// against the origin, mode 1 takes the extreme point along +z; inward 1 inverts the decision), as the last preparation step that
+// touches normals -- after PLADE_SMOOTH and PLADE_ESTIMATE_NORMALS, before PLADE_SUBSAMPLE; one console line per cloud.  Positions,
+// point count and order stay.  A value that does not parse (radius negative, not finite or so small that its fp32 square is below
+// FLT_MIN, mode or inward not 0 or 1, anything behind them) prints one warning and orients nothing; unset, nothing changes.
+const OrientSwitch &orient_switch() {
+    static const OrientSwitch sw = latched(cli_switches::parse_consistent_normals(getenv("PLADE_CONSISTENT_NORMALS")));
+    return sw;
+}
+// the normal columns of an x y z nx ny nz array oriented in place (view / dir: nullptr = the origin / +z)
+bool orient_packed(plade_ctx *ctx, float *rows, size_t n, double radius, int mode, int inward, const float *view, const float *dir,
+                   plade_orient_summary &s) {
+    plade_orient_params prm;
+    plade_orient_default_params(&prm);
+    prm.radius = radius; prm.mode = mode; prm.inward = inward;
+    if (view) memcpy(prm.viewpoint, view, 12);
+    if (dir) memcpy(prm.direction, dir, 12);
+    trace("orient: orienting");
+    // (in place: the upload of the rows precedes the read-back on the context's stream)
+    const int rc = plade_orient_normals(ctx, rows, (uint32_t)n, &prm, rows, nullptr, nullptr, &s);
+    trace("orient: done");
+    if (rc != PLADE_OK) {
+        con_err() << "normal orientation failed: " << plade_last_error(ctx) << std::endl;
+        return false;
+    }
+    return true;
+}
+bool orient_in_place(std::vector<float> &buf) {
+    const OrientSwitch &sw = orient_switch();
+    if (!(sw.radius > 0.0) || buf.empty()) return true;
+    plade_ctx *ctx = context();
+    if (!ctx) return false;
+    plade_orient_summary s;
+    if (!orient_packed(ctx, buf.data(), buf.size() / 6, sw.radius, sw.mode, sw.inward, nullptr, nullptr, s)) return false;
+    char b[240];
+    snprintf(b, sizeof(b), "consistent normals: flipped %u of %u points in %u components (radius %g, %u without a normal, %u rounds)", s.flipped,
+             s.n, s.components, sw.radius, s.unoriented, s.rounds);
+    con_out() << b << std::endl;
+    return true;
 }
 
 // PLADE_SUBSAMPLE=<spacing>[,<seed>] (opt-in, 0 / unset = off; the spacing absolute, in the clouds' units): both clouds of a pair are
@@ -843,11 +886,12 @@ bool register_packed(Eigen::Matrix<float, 4, 4> &transformation, const float *tg
 }
 
 // what every cloud goes through once its file is read: the filters that are switched on, in their order, then the normals of a
-// file that had none (estimate), then the subsample when that is switched on.  false: a message has been printed
+// file that had none (estimate), then the consistent orientation and the subsample when they are switched on.  false: a message has
+// been printed
 bool prepare_loaded(const std::string &file_name, std::vector<float> &buf, bool estimate) {
     if (!remove_outliers_in_place(buf) || !keep_components_in_place(buf) || !smooth_in_place(buf)) return false;
     if (estimate && !buf.empty() && !estimate_in_place(file_name, buf)) return false;
-    return subsample_in_place(buf);
+    return orient_in_place(buf) && subsample_in_place(buf);
 }
 
 // a PLY file straight into a packed array (no pcl::PointCloud in between: at GPU speeds the 48 B/point
@@ -1095,6 +1139,24 @@ bool subsample_cloud(pcl::PointCloud<pcl::PointNormal>::Ptr cloud, pcl::PointClo
     if (!subsample_packed(ctx, buf.data(), cloud->size(), spacing, seed, buf.data(), s)) return false;
     unflatten(buf.data(), (size_t)s.kept, subset);
     if (info) { info->n = s.n; info->kept = s.kept; info->rounds = s.rounds; }
+    return true;
+}
+
+// consistent normal orientation: see plade.h
+bool orient_cloud_normals(pcl::PointCloud<pcl::PointNormal>::Ptr cloud, pcl::PointCloud<pcl::PointNormal> &oriented, double radius, int mode,
+                          bool inward, const float *reference, NormalOrientation *info) {
+    plade_ctx *ctx = context();
+    if (!ctx) return false;
+    std::vector<float> buf = flatten(*cloud);
+    plade_orient_summary s;
+    if (!orient_packed(ctx, buf.data(), cloud->size(), radius, mode, inward ? 1 : 0, mode == 0 ? reference : nullptr,
+                       mode == 0 ? nullptr : reference, s))
+        return false;
+    unflatten(buf.data(), (size_t)s.n, oriented);
+    if (info) {
+        info->n = s.n; info->unoriented = s.unoriented; info->components = s.components; info->flipped = s.flipped;
+        info->tree_edges = s.tree_edges; info->rounds = s.rounds; info->tree_key_sum = s.tree_key_sum;
+    }
     return true;
 }
 

@@ -1,22 +1,8 @@
 // plade_amd/csrc/api.hip -- context management and instrumentation entry points of the C ABI.
 #include "ctx.h"
-#include "components.h"
-#include "distances.h"
 #include "exact_sort.h"
-#include "icp.h"
-#include "merge.h"
-#include "normals.h"
-#include "outliers.h"
 #include "pipeline.h"
 #include "ransac.h"
-#include "smooth.h"
-#include "gicp.h"
-#include "m3c2.h"
-#include "fpfh.h"
-#include "corr_pose.h"
-#include "keypoints.h"
-#include "subsample.h"
-#include "orient.h"
 
 using namespace plade;
 
@@ -145,20 +131,7 @@ extern "C" void plade_ctx_destroy(plade_ctx *ctx) {
     (void)hipStreamSynchronize(ctx->stream);
     if (ctx->reg_work) plade::registration_work_destroy(ctx->reg_work);
     if (ctx->ransac_work) plade::ransac_work_destroy(ctx->ransac_work);
-    if (ctx->normals_work) plade::normals_work_destroy(ctx->normals_work);
-    if (ctx->icp_work) plade::refine_work_destroy(ctx->icp_work);
-    if (ctx->dist_work) plade::dist_work_destroy(ctx->dist_work);
-    if (ctx->outlier_work) plade::outlier_work_destroy(ctx->outlier_work);
-    if (ctx->merge_work) plade::merge_work_destroy(ctx->merge_work);
-    if (ctx->component_work) plade::component_work_destroy(ctx->component_work);
-    if (ctx->smooth_work) plade::smooth_work_destroy(ctx->smooth_work);
-    if (ctx->gicp_work) plade::refine_work_destroy(ctx->gicp_work);
-    if (ctx->m3c2_work) plade::m3c2_work_destroy(ctx->m3c2_work);
-    if (ctx->fpfh_work) plade::fpfh_work_destroy(ctx->fpfh_work);
-    if (ctx->corr_pose_work) plade::corr_pose_work_destroy(ctx->corr_pose_work);
-    if (ctx->iss_work) plade::iss_work_destroy(ctx->iss_work);
-    if (ctx->subsample_work) plade::subsample_work_destroy(ctx->subsample_work);
-    if (ctx->orient_work) plade::orient_work_destroy(ctx->orient_work);
+    ctx->reset_tool_work();
     (void)hipStreamDestroy(ctx->stream);
     if (ctx->pf.stream) { (void)hipStreamSynchronize(ctx->pf.stream); (void)hipStreamDestroy(ctx->pf.stream); }
     delete ctx;

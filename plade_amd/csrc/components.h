@@ -24,11 +24,3 @@
 // unions happen, or whether the input is a host array or a resident cloud.
 #pragma once
 #include "ctx.h"
-
-namespace plade {
-
-struct ComponentWork;
-ComponentWork *component_work_create();
-void component_work_destroy(ComponentWork *w);
-
-}  // namespace plade

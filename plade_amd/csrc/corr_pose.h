@@ -41,8 +41,4 @@ constexpr int CORR_SCORE_TILE = 64;     // correspondences per LDS tile of k_hyp
 constexpr int CORR_SCORE_CHUNK = 256;   // the smallest number of correspondences per workgroup (blockIdx.y)
 constexpr int CORR_MOMENTS = 17;        // n, s (3), q (3), C (9), sum d2: plade_corr_pose_moments
 
-struct CorrPoseWork;
-CorrPoseWork *corr_pose_work_create();
-void corr_pose_work_destroy(CorrPoseWork *w);
-
 }  // namespace plade

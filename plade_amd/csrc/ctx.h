@@ -3,6 +3,7 @@
 #include "common.h"
 #include "plade_hip.h"
 #include "launch.h"
+#include "work_slot.h"
 #include <ctime>
 #include <sys/prctl.h>
 
@@ -89,21 +90,24 @@ struct plade_cloud {
     std::vector<float> host_copy;  // pos_nrm kept for the small host-side gathers
 };
 
-namespace plade { struct RegistrationWork; struct RansacWork; struct NormalsWork; struct RefineWork; struct DistWork; struct OutlierWork; struct MergeWork; struct ComponentWork; struct SmoothWork; struct M3c2Work; struct FpfhWork; struct CorrPoseWork; struct IssWork; struct SubsampleWork; struct OrientWork; }
+namespace plade { struct RegistrationWork; struct RansacWork; }
 namespace plade { void comm_all_gather_dev(plade_comm *c, const void *d_send, void *d_recv, size_t bytes, hipStream_t stream); }
 
 struct plade_ctx {
     int device = 0;
     plade::RegistrationWork *reg_work = nullptr;
     plade::RansacWork *ransac_work = nullptr;
-    plade::NormalsWork *normals_work = nullptr;   // grid and lists of plade_estimate_normals / plade_cloud_upload_xyz
-    plade::RefineWork *icp_work = nullptr;        // stage grids, sample and state of plade_refine_icp / plade_icp_linearize
-    plade::DistWork *dist_work = nullptr;         // grid, probes and partials of plade_cloud_distances
-    plade::OutlierWork *outlier_work = nullptr;   // grid, lists and partials of plade_filter_outliers
-    plade::MergeWork *merge_work = nullptr;       // concatenation, keys, runs and fused rows of plade_merge_clouds
-    plade::ComponentWork *component_work = nullptr;   // grid, parents, labels and lists of plade_label_components
-    plade::SmoothWork *smooth_work = nullptr;     // grid, per-point outputs and partials of plade_smooth_cloud
-    plade::RefineWork *gicp_work = nullptr;       // stage grids and state of plade_refine_gicp / plade_gicp_linearize
+    // The cloud tools' work areas (grids, lists, partials, the host-pointer entry points' device copies), one slot per tool: made on
+    // first use by the tool's own .hip file (work_in<XWork>(ctx->x_work), work_slot.h), released by reset_tool_work() or with the
+    // context.  icp_work and gicp_work both hold a RefineWork (icp_core.h).
+    plade::WorkSlot normals_work, icp_work, dist_work, outlier_work, merge_work, component_work, smooth_work, gicp_work, m3c2_work,
+        fpfh_work, corr_pose_work, iss_work, subsample_work, orient_work;
+    // the work structs' destructors call HIP (DBuf, EventSpans): plade_ctx_destroy runs this with the device set, before the stream goes
+    void reset_tool_work() {
+        for (plade::WorkSlot *s : {&normals_work, &icp_work, &dist_work, &outlier_work, &merge_work, &component_work, &smooth_work,
+                                   &gicp_work, &m3c2_work, &fpfh_work, &corr_pose_work, &iss_work, &subsample_work, &orient_work})
+            s->reset();
+    }
     plade_ctx *peers[PLADE_GROUP_MAX - 1] = {};   // the contexts of pairs 1.. of a group (plade_registration_pairs): stream, aux, work areas
     hipEvent_t ev_group = nullptr;   // end of a group's joint plane extraction on `stream` (the peers' streams wait for it)
     bool in_group = false;      // this context carries one pair of a group of several (register_group)
@@ -466,20 +470,6 @@ struct plade_ctx {
     // generic scratch
     plade::DBuf<char> scratch[8];
     plade::HBuf<char> pinned[4];
-    // grids, per-core-point outputs and partials of plade_cloud_m3c2 (like smooth_work above; behind the other members, whose
-    // offsets stay what they were)
-    plade::M3c2Work *m3c2_work = nullptr;
-    // grid, axes, histograms and match tables of plade_cloud_fpfh / plade_match_features (behind the other members as well)
-    plade::FpfhWork *fpfh_work = nullptr;
-    // packed correspondences, hypothesis tables and state of plade_estimate_pose_corr / plade_corr_pose_moments (behind them too)
-    plade::CorrPoseWork *corr_pose_work = nullptr;
-    // grid, per-point outputs, list and partials of plade_cloud_keypoints_iss; the index list of plade_features_select (behind them too)
-    plade::IssWork *iss_work = nullptr;
-    // grid, state words, active lists and kept list of plade_subsample_spacing (behind them too)
-    plade::SubsampleWork *subsample_work = nullptr;
-    // grid, snapshot, hook words, per-root minima, records, active lists and anchors of plade_orient_normals (behind them too)
-    plade::OrientWork *orient_work = nullptr;
-
     template <class T>
     void put(const std::string &name, const T *data, size_t count) {
         if (!params.dump) return;

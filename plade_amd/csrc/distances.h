@@ -18,11 +18,3 @@
 //   errors      PLADE_EINVAL: NULL clouds or summary, n = 0, non-finite coordinates or T, d <= 0 or not finite, stride < 3
 #pragma once
 #include "ctx.h"
-
-namespace plade {
-
-struct DistWork;
-DistWork *dist_work_create();
-void dist_work_destroy(DistWork *w);
-
-}  // namespace plade

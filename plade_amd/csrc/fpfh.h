@@ -49,10 +49,6 @@ constexpr int FPFH_BINS = 11, FPFH_DIM = 33;
 constexpr int FEAT_TILE = 64;     // targets per LDS tile of k_feat_match
 constexpr int FEAT_CHUNK = 512;   // the smallest number of targets per workgroup (blockIdx.y)
 
-struct FpfhWork;
-FpfhWork *fpfh_work_create();
-void fpfh_work_destroy(FpfhWork *w);
-
 }  // namespace plade
 
 // a resident descriptor table: n x 33 fp32, rows of NaN where a point is not described

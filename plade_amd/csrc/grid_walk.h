@@ -70,6 +70,13 @@ inline double grid_margin(const GridView &g, const float bbmin[3], const float b
 inline float radius_cell(double r, const float mn[3], const float mx[3], double factor = 1.03) {
     return (float)std::min(factor * r + 4e-6 * amax_of(mn, mx), 1e37);
 }
+// The radius of such a search as its entry point accepts it: finite and > 0, also as fp32, and r2 = (float)r * (float)r finite.
+// square_not_below_flt_min: r2 a normal fp32 number too, for the tools in which a point must be its own neighbour -- d = 0 < r2 has
+// to hold, and a subnormal r2 carries few bits.
+inline bool radius_ok(double radius, bool square_not_below_flt_min) {
+    const float r = (float)radius;
+    return std::isfinite(radius) && std::isfinite(r) && r > 0.f && std::isfinite(r * r) && (!square_not_below_flt_min || r * r >= FLT_MIN);
+}
 
 // The grid of a k-nearest-neighbour search over d_rows (n points, `stride` floats apart, bounding box known).  The cell: a
 // surface-like cloud spread over the faces of its box has r_k = sqrt(k A / (pi n)) (A = the box's area); the cell is 1.5 r_k, so

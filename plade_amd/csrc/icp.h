@@ -31,8 +31,4 @@ namespace plade {
 constexpr int ICP_MOMENTS = 29;      // 21 J^T J, 6 J^T r, sum r^2, count
 constexpr int ICP_MAX_STAGES = 16;
 
-// the work area of one variant of the refinement (icp_core.h); a context makes one per variant on first use
-struct RefineWork;
-void refine_work_destroy(RefineWork *w);
-
 }  // namespace plade

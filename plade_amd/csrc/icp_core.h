@@ -19,6 +19,7 @@
 // Included by those two .hip files only.  What is not named by ctx.h sits in an unnamed namespace: each file gets kernels of its own.
 #pragma once
 #include "icp.h"
+#include "cloud_tool.h"
 #include "fixed_reduce.h"
 #include "grid_walk.h"
 #include "voxel.h"
@@ -328,13 +329,6 @@ inline void check_T(const float *T16, const std::string &who) {
     for (int k = 0; k < 16; ++k) PLADE_REQUIRE(std::isfinite(T16[k]), PLADE_EINVAL, who + ": T_in must be finite");
 }
 
-template <class M>
-RefineWork &work_of(plade_ctx *ctx) {
-    RefineWork *&w = ctx->*M::slot;
-    if (!w) w = new RefineWork;
-    return *w;
-}
-
 // what the loop and the seam begin alike: the state and the partials for `blocks` workgroups, the state's upload from T (and the
 // given centre), and the arguments of k_icp_solve that do not depend on the schedule
 template <class M>
@@ -360,8 +354,7 @@ template <class M>
 int refine_dev(plade_ctx *ctx, RefineWork &W, const float *d_tgt, uint32_t n_t, const float tmn[3], const float tmx[3], const float *d_src,
                uint32_t n_s, const float smn[3], const float smx[3], const float *T_in16, const typename M::params *prm, float *T_out16,
                typename M::result *res) {
-    typename M::params p;
-    if (prm) p = *prm; else M::defaults(&p);
+    const typename M::params p = params_or_default(prm, M::defaults);
     const IcpConfig c = resolve(p, tmn, tmx, M::who);
     typename M::Args a;
     memset(&a, 0, sizeof(a));
@@ -432,7 +425,7 @@ int refine_host(plade_ctx *ctx, const float *tgt_pos_nrm, uint32_t n_t, const fl
         PLADE_REQUIRE(tgt_pos_nrm && src_pos_nrm && T_in16 && T_out16, PLADE_EINVAL, name + ": bad argument");
         PLADE_REQUIRE(n_t >= 1 && n_s >= 1, PLADE_EINVAL, name + ": empty cloud");
         check_T(T_in16, M::who);
-        RefineWork &W = work_of<M>(ctx);
+        RefineWork &W = work_in<RefineWork>(ctx->*M::slot);
         float tmn[3], tmx[3], smn[3], smx[3];
         upload_rows(ctx, W.in_t, tgt_pos_nrm, n_t, 6, tmn, tmx);
         upload_rows(ctx, W.in_s, src_pos_nrm, n_s, 6, smn, smx);
@@ -449,8 +442,8 @@ int refine_resident(plade_ctx *ctx, plade_cloud *tgt, plade_cloud *src, const fl
         PLADE_REQUIRE(tgt->dev.n >= 1 && src->dev.n >= 1, PLADE_EINVAL, name + ": empty cloud");
         check_T(T_in16, M::who);
         const CloudDev &t = tgt->dev, &s = src->dev;
-        return refine_dev<M>(ctx, work_of<M>(ctx), t.aos.p, t.n, t.bbmin, t.bbmax, s.aos.p, s.n, s.bbmin, s.bbmax, T_in16, params,
-                             T_out16, result);
+        return refine_dev<M>(ctx, work_in<RefineWork>(ctx->*M::slot), t.aos.p, t.n, t.bbmin, t.bbmax, s.aos.p, s.n, s.bbmin, s.bbmax,
+                             T_in16, params, T_out16, result);
     });
 }
 
@@ -469,7 +462,7 @@ int linearize_seam(plade_ctx *ctx, const float *tgt_pos_nrm, uint32_t n_t, const
         typename M::Args a;
         memset(&a, 0, sizeof(a));
         M::extra(a, epsilon, M::seam);
-        RefineWork &W = work_of<M>(ctx);
+        RefineWork &W = work_in<RefineWork>(ctx->*M::slot);
         float tmn[3], tmx[3], smn[3], smx[3];
         upload_rows(ctx, W.in_t, tgt_pos_nrm, n_t, 6, tmn, tmx);
         upload_rows(ctx, W.in_s, src, n_s, stride, smn, smx);

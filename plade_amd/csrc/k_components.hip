@@ -17,11 +17,9 @@
 //   select   k_cc_pass; with keep_largest the keys ~size << 32 | id (all ones in the high word: does not pass) through the stable
 //            sort_pairs_u64 and k_cc_mark_first; k_cc_summary (largest, kept components); k_cc_keep, compact_flags, gather_rows (prims.h).
 #include "components.h"
+#include "cloud_tool.h"
 #include "grid_walk.h"
-#include "prims.h"
-#include "stages.h"
 #include "voxel.h"
-#include <functional>
 
 namespace plade {
 
@@ -159,28 +157,23 @@ __global__ __launch_bounds__(ROW_TPB) void k_cc_keep(const int32_t *__restrict__
 
 }  // namespace
 
-struct ComponentWork {
+struct ComponentWork : KeepWork {
     TargetGrid grid;
-    DBuf<uint32_t> parent, root, flags, root_pos, root_list, pos, kept, size, count, sort_val, sort_val2;
+    DBuf<uint32_t> parent, root, root_pos, root_list, size, count, sort_val, sort_val2;
     DBuf<unsigned long long> sort_key, sort_key2;
     DBuf<int32_t> label;
-    DBuf<uint8_t> keep, comp_kept;
-    DBuf<float> in, out;             // the host-pointer entry point's device copies (grow-only)
+    DBuf<uint8_t> comp_kept;
     EventSpans<5> spans;             // grid, link, label, compact
     uint32_t h_count[2] = {0, 0};    // the largest size, the kept components
     uint32_t components = 0;
 };
-ComponentWork *component_work_create() { return new ComponentWork; }
-void component_work_destroy(ComponentWork *w) { delete w; }
 
 namespace {
 
 void check_params(uint32_t n, uint32_t stride, const plade_component_params &p) {
     PLADE_REQUIRE(n >= 1, PLADE_EINVAL, "label_components: the cloud is empty (n = 0)");
     PLADE_REQUIRE(stride >= 3, PLADE_EINVAL, "label_components: stride must be >= 3 floats");
-    const float r = (float)p.radius;
-    PLADE_REQUIRE(std::isfinite(p.radius) && std::isfinite(r) && r > 0.f && std::isfinite(r * r), PLADE_EINVAL,
-                  "label_components: radius must be finite and > 0");
+    PLADE_REQUIRE(radius_ok(p.radius, false), PLADE_EINVAL, "label_components: radius must be finite and > 0");
     PLADE_REQUIRE(p.min_size >= 1, PLADE_EINVAL, "label_components: min_size must be >= 1");
     PLADE_REQUIRE(p.max_size == 0 || p.max_size >= p.min_size, PLADE_EINVAL, "label_components: max_size must be 0 (no bound) or >= min_size");
     PLADE_REQUIRE(p.keep_largest >= 0, PLADE_EINVAL, "label_components: keep_largest must be >= 0");
@@ -190,7 +183,7 @@ void check_params(uint32_t n, uint32_t stride, const plade_component_params &p) 
 // list in W, gathers the kept rows into dst(kept) -- not called when nothing is kept --, waits, fills the summary and the stats.
 // Returns the number of kept points.
 uint32_t components_dev(plade_ctx *ctx, ComponentWork &W, const float *d_rows, uint32_t n, uint32_t stride, const float bbmin[3],
-                        const float bbmax[3], const plade_component_params &p, const std::function<float *(uint32_t)> &dst,
+                        const float bbmax[3], const plade_component_params &p, const KeepRows &dst,
                         plade_component_summary *summary) {
     W.spans.mark(ctx, 0);
     TargetGrid &G = W.grid;
@@ -208,10 +201,10 @@ uint32_t components_dev(plade_ctx *ctx, ComponentWork &W, const float *d_rows, u
     HIP_TRY(hipGetLastError());
     W.spans.mark(ctx, 2);
 
-    uint32_t *d_root = W.root.ensure(n), *d_flags = W.flags.ensure((size_t)n + 1), *d_size = W.size.ensure(n), *d_cnt = W.count.ensure(4);
+    uint32_t *d_root = W.root.ensure(n), *d_size = W.size.ensure(n), *d_cnt = W.count.ensure(4);
     int32_t *d_label = W.label.ensure(n);
     uint8_t *d_keep = W.keep.ensure((size_t)n + 4), *d_ckept = W.comp_kept.ensure((size_t)n + 4);
-    ctx->fill_async(d_flags + n, 0, 4);    // compact_flags scans n + 1 entries
+    uint32_t *d_flags = keep_flags(ctx, W, n);   // first the roots' flags, then the kept points'
     ctx->fill_async(d_size, 0, (size_t)n * 4);
     ctx->fill_async(d_cnt, 0, 16);
     hipLaunchKernelGGL(k_cc_flatten, dim3(cdiv(n, ROW_TPB)), dim3(ROW_TPB), 0, ctx->stream, a.parent, n, d_root, d_flags);
@@ -237,8 +230,7 @@ uint32_t components_dev(plade_ctx *ctx, ComponentWork &W, const float *d_rows, u
     HIP_TRY(hipMemcpyAsync(W.h_count, d_cnt, 8, hipMemcpyDeviceToHost, ctx->stream));
     W.spans.mark(ctx, 3);
 
-    const uint32_t total = compact_flags(ctx, d_flags, n, W.pos, W.kept);   // (waits for the count)
-    if (total) gather_rows(ctx, d_rows, stride, W.kept.p, total, dst(total));
+    const uint32_t total = keep_compact_gather(ctx, W, d_rows, n, stride, dst);
     W.spans.mark(ctx, 4);
     ctx->sync();
     if (summary) {
@@ -261,11 +253,6 @@ uint32_t components_dev(plade_ctx *ctx, ComponentWork &W, const float *d_rows, u
     return total;
 }
 
-ComponentWork &work_of(plade_ctx *ctx) {
-    if (!ctx->component_work) ctx->component_work = component_work_create();
-    return *ctx->component_work;
-}
-
 }  // namespace
 }  // namespace plade
 
@@ -286,19 +273,15 @@ extern "C" int plade_label_components(plade_ctx *ctx, const float *rows, uint32_
                                       float *rows_out, plade_component_summary *summary) {
     return guarded(ctx, [&]() -> int {
         PLADE_REQUIRE(rows, PLADE_EINVAL, "plade_label_components: NULL cloud");
-        plade_component_params p;
-        if (params) p = *params; else plade_component_default_params(&p);
+        const plade_component_params p = params_or_default(params, plade_component_default_params);
         check_params(n, stride, p);
-        ComponentWork &W = work_of(ctx);
+        ComponentWork &W = work_in<ComponentWork>(ctx->component_work);
         float mn[3], mx[3];
         upload_rows(ctx, W.in, rows, n, stride, mn, mx);
-        const uint32_t total = components_dev(ctx, W, W.in.p, n, stride, mn, mx, p,
-                                              [&](uint32_t kept) { return W.out.ensure((size_t)kept * stride + 4); }, summary);
+        const uint32_t total = components_dev(ctx, W, W.in.p, n, stride, mn, mx, p, keep_rows_host(W, stride), summary);
         if (label_out) HIP_TRY(hipMemcpyAsync(label_out, W.label.p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
         if (size_out) HIP_TRY(hipMemcpyAsync(size_out, W.size.p, (size_t)W.components * 4, hipMemcpyDeviceToHost, ctx->stream));
-        if (keep_out) HIP_TRY(hipMemcpyAsync(keep_out, W.keep.p, n, hipMemcpyDeviceToHost, ctx->stream));
-        if (kept_index_out && total) HIP_TRY(hipMemcpyAsync(kept_index_out, W.kept.p, (size_t)total * 4, hipMemcpyDeviceToHost, ctx->stream));
-        if (rows_out && total) HIP_TRY(hipMemcpyAsync(rows_out, W.out.p, (size_t)total * stride * 4, hipMemcpyDeviceToHost, ctx->stream));
+        keep_copy_out(ctx, W, n, total, stride, keep_out, kept_index_out, rows_out);
         ctx->sync();
         return PLADE_OK;
     });
@@ -309,22 +292,17 @@ extern "C" int plade_cloud_filter_components_dev(plade_ctx *ctx, plade_cloud *cl
     return guarded(ctx, [&]() -> int {
         PLADE_REQUIRE(cloud && out, PLADE_EINVAL, "plade_cloud_filter_components_dev: NULL cloud");
         *out = nullptr;
-        plade_component_params p;
-        if (params) p = *params; else plade_component_default_params(&p);
+        const plade_component_params p = params_or_default(params, plade_component_default_params);
         const CloudDev &in = cloud->dev;
         check_params(in.n, 6, p);
-        ComponentWork &W = work_of(ctx);
-        plade_cloud *c = new plade_cloud;
-        try {
-            const uint32_t total = components_dev(ctx, W, in.aos.p, in.n, 6, in.bbmin, in.bbmax, p,
-                                                  [&](uint32_t kept) { cloud_shape(c->dev, kept); return c->dev.aos.p; }, summary);
+        ComponentWork &W = work_in<ComponentWork>(ctx->component_work);
+        resident_result(ctx, out, [&](CloudDev &c) {
+            const uint32_t total = components_dev(ctx, W, in.aos.p, in.n, 6, in.bbmin, in.bbmax, p, keep_rows_cloud(c), summary);
             if (label_out) HIP_TRY(hipMemcpyAsync(label_out, W.label.p, (size_t)in.n * 4, hipMemcpyDeviceToHost, ctx->stream));
-            if (kept_index_out && total) HIP_TRY(hipMemcpyAsync(kept_index_out, W.kept.p, (size_t)total * 4, hipMemcpyDeviceToHost, ctx->stream));
+            keep_copy_out(ctx, W, in.n, total, 6, nullptr, kept_index_out, nullptr);
             ctx->sync();
-            PLADE_REQUIRE(total >= 1, PLADE_EFAIL, "plade_cloud_filter_components_dev: the selection keeps no point (a resident cloud cannot be empty)");
-            cloud_finish_device(ctx, c->dev);   // SoA planes + bounding box of the resident cloud, as plade_cloud_upload
-        } catch (...) { delete c; throw; }
-        *out = c;
+            require_kept(total, "plade_cloud_filter_components_dev: the selection");
+        });
         return PLADE_OK;
     });
 }

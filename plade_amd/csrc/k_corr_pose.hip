@@ -16,6 +16,7 @@
 //            quaternion on lane 0), k_corr_flags under the new T and k_corr_accept -- all queued without a host wait; the state
 //            (CorrState) lives on the device and once it says done every later kernel of the loop returns at once.
 #include "corr_pose.h"
+#include "cloud_tool.h"
 #include "fpfh.h"
 #include "keypoints.h"
 #include "fixed_reduce.h"
@@ -407,15 +408,8 @@ struct CorrPoseWork {
     CorrState h_st;
     EventSpans<4> spans;             // build, score, refine
 };
-CorrPoseWork *corr_pose_work_create() { return new CorrPoseWork; }
-void corr_pose_work_destroy(CorrPoseWork *w) { delete w; }
 
 namespace {
-
-CorrPoseWork &work_of(plade_ctx *ctx) {
-    if (!ctx->corr_pose_work) ctx->corr_pose_work = corr_pose_work_create();
-    return *ctx->corr_pose_work;
-}
 
 void check_params(const plade_corr_pose_params &p) {
     PLADE_REQUIRE(std::isfinite(p.inlier_dist) && p.inlier_dist > 0.0 && std::isfinite(p.inlier_dist * p.inlier_dist) &&
@@ -666,7 +660,7 @@ extern "C" int plade_estimate_pose_corr(plade_ctx *ctx, const float *src, uint32
         PLADE_REQUIRE(src_stride >= 3 && tgt_stride >= 3, PLADE_EINVAL, "plade_estimate_pose_corr: a stride below 3 floats");
         check_params(*params);
         check_list(corr, m, ns, nt, "plade_estimate_pose_corr");
-        CorrPoseWork &W = work_of(ctx);
+        CorrPoseWork &W = work_in<CorrPoseWork>(ctx->corr_pose_work);
         float mn[3], mx[3];
         upload_rows(ctx, W.in_s, src, ns, src_stride, mn, mx);           // (the bounding box checks the coordinates)
         upload_rows(ctx, W.in_t, tgt, nt, tgt_stride, mn, mx);
@@ -684,7 +678,8 @@ extern "C" int plade_estimate_pose_corr_dev(plade_ctx *ctx, plade_cloud *src, pl
         check_params(*params);
         check_list(corr, m, src->dev.n, tgt->dev.n, "plade_estimate_pose_corr_dev");
         const Seams out = {inlier_out, triple_out, status_out, count_out, T_out};
-        return pose_dev(ctx, work_of(ctx), src->dev.aos.p, 6, tgt->dev.aos.p, 6, corr, (uint32_t)m, *params, T16, out, result);
+        return pose_dev(ctx, work_in<CorrPoseWork>(ctx->corr_pose_work), src->dev.aos.p, 6, tgt->dev.aos.p, 6, corr, (uint32_t)m, *params,
+                        T16, out, result);
     });
 }
 
@@ -698,7 +693,7 @@ extern "C" int plade_corr_pose_moments(plade_ctx *ctx, const float *src, uint32_
                       PLADE_EINVAL, "plade_corr_pose_moments: inlier_dist must be finite and > 0");
         for (int k = 0; k < 12; ++k) PLADE_REQUIRE(std::isfinite(T12[k]), PLADE_EINVAL, "plade_corr_pose_moments: T12 is not finite");
         check_list(corr, m, ns, nt, "plade_corr_pose_moments");
-        CorrPoseWork &W = work_of(ctx);
+        CorrPoseWork &W = work_in<CorrPoseWork>(ctx->corr_pose_work);
         float mn[3], mx[3];
         upload_rows(ctx, W.in_s, src, ns, src_stride, mn, mx);
         upload_rows(ctx, W.in_t, tgt, nt, tgt_stride, mn, mx);
@@ -736,9 +731,8 @@ extern "C" int plade_register_features(plade_ctx *ctx, const float *tgt_pos_nrm,
         PLADE_REQUIRE(tgt_pos_nrm && src_pos_nrm && fpfh && pose && T16 && src_summary && tgt_summary && result, PLADE_EINVAL,
                       "plade_register_features: NULL cloud, params, T16, summary or result");
         PLADE_REQUIRE(n_t >= 1 && n_s >= 1, PLADE_EINVAL, "plade_register_features: an empty cloud (n = 0)");
-        plade_feature_match_params mp;
-        if (match) mp = *match; else plade_feature_match_default_params(&mp);
-        CorrPoseWork &W = work_of(ctx);
+        const plade_feature_match_params mp = params_or_default(match, plade_feature_match_default_params);
+        CorrPoseWork &W = work_in<CorrPoseWork>(ctx->corr_pose_work);
         float tmn[3], tmx[3], smn[3], smx[3];
         upload_rows(ctx, W.in_t, tgt_pos_nrm, n_t, 6, tmn, tmx);         // (the bounding box checks the coordinates)
         upload_rows(ctx, W.in_s, src_pos_nrm, n_s, 6, smn, smx);
@@ -754,11 +748,10 @@ extern "C" int plade_register_features_dev(plade_ctx *ctx, plade_cloud *tgt, pla
     return guarded(ctx, [&]() -> int {
         PLADE_REQUIRE(tgt && src && fpfh && pose && T16 && src_summary && tgt_summary && result, PLADE_EINVAL,
                       "plade_register_features_dev: NULL cloud, params, T16, summary or result");
-        plade_feature_match_params mp;
-        if (match) mp = *match; else plade_feature_match_default_params(&mp);
+        const plade_feature_match_params mp = params_or_default(match, plade_feature_match_default_params);
         const CloudDev &t = tgt->dev, &s = src->dev;
-        return register_dev(ctx, work_of(ctx), t.aos.p, t.n, t.bbmin, t.bbmax, s.aos.p, s.n, s.bbmin, s.bbmax, *fpfh, mp, *pose, T16,
-                            src_summary, tgt_summary, result, corr_out, cap, n_corr);
+        return register_dev(ctx, work_in<CorrPoseWork>(ctx->corr_pose_work), t.aos.p, t.n, t.bbmin, t.bbmax, s.aos.p, s.n, s.bbmin, s.bbmax,
+                            *fpfh, mp, *pose, T16, src_summary, tgt_summary, result, corr_out, cap, n_corr);
     });
 }
 
@@ -771,9 +764,8 @@ extern "C" int plade_register_keypoints(plade_ctx *ctx, const float *tgt_pos_nrm
         PLADE_REQUIRE(tgt_pos_nrm && src_pos_nrm && iss && fpfh && pose && T16 && iss_summary && src_summary && tgt_summary && result,
                       PLADE_EINVAL, "plade_register_keypoints: NULL cloud, params, T16, summary or result");
         PLADE_REQUIRE(n_t >= 1 && n_s >= 1, PLADE_EINVAL, "plade_register_keypoints: an empty cloud (n = 0)");
-        plade_feature_match_params mp;
-        if (match) mp = *match; else plade_feature_match_default_params(&mp);
-        CorrPoseWork &W = work_of(ctx);
+        const plade_feature_match_params mp = params_or_default(match, plade_feature_match_default_params);
+        CorrPoseWork &W = work_in<CorrPoseWork>(ctx->corr_pose_work);
         float tmn[3], tmx[3], smn[3], smx[3];
         upload_rows(ctx, W.in_t, tgt_pos_nrm, n_t, 6, tmn, tmx);         // (the bounding box checks the coordinates)
         upload_rows(ctx, W.in_s, src_pos_nrm, n_s, 6, smn, smx);
@@ -790,10 +782,10 @@ extern "C" int plade_register_keypoints_dev(plade_ctx *ctx, plade_cloud *tgt, pl
     return guarded(ctx, [&]() -> int {
         PLADE_REQUIRE(tgt && src && iss && fpfh && pose && T16 && iss_summary && src_summary && tgt_summary && result, PLADE_EINVAL,
                       "plade_register_keypoints_dev: NULL cloud, params, T16, summary or result");
-        plade_feature_match_params mp;
-        if (match) mp = *match; else plade_feature_match_default_params(&mp);
+        const plade_feature_match_params mp = params_or_default(match, plade_feature_match_default_params);
         const CloudDev &t = tgt->dev, &s = src->dev;
-        return register_keypoints_dev(ctx, work_of(ctx), t.aos.p, t.n, t.bbmin, t.bbmax, s.aos.p, s.n, s.bbmin, s.bbmax, *iss, *fpfh, mp,
-                                      *pose, T16, iss_summary, src_summary, tgt_summary, result, corr_out, cap, n_corr);
+        return register_keypoints_dev(ctx, work_in<CorrPoseWork>(ctx->corr_pose_work), t.aos.p, t.n, t.bbmin, t.bbmax, s.aos.p, s.n,
+                                      s.bbmin, s.bbmax, *iss, *fpfh, mp, *pose, T16, iss_summary, src_summary, tgt_summary, result,
+                                      corr_out, cap, n_corr);
     });
 }

@@ -207,8 +207,6 @@ struct DistWork {
     double h_out[SUM_TERMS];
     uint32_t h_count = 0;
 };
-DistWork *dist_work_create() { return new DistWork; }
-void dist_work_destroy(DistWork *w) { delete w; }
 
 namespace {
 
@@ -306,11 +304,6 @@ void distances_dev(plade_ctx *ctx, DistWork &W, const float *d_tgt, uint32_t n_t
     grid_stats(ctx, "distances", G);
 }
 
-DistWork &work_of(plade_ctx *ctx) {
-    if (!ctx->dist_work) ctx->dist_work = dist_work_create();
-    return *ctx->dist_work;
-}
-
 }  // namespace
 }  // namespace plade
 
@@ -326,7 +319,7 @@ extern "C" int plade_cloud_distances(plade_ctx *ctx, const float *tgt_pos_nrm, u
         PLADE_REQUIRE(stride >= 3, PLADE_EINVAL, "plade_cloud_distances: stride must be >= 3 floats");
         const float *T = T16 ? T16 : kIdentity;
         check_args(T, max_dist);
-        DistWork &W = work_of(ctx);
+        DistWork &W = work_in<DistWork>(ctx->dist_work);
         float tmn[3], tmx[3], smn[3], smx[3];
         upload_rows(ctx, W.in_t, tgt_pos_nrm, n_t, 6, tmn, tmx);
         upload_rows(ctx, W.in_s, src_xyz, n_s, stride, smn, smx);
@@ -342,7 +335,7 @@ extern "C" int plade_cloud_distances_dev(plade_ctx *ctx, plade_cloud *tgt, plade
         PLADE_REQUIRE(tgt->dev.n >= 1 && src->dev.n >= 1, PLADE_EINVAL, "plade_cloud_distances_dev: empty cloud (n = 0)");
         const float *T = T16 ? T16 : kIdentity;
         check_args(T, max_dist);
-        DistWork &W = work_of(ctx);
+        DistWork &W = work_in<DistWork>(ctx->dist_work);
         const CloudDev &t = tgt->dev, &s = src->dev;
         distances_dev(ctx, W, t.aos.p, t.n, t.bbmin, t.bbmax, s.aos.p, s.n, 6, T, max_dist, idx_out, d2_out, plane_out, summary);
         return PLADE_OK;

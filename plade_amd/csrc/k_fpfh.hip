@@ -22,6 +22,7 @@
 //            k_feat_merge takes the two smallest over the chunks (a minimum: order-independent, exact); k_feat_keep applies the
 //            mutual and ratio tests, the scan of prims.h places the kept pairs, k_feat_compact writes them.
 #include "fpfh.h"
+#include "cloud_tool.h"
 #include "fixed_reduce.h"
 #include "grid_walk.h"
 #include "prims.h"
@@ -332,8 +333,6 @@ struct FpfhWork {
     DBuf<uint32_t> flags, offs;
     EventSpans<6> spans;             // 0..3: grid, spfh, weight; 4..5: the match
 };
-FpfhWork *fpfh_work_create() { return new FpfhWork; }
-void fpfh_work_destroy(FpfhWork *w) { delete w; }
 
 namespace {
 
@@ -346,8 +345,7 @@ struct Outputs {
 
 void check_params(uint32_t n, const plade_fpfh_params &p) {
     PLADE_REQUIRE(n >= 1, PLADE_EINVAL, "cloud_fpfh: the cloud is empty (n = 0)");
-    const float r = (float)p.radius;
-    PLADE_REQUIRE(std::isfinite(p.radius) && std::isfinite(r) && r > 0.f && std::isfinite(r * r) && r * r >= FLT_MIN, PLADE_EINVAL,
+    PLADE_REQUIRE(radius_ok(p.radius, true), PLADE_EINVAL,
                   "cloud_fpfh: radius must be finite and > 0, and its fp32 square finite and not below FLT_MIN");
     PLADE_REQUIRE(p.min_pairs >= 1, PLADE_EINVAL, "cloud_fpfh: min_pairs must be >= 1");
 }
@@ -469,18 +467,13 @@ void check_match(const plade_feature_match_params &p, uint32_t ns, uint32_t nt) 
                   "match_features: max_ratio must be finite and >= 0");
 }
 
-FpfhWork &work_of(plade_ctx *ctx) {
-    if (!ctx->fpfh_work) ctx->fpfh_work = fpfh_work_create();
-    return *ctx->fpfh_work;
-}
-
 }  // namespace
 
 // ---- the two steps as plade_register_features chains them (k_corr_pose.hip): nothing leaves the device but the summaries -------
 void fpfh_table_dev(plade_ctx *ctx, const float *d_rows, uint32_t n, const float bbmin[3], const float bbmax[3],
                     const plade_fpfh_params &p, plade_features &out, plade_fpfh_summary *summary) {
     check_params(n, p);
-    FpfhWork &W = work_of(ctx);
+    FpfhWork &W = work_in<FpfhWork>(ctx->fpfh_work);
     const Outputs none = {nullptr, nullptr, nullptr, nullptr, nullptr};
     fpfh_dev(ctx, W, d_rows, n, 6, bbmin, bbmax, p, none, summary);
     out.n = n;
@@ -490,7 +483,7 @@ void fpfh_table_dev(plade_ctx *ctx, const float *d_rows, uint32_t n, const float
 const int32_t *feature_corr_dev(plade_ctx *ctx, const plade_features &src, const plade_features &tgt, const plade_feature_match_params &p,
                                 uint64_t *n_corr) {
     check_match(p, src.n, tgt.n);
-    FpfhWork &W = work_of(ctx);
+    FpfhWork &W = work_in<FpfhWork>(ctx->fpfh_work);
     match_dev(ctx, W, src.desc.p, src.n, tgt.desc.p, tgt.n, p, nullptr, nullptr, nullptr, nullptr, 0, n_corr);
     return W.corr.p;
 }
@@ -520,7 +513,7 @@ extern "C" int plade_cloud_fpfh(plade_ctx *ctx, const float *pos_nrm, uint32_t n
     return guarded(ctx, [&]() -> int {
         PLADE_REQUIRE(pos_nrm && params && summary, PLADE_EINVAL, "plade_cloud_fpfh: NULL cloud, params or summary");
         check_params(n, *params);
-        FpfhWork &W = work_of(ctx);
+        FpfhWork &W = work_in<FpfhWork>(ctx->fpfh_work);
         float mn[3], mx[3];
         upload_rows(ctx, W.in, pos_nrm, n, 6, mn, mx);                   // (the bounding box checks the coordinates)
         const Outputs out = {desc_out, described_out, pairs_out, spfh_out, raw_out};
@@ -537,7 +530,7 @@ extern "C" int plade_cloud_fpfh_dev(plade_ctx *ctx, plade_cloud *cloud, const pl
         PLADE_REQUIRE(cloud && params && summary, PLADE_EINVAL, "plade_cloud_fpfh_dev: NULL cloud, params or summary");
         const CloudDev &c = cloud->dev;
         check_params(c.n, *params);
-        FpfhWork &W = work_of(ctx);
+        FpfhWork &W = work_in<FpfhWork>(ctx->fpfh_work);
         const Outputs out = {desc_out, described_out, pairs_out, spfh_out, raw_out};
         fpfh_dev(ctx, W, c.aos.p, c.n, 6, c.bbmin, c.bbmax, *params, out, summary);
         if (features_out) {
@@ -561,10 +554,9 @@ extern "C" int plade_match_features(plade_ctx *ctx, const float *src, uint32_t n
                                     int32_t *corr_out, uint64_t cap, uint64_t *n_corr) {
     return guarded(ctx, [&]() -> int {
         PLADE_REQUIRE(src && tgt && n_corr, PLADE_EINVAL, "plade_match_features: NULL table or n_corr");
-        plade_feature_match_params p;
-        if (params) p = *params; else plade_feature_match_default_params(&p);
+        const plade_feature_match_params p = params_or_default(params, plade_feature_match_default_params);
         check_match(p, ns, nt);
-        FpfhWork &W = work_of(ctx);
+        FpfhWork &W = work_in<FpfhWork>(ctx->fpfh_work);
         float *d_s = W.m_src.ensure((size_t)ns * FPFH_DIM + 4), *d_t = W.m_tgt.ensure((size_t)nt * FPFH_DIM + 4);
         HIP_TRY(hipMemcpyAsync(d_s, src, (size_t)ns * FPFH_DIM * 4, hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(hipMemcpyAsync(d_t, tgt, (size_t)nt * FPFH_DIM * 4, hipMemcpyHostToDevice, ctx->stream));
@@ -577,9 +569,9 @@ extern "C" int plade_match_features_dev(plade_ctx *ctx, plade_features *src, pla
                                         uint64_t *n_corr) {
     return guarded(ctx, [&]() -> int {
         PLADE_REQUIRE(src && tgt && n_corr, PLADE_EINVAL, "plade_match_features_dev: NULL table or n_corr");
-        plade_feature_match_params p;
-        if (params) p = *params; else plade_feature_match_default_params(&p);
+        const plade_feature_match_params p = params_or_default(params, plade_feature_match_default_params);
         check_match(p, src->n, tgt->n);
-        return match_dev(ctx, work_of(ctx), src->desc.p, src->n, tgt->desc.p, tgt->n, p, nn_out, d2_out, back_out, corr_out, cap, n_corr);
+        return match_dev(ctx, work_in<FpfhWork>(ctx->fpfh_work), src->desc.p, src->n, tgt->desc.p, tgt->n, p, nn_out, d2_out, back_out,
+                         corr_out, cap, n_corr);
     });
 }

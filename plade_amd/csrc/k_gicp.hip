@@ -28,7 +28,7 @@ struct GicpModel {
     static constexpr uint32_t STRIDE = 6;                         // the sample: x y z and the normal m
     static constexpr const char *prefix = "gicp", *who = "refine_gicp", *seam = "plade_gicp_linearize",
                                 *seam_grid = "plade_gicp_linearize", *seam_empty = "empty cloud";
-    static constexpr RefineWork *plade_ctx::*slot = &plade_ctx::gicp_work;
+    static constexpr WorkSlot plade_ctx::*slot = &plade_ctx::gicp_work;
     using params = plade_gicp_params;
     using result = plade_gicp_result;
     struct Args {

@@ -26,7 +26,7 @@ struct IcpModel {
     static constexpr uint32_t STRIDE = 3;                         // the sample: x y z
     static constexpr const char *prefix = "icp", *who = "refine_icp", *seam = "plade_icp_linearize", *seam_grid = "refine_icp",
                                 *seam_empty = "empty cloud or stride < 3";
-    static constexpr RefineWork *plade_ctx::*slot = &plade_ctx::icp_work;
+    static constexpr WorkSlot plade_ctx::*slot = &plade_ctx::icp_work;
     using params = plade_icp_params;
     using result = plade_icp_result;
     struct Args {
@@ -78,8 +78,6 @@ struct IcpModel {
 };
 
 }  // namespace
-
-void refine_work_destroy(RefineWork *w) { delete w; }
 
 }  // namespace plade
 

@@ -186,8 +186,6 @@ struct IssWork {
     uint32_t h_total = 0;
     EventSpans<4> spans;             // grid, scatter, nms (+ list and summary)
 };
-IssWork *iss_work_create() { return new IssWork; }
-void iss_work_destroy(IssWork *w) { delete w; }
 
 namespace {
 
@@ -201,28 +199,18 @@ struct Outputs {
     double *scatter;
 };
 
-bool radius_ok(double radius) {
-    const float r = (float)radius;
-    return std::isfinite(radius) && std::isfinite(r) && r > 0.f && std::isfinite(r * r) && r * r >= FLT_MIN;
-}
-
 void check_params(uint32_t n, uint32_t stride, const plade_iss_params &p) {
     PLADE_REQUIRE(n >= 1, PLADE_EINVAL, "keypoints_iss: the cloud is empty (n = 0)");
     PLADE_REQUIRE(stride >= 3, PLADE_EINVAL, "keypoints_iss: stride must be >= 3 floats");
     // r2 a normal fp32 number, as smooth_cloud: at 0 no point would be its own neighbour
-    PLADE_REQUIRE(radius_ok(p.salient_radius), PLADE_EINVAL,
+    PLADE_REQUIRE(radius_ok(p.salient_radius, true), PLADE_EINVAL,
                   "keypoints_iss: salient_radius must be finite and > 0, and its fp32 square finite and not below FLT_MIN");
-    PLADE_REQUIRE(p.non_max_radius == 0.0 || radius_ok(p.non_max_radius), PLADE_EINVAL,
+    PLADE_REQUIRE(p.non_max_radius == 0.0 || radius_ok(p.non_max_radius, true), PLADE_EINVAL,
                   "keypoints_iss: non_max_radius must be 0 (= salient_radius) or finite and > 0, its fp32 square finite and not below FLT_MIN");
     PLADE_REQUIRE(std::isfinite(p.gamma21) && p.gamma21 > 0.0 && p.gamma21 <= 1.0 && std::isfinite(p.gamma32) && p.gamma32 > 0.0 &&
                       p.gamma32 <= 1.0,
                   PLADE_EINVAL, "keypoints_iss: gamma21 and gamma32 must be finite and in (0, 1]");
     PLADE_REQUIRE(p.min_neighbours >= 1, PLADE_EINVAL, "keypoints_iss: min_neighbours must be >= 1");
-}
-
-IssWork &work_of(plade_ctx *ctx) {
-    if (!ctx->iss_work) ctx->iss_work = iss_work_create();
-    return *ctx->iss_work;
 }
 
 // The detector on a device cloud of `stride` floats per point with a known bounding box: leaves every per-point array and the list in
@@ -307,7 +295,7 @@ int iss_dev(plade_ctx *ctx, IssWork &W, const float *d_rows, uint32_t n, uint32_
 const uint32_t *iss_list_dev(plade_ctx *ctx, const float *d_rows, uint32_t n, uint32_t stride, const float bbmin[3], const float bbmax[3],
                              const plade_iss_params &p, plade_iss_summary *summary, uint32_t *n_keypoints) {
     check_params(n, stride, p);
-    IssWork &W = work_of(ctx);
+    IssWork &W = work_in<IssWork>(ctx->iss_work);
     const Outputs none = {nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     iss_dev(ctx, W, d_rows, n, stride, bbmin, bbmax, p, none, summary);
     *n_keypoints = W.h_total;
@@ -323,7 +311,7 @@ void features_select_dev(plade_ctx *ctx, const plade_features &in, const uint32_
 }
 
 const int32_t *corr_map_source_dev(plade_ctx *ctx, const int32_t *d_corr, uint64_t m, const uint32_t *d_index) {
-    IssWork &W = work_of(ctx);
+    IssWork &W = work_in<IssWork>(ctx->iss_work);
     int32_t *d_out = W.corr.ensure((size_t)m * 2 + 2);
     if (m) {
         hipLaunchKernelGGL(k_corr_map, dim3(cdiv(m, 256)), dim3(256), 0, ctx->stream, d_corr, (uint32_t)m, d_index, d_out);
@@ -354,7 +342,7 @@ extern "C" int plade_cloud_keypoints_iss(plade_ctx *ctx, const float *rows, uint
     return guarded(ctx, [&]() -> int {
         PLADE_REQUIRE(rows && params && summary, PLADE_EINVAL, "plade_cloud_keypoints_iss: NULL cloud, params or summary");
         check_params(n, stride, *params);
-        IssWork &W = work_of(ctx);
+        IssWork &W = work_in<IssWork>(ctx->iss_work);
         float mn[3], mx[3];
         upload_rows(ctx, W.in, rows, n, stride, mn, mx);                 // (the bounding box checks the coordinates)
         const Outputs out = {keypoint_out, index_out, cap, n_keypoints, saliency_out, eigenvalues_out, count_out, nms_count_out, scatter_out};
@@ -371,7 +359,7 @@ extern "C" int plade_cloud_keypoints_iss_dev(plade_ctx *ctx, plade_cloud *cloud,
         const CloudDev &c = cloud->dev;
         check_params(c.n, 6, *params);
         const Outputs out = {keypoint_out, index_out, cap, n_keypoints, saliency_out, eigenvalues_out, count_out, nms_count_out, scatter_out};
-        return iss_dev(ctx, work_of(ctx), c.aos.p, c.n, 6, c.bbmin, c.bbmax, *params, out, summary);
+        return iss_dev(ctx, work_in<IssWork>(ctx->iss_work), c.aos.p, c.n, 6, c.bbmin, c.bbmax, *params, out, summary);
     });
 }
 
@@ -383,7 +371,7 @@ extern "C" int plade_features_select(plade_ctx *ctx, plade_features *features, c
         for (uint32_t o = 0; o < k; ++o)
             PLADE_REQUIRE(index[o] < features->n, PLADE_EINVAL,
                           "plade_features_select: index " + std::to_string(o) + " names a row that does not exist");
-        IssWork &W = work_of(ctx);
+        IssWork &W = work_in<IssWork>(ctx->iss_work);
         uint32_t *d_index = W.sel_index.ensure(k);
         HIP_TRY(hipMemcpyAsync(d_index, index, (size_t)k * 4, hipMemcpyHostToDevice, ctx->stream));
         plade_features *f = new plade_features;

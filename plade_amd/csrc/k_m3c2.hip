@@ -224,8 +224,6 @@ struct M3c2Work {
     double h_d[3] = {0.0, 0.0, 0.0};
     uint32_t h_u[3] = {0, 0, 0};
 };
-M3c2Work *m3c2_work_create() { return new M3c2Work; }
-void m3c2_work_destroy(M3c2Work *w) { delete w; }
 
 namespace {
 
@@ -316,11 +314,6 @@ void m3c2_dev(plade_ctx *ctx, M3c2Work &W, const float *d_core, uint32_t m, uint
     grid_stats(ctx, "m3c2_b", W.grid_b);
 }
 
-M3c2Work &work_of(plade_ctx *ctx) {
-    if (!ctx->m3c2_work) ctx->m3c2_work = m3c2_work_create();
-    return *ctx->m3c2_work;
-}
-
 }  // namespace
 }  // namespace plade
 
@@ -347,7 +340,7 @@ extern "C" int plade_cloud_m3c2(plade_ctx *ctx, const float *core_pos_nrm, uint3
         PLADE_REQUIRE(stride_a >= 3 && stride_b >= 3, PLADE_EINVAL, "plade_cloud_m3c2: stride must be >= 3 floats");
         const float *T = T16 ? T16 : kIdentity;
         check_params(T, *params);
-        M3c2Work &W = work_of(ctx);
+        M3c2Work &W = work_in<M3c2Work>(ctx->m3c2_work);
         float cmn[3], cmx[3], amn[3], amx[3], bmn[3], bmx[3];
         upload_rows(ctx, W.in_core, core_pos_nrm, m, 6, cmn, cmx);       // (the bounding boxes check the coordinates)
         upload_rows(ctx, W.in_a, ref_rows, n_a, stride_a, amn, amx);
@@ -367,7 +360,7 @@ extern "C" int plade_cloud_m3c2_dev(plade_ctx *ctx, plade_cloud *core, plade_clo
                       "plade_cloud_m3c2_dev: empty cloud (m = 0 or n = 0)");
         const float *T = T16 ? T16 : kIdentity;
         check_params(T, *params);
-        M3c2Work &W = work_of(ctx);
+        M3c2Work &W = work_in<M3c2Work>(ctx->m3c2_work);
         const CloudDev &c = core->dev, &a = ref->dev, &b = cmp->dev;
         const Outputs out = {distance_out, lod_out, significant_out, count_out, sigma_out, moments_out};
         m3c2_dev(ctx, W, c.aos.p, c.n, 6, a.aos.p, a.n, 6, a.bbmin, a.bbmax, b.aos.p, b.n, 6, T, *params, out, summary);

@@ -10,6 +10,7 @@
 // (d) k_merge_fuse       one lane per voxel adds its run in that order in fp64 from LDS-staged, coalesced chunks
 // No floating-point atomics anywhere: the bits do not depend on the launch shape or the run.
 #include "merge.h"
+#include "cloud_tool.h"
 #include "prims.h"
 #include "voxel.h"
 
@@ -251,15 +252,8 @@ struct MergeWork {
     EventSpans<5> spans;             // transform; with a leaf: sort, runs, fuse
     uint32_t h_count[4] = {0, 0, 0, 0};
 };
-MergeWork *merge_work_create() { return new MergeWork; }
-void merge_work_destroy(MergeWork *w) { delete w; }
 
 namespace {
-
-MergeWork &work_of(plade_ctx *ctx) {
-    if (!ctx->merge_work) ctx->merge_work = merge_work_create();
-    return *ctx->merge_work;
-}
 
 const float kIdentity[16] = {1.f, 0.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 0.f, 1.f};
 
@@ -395,7 +389,7 @@ uint32_t merge_fuse_one(plade_ctx *ctx, const float *d_rows, uint32_t n, float l
         // (a leaf that rounds to 0 in fp32 would select the concatenation: there would be no fused rows to hand out)
         PLADE_REQUIRE(leaf > 0.f, PLADE_EINVAL, "merge_clouds: the leaf is 0 in fp32");
         const uint32_t total = check_args(1, clouds, ns, nullptr, leaf);
-        MergeWork &W = work_of(ctx);
+        MergeWork &W = work_in<MergeWork>(ctx->merge_work);
         const uint32_t m = merge_dev(ctx, W, 1, rows, ns, nullptr, leaf, total, W.cat.ensure(6 * (size_t)total + 8), nullptr);
         *d_out = W.out_rows.p;
         return m;
@@ -418,7 +412,7 @@ extern "C" int plade_merge_clouds(plade_ctx *ctx, uint32_t k, const float *const
         const float *Tc[MERGE_MAX_CLOUDS] = {};
         for (uint32_t c = 0; c < k && c < (uint32_t)MERGE_MAX_CLOUDS; ++c) Tc[c] = T ? T + 16 * (size_t)c : nullptr;
         const uint32_t total = check_args(k, reinterpret_cast<const void *const *>(clouds), n, Tc, leaf);
-        MergeWork &W = work_of(ctx);
+        MergeWork &W = work_in<MergeWork>(ctx->merge_work);
         W.in.ensure(6 * (size_t)total + 8);
         W.cat.ensure(6 * (size_t)total + 8);
         const float *d_rows[MERGE_MAX_CLOUDS];
@@ -456,24 +450,21 @@ extern "C" int plade_merge_clouds_dev(plade_ctx *ctx, uint32_t k, plade_cloud *c
             if (clouds && clouds[c]) { n[c] = clouds[c]->dev.n; d_rows[c] = clouds[c]->dev.aos.p; }
         }
         const uint32_t total = check_args(k, reinterpret_cast<const void *const *>(clouds), n, Tc, leaf);
-        MergeWork &W = work_of(ctx);
-        plade_cloud *r = new plade_cloud;
-        try {
+        MergeWork &W = work_in<MergeWork>(ctx->merge_work);
+        resident_result(ctx, out, [&](CloudDev &r) {
             const bool fuse = leaf > 0.f;
             float *d_cat;
             if (fuse) d_cat = W.cat.ensure(6 * (size_t)total + 8);
-            else { cloud_shape(r->dev, total); d_cat = r->dev.aos.p; }
+            else { cloud_shape(r, total); d_cat = r.aos.p; }
             const uint32_t m = merge_dev(ctx, W, k, d_rows, n, Tc, leaf, total, d_cat, summary);
             if (fuse) {
-                cloud_shape(r->dev, m);
-                ctx->copy_dd_async(r->dev.aos.p, W.out_rows.p, (size_t)m * 24);
+                cloud_shape(r, m);
+                ctx->copy_dd_async(r.aos.p, W.out_rows.p, (size_t)m * 24);
                 if (out_count) HIP_TRY(hipMemcpyAsync(out_count, W.out_count.p, (size_t)m * 4, hipMemcpyDeviceToHost, ctx->stream));
                 if (out_mask) HIP_TRY(hipMemcpyAsync(out_mask, W.out_mask.p, (size_t)m * 4, hipMemcpyDeviceToHost, ctx->stream));
                 ctx->sync();
             } else fill_unfused(k, n, out_count, out_mask);
-            cloud_finish_device(ctx, r->dev);   // SoA planes + bounding box of the resident cloud, as plade_cloud_upload
-        } catch (...) { delete r; throw; }
-        *out = r;
+        });
         return PLADE_OK;
     });
 }

@@ -18,6 +18,7 @@
 //           of the 3 x 3 symmetric covariance, the eigenvector of the smallest from the cross products of the rows of C - l0 I;
 //           orientation toward the viewpoint.
 #include "normals.h"
+#include "cloud_tool.h"
 #include "grid_walk.h"
 #include "pca_eig.h"
 #include "voxel.h"
@@ -33,8 +34,6 @@ struct NormalsWork {
     int builds = 0;
     uint32_t h_count = 0;
 };
-NormalsWork *normals_work_create() { return new NormalsWork; }
-void normals_work_destroy(NormalsWork *w) { delete w; }
 
 namespace {
 
@@ -234,8 +233,7 @@ extern "C" int plade_estimate_normals(plade_ctx *ctx, const float *xyz, uint32_t
         PLADE_REQUIRE(xyz && pos_nrm_out, PLADE_EINVAL, "plade_estimate_normals: bad argument");
         const float *view = viewpoint ? viewpoint : kOrigin;
         normals_check_args(n, stride, k, view);
-        if (!ctx->normals_work) ctx->normals_work = normals_work_create();
-        NormalsWork &W = *ctx->normals_work;
+        NormalsWork &W = work_in<NormalsWork>(ctx->normals_work);
         float mn[3], mx[3];
         upload_rows(ctx, W.in, xyz, n, stride, mn, mx);
         W.out.ensure((size_t)n * 6);
@@ -259,19 +257,15 @@ extern "C" int plade_cloud_upload_xyz(plade_ctx *ctx, const float *xyz, uint32_t
         *out = nullptr;
         const float *view = viewpoint ? viewpoint : kOrigin;
         normals_check_args(n, stride, k, view);
-        if (!ctx->normals_work) ctx->normals_work = normals_work_create();
-        NormalsWork &W = *ctx->normals_work;
+        NormalsWork &W = work_in<NormalsWork>(ctx->normals_work);
         float mn[3], mx[3];
         upload_rows(ctx, W.in, xyz, n, stride, mn, mx);
-        plade_cloud *c = new plade_cloud;
-        try {
-            cloud_shape(c->dev, n);
-            estimate_normals_dev(ctx, W, W.in.p, n, stride, mn, mx, k, view, c->dev.aos.p, nullptr, nullptr);
+        resident_result(ctx, out, [&](CloudDev &c) {
+            cloud_shape(c, n);
+            estimate_normals_dev(ctx, W, W.in.p, n, stride, mn, mx, k, view, c.aos.p, nullptr, nullptr);
             ctx->sync();
             normals_stats(ctx, W);
-            cloud_finish_device(ctx, c->dev);   // SoA planes + bounding box of the resident cloud, as plade_cloud_upload
-        } catch (...) { delete c; throw; }
-        *out = c;
+        });
         return PLADE_OK;
     });
 }

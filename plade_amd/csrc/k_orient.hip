@@ -38,12 +38,11 @@
 //            the rule of k_components.hip: the exclusive position of a component's smallest index), k_or_scatter (rows, flip and
 //            label in the original order; the flipped and the unoriented by ballots).
 #include "orient.h"
+#include "cloud_tool.h"
 #include "grid_walk.h"
 #include "prims.h"
 #include "stages.h"
 #include "voxel.h"
-#include <cfloat>
-#include <functional>
 
 namespace plade {
 
@@ -367,16 +366,13 @@ struct OrientWork {
     DBuf<float> in, out;             // the host-pointer entry point's device copies (grow-only)
     EventSpans<4> spans;             // grid, rounds, finish
 };
-OrientWork *orient_work_create() { return new OrientWork; }
-void orient_work_destroy(OrientWork *w) { delete w; }
 
 namespace {
 
 void check_params(uint32_t n, const plade_orient_params &p) {
     PLADE_REQUIRE(n >= 1, PLADE_EINVAL, "orient_normals: the cloud is empty (n = 0)");
     PLADE_REQUIRE(n < 0x80000000u, PLADE_EINVAL, "orient_normals: more than 2^31 - 1 points");   // (root << 1 | parity in 32 bits)
-    const float r = (float)p.radius;
-    PLADE_REQUIRE(std::isfinite(p.radius) && std::isfinite(r) && r > 0.f && std::isfinite(r * r) && r * r >= FLT_MIN, PLADE_EINVAL,
+    PLADE_REQUIRE(radius_ok(p.radius, true), PLADE_EINVAL,
                   "orient_normals: radius must be finite and > 0, its fp32 square finite and not below FLT_MIN");
     PLADE_REQUIRE(p.mode == PLADE_ORIENT_VOTE || p.mode == PLADE_ORIENT_EXTREME, PLADE_EINVAL,
                   "orient_normals: mode must be 0 (vote) or 1 (extreme point)");
@@ -494,11 +490,6 @@ void orient_dev(plade_ctx *ctx, OrientWork &W, const float *d_rows, uint32_t n, 
     grid_stats(ctx, "orient", W.grid);
 }
 
-OrientWork &work_of(plade_ctx *ctx) {
-    if (!ctx->orient_work) ctx->orient_work = orient_work_create();
-    return *ctx->orient_work;
-}
-
 }  // namespace
 }  // namespace plade
 
@@ -518,10 +509,9 @@ extern "C" int plade_orient_normals(plade_ctx *ctx, const float *pos_nrm, uint32
                                     uint8_t *flip_out, int32_t *label_out, plade_orient_summary *summary) {
     return guarded(ctx, [&]() -> int {
         PLADE_REQUIRE(pos_nrm, PLADE_EINVAL, "plade_orient_normals: NULL cloud");
-        plade_orient_params p;
-        if (params) p = *params; else plade_orient_default_params(&p);
+        const plade_orient_params p = params_or_default(params, plade_orient_default_params);
         check_params(n, p);
-        OrientWork &W = work_of(ctx);
+        OrientWork &W = work_in<OrientWork>(ctx->orient_work);
         float mn[3], mx[3];
         upload_rows(ctx, W.in, pos_nrm, n, 6, mn, mx);
         orient_dev(ctx, W, W.in.p, n, mn, mx, p, W.out.ensure((size_t)n * 6 + 4), summary);
@@ -538,21 +528,17 @@ extern "C" int plade_cloud_orient_normals_dev(plade_ctx *ctx, plade_cloud *cloud
     return guarded(ctx, [&]() -> int {
         PLADE_REQUIRE(cloud && out, PLADE_EINVAL, "plade_cloud_orient_normals_dev: NULL cloud");
         *out = nullptr;
-        plade_orient_params p;
-        if (params) p = *params; else plade_orient_default_params(&p);
+        const plade_orient_params p = params_or_default(params, plade_orient_default_params);
         const CloudDev &in = cloud->dev;
         check_params(in.n, p);
-        OrientWork &W = work_of(ctx);
-        plade_cloud *c = new plade_cloud;
-        try {
-            cloud_shape(c->dev, in.n);
-            orient_dev(ctx, W, in.aos.p, in.n, in.bbmin, in.bbmax, p, c->dev.aos.p, summary);
+        OrientWork &W = work_in<OrientWork>(ctx->orient_work);
+        resident_result(ctx, out, [&](CloudDev &c) {
+            cloud_shape(c, in.n);
+            orient_dev(ctx, W, in.aos.p, in.n, in.bbmin, in.bbmax, p, c.aos.p, summary);
             if (flip_out) HIP_TRY(hipMemcpyAsync(flip_out, W.flip.p, in.n, hipMemcpyDeviceToHost, ctx->stream));
             if (label_out) HIP_TRY(hipMemcpyAsync(label_out, W.label.p, (size_t)in.n * 4, hipMemcpyDeviceToHost, ctx->stream));
             ctx->sync();
-            cloud_finish_device(ctx, c->dev);   // SoA planes + bounding box of the resident cloud, as plade_cloud_upload
-        } catch (...) { delete c; throw; }
-        *out = c;
+        });
         return PLADE_OK;
     });
 }

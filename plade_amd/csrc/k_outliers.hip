@@ -18,12 +18,10 @@
 //   keep     k_outliers_flags; compact_flags (one scan) gives the ascending kept list; gather_rows (prims.h) copies the kept
 //            rows word by word.
 #include "outliers.h"
+#include "cloud_tool.h"
 #include "fixed_reduce.h"
 #include "grid_walk.h"
-#include "prims.h"
-#include "stages.h"
 #include "voxel.h"
-#include <functional>
 
 namespace plade {
 
@@ -189,19 +187,15 @@ void launch_search(plade_ctx *ctx, const StatArgs &a) {
 
 }  // namespace
 
-struct OutlierWork {
+struct OutlierWork : KeepWork {
     TargetGrid grid;
-    DBuf<uint32_t> fail, count, flags, pos, kept, nbr_count;
-    DBuf<float> in, out;             // the host-pointer entry point's device copies (grow-only)
+    DBuf<uint32_t> fail, count, nbr_count;
     DBuf<double> mean, partial, stat;
-    DBuf<uint8_t> keep;
     EventSpans<5> spans;             // grid, search, reduce, compact
     int builds = 0;
     uint32_t h_count = 0;
     double h_stat[3] = {0.0, 0.0, 0.0};
 };
-OutlierWork *outlier_work_create() { return new OutlierWork; }
-void outlier_work_destroy(OutlierWork *w) { delete w; }
 
 namespace {
 
@@ -213,9 +207,7 @@ void check_params(uint32_t n, uint32_t stride, const plade_outlier_params &p) {
         PLADE_REQUIRE(p.k >= OUTLIERS_K_MIN && p.k <= OUTLIERS_K_MAX, PLADE_EINVAL, "filter_outliers: k must be in [1, 64]");
         PLADE_REQUIRE(std::isfinite(p.alpha) && p.alpha >= 0.0, PLADE_EINVAL, "filter_outliers: alpha must be finite and >= 0");
     } else {
-        const float r = (float)p.radius;
-        PLADE_REQUIRE(std::isfinite(p.radius) && std::isfinite(r) && r > 0.f && std::isfinite(r * r), PLADE_EINVAL,
-                      "filter_outliers: radius must be finite and > 0");
+        PLADE_REQUIRE(radius_ok(p.radius, false), PLADE_EINVAL, "filter_outliers: radius must be finite and > 0");
         PLADE_REQUIRE(p.min_neighbours >= 1, PLADE_EINVAL, "filter_outliers: min_neighbours must be >= 1");
     }
 }
@@ -224,19 +216,18 @@ void check_params(uint32_t n, uint32_t stride, const plade_outlier_params &p) {
 // m or c (want_values) in W, gathers the kept rows into dst(kept) -- not called when nothing is kept --, waits, fills the summary
 // and the stats.  Returns the number of kept points.
 uint32_t filter_dev(plade_ctx *ctx, OutlierWork &W, const float *d_rows, uint32_t n, uint32_t stride, const float bbmin[3],
-                    const float bbmax[3], const plade_outlier_params &p, bool want_values, const std::function<float *(uint32_t)> &dst,
+                    const float bbmax[3], const plade_outlier_params &p, bool want_values, const KeepRows &dst,
                     plade_outlier_summary *summary) {
     W.spans.mark(ctx, 0);
     TargetGrid &G = W.grid;
     const bool stat = p.mode == PLADE_OUTLIER_STATISTICAL;
     uint32_t *d_cnt = W.count.ensure(4);   // [0]: the ring list's length, [1]: occupied cells
     uint8_t *d_keep = W.keep.ensure((size_t)n + 4);
-    uint32_t *d_flags = W.flags.ensure((size_t)n + 1);
     double *d_stat = W.stat.ensure(4);
     W.builds = 0;
     W.h_count = 0;
     ctx->fill_async(d_cnt, 0, 4);
-    ctx->fill_async(d_flags + n, 0, 4);    // compact_flags scans n + 1 entries
+    uint32_t *d_flags = keep_flags(ctx, W, n);
     if (stat) {
         const int k = p.k, m = (int)std::min<uint32_t>((uint32_t)k, n - 1);
         double *d_mean = W.mean.ensure(n);
@@ -288,8 +279,7 @@ uint32_t filter_dev(plade_ctx *ctx, OutlierWork &W, const float *d_rows, uint32_
         W.spans.mark(ctx, 2);
     }
     W.spans.mark(ctx, 3);
-    const uint32_t total = compact_flags(ctx, d_flags, n, W.pos, W.kept);   // (waits for the count)
-    if (total) gather_rows(ctx, d_rows, stride, W.kept.p, total, dst(total));
+    const uint32_t total = keep_compact_gather(ctx, W, d_rows, n, stride, dst);
     W.spans.mark(ctx, 4);
     ctx->sync();
     if (summary) {
@@ -310,11 +300,6 @@ uint32_t filter_dev(plade_ctx *ctx, OutlierWork &W, const float *d_rows, uint32_
     if (W.builds) grid_stats(ctx, "outliers", G);
     ctx->stats.add("outliers_kept", total);
     return total;
-}
-
-OutlierWork &work_of(plade_ctx *ctx) {
-    if (!ctx->outlier_work) ctx->outlier_work = outlier_work_create();
-    return *ctx->outlier_work;
 }
 
 }  // namespace
@@ -338,19 +323,15 @@ extern "C" int plade_filter_outliers(plade_ctx *ctx, const float *rows, uint32_t
                                      uint32_t *count_out, plade_outlier_summary *summary) {
     return guarded(ctx, [&]() -> int {
         PLADE_REQUIRE(rows, PLADE_EINVAL, "plade_filter_outliers: NULL cloud");
-        plade_outlier_params p;
-        if (params) p = *params; else plade_outlier_default_params(&p);
+        const plade_outlier_params p = params_or_default(params, plade_outlier_default_params);
         check_params(n, stride, p);
-        OutlierWork &W = work_of(ctx);
+        OutlierWork &W = work_in<OutlierWork>(ctx->outlier_work);
         float mn[3], mx[3];
         upload_rows(ctx, W.in, rows, n, stride, mn, mx);
         const bool stat = p.mode == PLADE_OUTLIER_STATISTICAL;
         const bool want_values = stat ? mean_dist_out != nullptr : count_out != nullptr;
-        const uint32_t total = filter_dev(ctx, W, W.in.p, n, stride, mn, mx, p, want_values,
-                                          [&](uint32_t kept) { return W.out.ensure((size_t)kept * stride + 4); }, summary);
-        if (keep_out) HIP_TRY(hipMemcpyAsync(keep_out, W.keep.p, n, hipMemcpyDeviceToHost, ctx->stream));
-        if (kept_index_out && total) HIP_TRY(hipMemcpyAsync(kept_index_out, W.kept.p, (size_t)total * 4, hipMemcpyDeviceToHost, ctx->stream));
-        if (rows_out && total) HIP_TRY(hipMemcpyAsync(rows_out, W.out.p, (size_t)total * stride * 4, hipMemcpyDeviceToHost, ctx->stream));
+        const uint32_t total = filter_dev(ctx, W, W.in.p, n, stride, mn, mx, p, want_values, keep_rows_host(W, stride), summary);
+        keep_copy_out(ctx, W, n, total, stride, keep_out, kept_index_out, rows_out);
         if (stat && mean_dist_out) HIP_TRY(hipMemcpyAsync(mean_dist_out, W.mean.p, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
         if (!stat && count_out) HIP_TRY(hipMemcpyAsync(count_out, W.nbr_count.p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
         ctx->sync();
@@ -363,22 +344,16 @@ extern "C" int plade_cloud_filter_outliers_dev(plade_ctx *ctx, plade_cloud *clou
     return guarded(ctx, [&]() -> int {
         PLADE_REQUIRE(cloud && out, PLADE_EINVAL, "plade_cloud_filter_outliers_dev: NULL cloud");
         *out = nullptr;
-        plade_outlier_params p;
-        if (params) p = *params; else plade_outlier_default_params(&p);
+        const plade_outlier_params p = params_or_default(params, plade_outlier_default_params);
         const CloudDev &in = cloud->dev;
         check_params(in.n, 6, p);
-        OutlierWork &W = work_of(ctx);
-        plade_cloud *c = new plade_cloud;
-        try {
-            const uint32_t total = filter_dev(ctx, W, in.aos.p, in.n, 6, in.bbmin, in.bbmax, p, false,
-                                              [&](uint32_t kept) { cloud_shape(c->dev, kept); return c->dev.aos.p; }, summary);
-            if (keep_out) HIP_TRY(hipMemcpyAsync(keep_out, W.keep.p, in.n, hipMemcpyDeviceToHost, ctx->stream));
-            if (kept_index_out && total) HIP_TRY(hipMemcpyAsync(kept_index_out, W.kept.p, (size_t)total * 4, hipMemcpyDeviceToHost, ctx->stream));
+        OutlierWork &W = work_in<OutlierWork>(ctx->outlier_work);
+        resident_result(ctx, out, [&](CloudDev &c) {
+            const uint32_t total = filter_dev(ctx, W, in.aos.p, in.n, 6, in.bbmin, in.bbmax, p, false, keep_rows_cloud(c), summary);
+            keep_copy_out(ctx, W, in.n, total, 6, keep_out, kept_index_out, nullptr);
             ctx->sync();
-            PLADE_REQUIRE(total >= 1, PLADE_EFAIL, "plade_cloud_filter_outliers_dev: the filter keeps no point (a resident cloud cannot be empty)");
-            cloud_finish_device(ctx, c->dev);   // SoA planes + bounding box of the resident cloud, as plade_cloud_upload
-        } catch (...) { delete c; throw; }
-        *out = c;
+            require_kept(total, "plade_cloud_filter_outliers_dev: the filter");
+        });
         return PLADE_OK;
     });
 }

@@ -11,6 +11,7 @@
 //   summary  k_smooth_sum / k_smooth_final, in the fixed order of fixed_reduce.h: sum of delta^2 and max |delta| over the fitted
 //            points, their number, the largest count.
 #include "smooth.h"
+#include "cloud_tool.h"
 #include "fixed_reduce.h"
 #include "grid_walk.h"
 #include "pca_eig.h"
@@ -156,17 +157,14 @@ struct SmoothWork {
     double h_d[2] = {0.0, 0.0};
     uint32_t h_u[2] = {0, 0};
 };
-SmoothWork *smooth_work_create() { return new SmoothWork; }
-void smooth_work_destroy(SmoothWork *w) { delete w; }
 
 namespace {
 
 void check_params(uint32_t n, uint32_t stride, const plade_smooth_params &p) {
     PLADE_REQUIRE(n >= 1, PLADE_EINVAL, "smooth_cloud: the cloud is empty (n = 0)");
     PLADE_REQUIRE(stride >= 3, PLADE_EINVAL, "smooth_cloud: stride must be >= 3 floats");
-    const float r = (float)p.radius;
     // r2 a normal fp32 number: at 0 no point would be its own neighbour (d = 0 < r2 must hold), a subnormal r2 carries few bits
-    PLADE_REQUIRE(std::isfinite(p.radius) && std::isfinite(r) && r > 0.f && std::isfinite(r * r) && r * r >= FLT_MIN, PLADE_EINVAL,
+    PLADE_REQUIRE(radius_ok(p.radius, true), PLADE_EINVAL,
                   "smooth_cloud: radius must be finite and > 0, and its fp32 square finite and not below FLT_MIN");
     PLADE_REQUIRE(p.min_neighbours >= SMOOTH_MIN_NEIGHBOURS, PLADE_EINVAL, "smooth_cloud: min_neighbours must be >= 3");
     PLADE_REQUIRE(std::isfinite(p.viewpoint[0]) && std::isfinite(p.viewpoint[1]) && std::isfinite(p.viewpoint[2]), PLADE_EINVAL,
@@ -220,11 +218,6 @@ void smooth_dev(plade_ctx *ctx, SmoothWork &W, const float *d_rows, uint32_t n, 
     grid_stats(ctx, "smooth", W.grid);
 }
 
-SmoothWork &work_of(plade_ctx *ctx) {
-    if (!ctx->smooth_work) ctx->smooth_work = smooth_work_create();
-    return *ctx->smooth_work;
-}
-
 }  // namespace
 }  // namespace plade
 
@@ -244,10 +237,9 @@ extern "C" int plade_smooth_cloud(plade_ctx *ctx, const float *rows, uint32_t n,
                                   uint8_t *fitted_out, double *moments_out, plade_smooth_summary *summary) {
     return guarded(ctx, [&]() -> int {
         PLADE_REQUIRE(rows && out_xyz, PLADE_EINVAL, "plade_smooth_cloud: NULL cloud or output");
-        plade_smooth_params p;
-        if (params) p = *params; else plade_smooth_default_params(&p);
+        const plade_smooth_params p = params_or_default(params, plade_smooth_default_params);
         check_params(n, stride, p);
-        SmoothWork &W = work_of(ctx);
+        SmoothWork &W = work_in<SmoothWork>(ctx->smooth_work);
         float mn[3], mx[3];
         upload_rows(ctx, W.in, rows, n, stride, mn, mx);
         FitArgs a;
@@ -274,23 +266,19 @@ extern "C" int plade_cloud_smooth_dev(plade_ctx *ctx, plade_cloud *cloud, const 
     return guarded(ctx, [&]() -> int {
         PLADE_REQUIRE(cloud && out, PLADE_EINVAL, "plade_cloud_smooth_dev: NULL cloud");
         *out = nullptr;
-        plade_smooth_params p;
-        if (params) p = *params; else plade_smooth_default_params(&p);
+        const plade_smooth_params p = params_or_default(params, plade_smooth_default_params);
         const CloudDev &in = cloud->dev;
         check_params(in.n, 6, p);
-        SmoothWork &W = work_of(ctx);
-        plade_cloud *c = new plade_cloud;
-        try {
-            cloud_shape(c->dev, in.n);
+        SmoothWork &W = work_in<SmoothWork>(ctx->smooth_work);
+        resident_result(ctx, out, [&](CloudDev &c) {
+            cloud_shape(c, in.n);
             FitArgs a;
             memset(&a, 0, sizeof(a));
-            a.xyz = c->dev.aos.p; a.xyz_stride = 6;
-            a.nrm = c->dev.aos.p + 3; a.nrm_stride = 6;
+            a.xyz = c.aos.p; a.xyz_stride = 6;
+            a.nrm = c.aos.p + 3; a.nrm_stride = 6;
             if (!use_fit_normals) a.keep_nrm = reinterpret_cast<const uint32_t *>(in.aos.p);
             smooth_dev(ctx, W, in.aos.p, in.n, 6, in.bbmin, in.bbmax, p, a, summary);
-            cloud_finish_device(ctx, c->dev);   // SoA planes + bounding box of the resident cloud, as plade_cloud_upload
-        } catch (...) { delete c; throw; }
-        *out = c;
+        });
         return PLADE_OK;
     });
 }

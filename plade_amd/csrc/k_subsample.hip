@@ -23,11 +23,9 @@
 //   output   k_sub_scatter: keep, flags and round in the original order; compact_flags (one scan) gives the ascending kept list;
 //            gather_rows (prims.h) copies the kept rows word for word.
 #include "subsample.h"
+#include "cloud_tool.h"
 #include "grid_walk.h"
-#include "prims.h"
-#include "stages.h"
 #include "voxel.h"
-#include <functional>
 
 namespace plade {
 
@@ -98,15 +96,11 @@ __global__ __launch_bounds__(ROW_TPB) void k_sub_scatter(const float4 *__restric
 
 }  // namespace
 
-struct SubsampleWork {
+struct SubsampleWork : KeepWork {
     TargetGrid grid;
-    DBuf<uint32_t> state, list[2], count, flags, pos, kept, round;
-    DBuf<uint8_t> keep;
-    DBuf<float> in, out;             // the host-pointer entry point's device copies (grow-only)
+    DBuf<uint32_t> state, list[2], count, round;
     EventSpans<4> spans;             // grid, rounds, compact + gather
 };
-SubsampleWork *subsample_work_create() { return new SubsampleWork; }
-void subsample_work_destroy(SubsampleWork *w) { delete w; }
 
 namespace {
 
@@ -114,15 +108,14 @@ void check_params(uint32_t n, uint32_t stride, const plade_subsample_params &p) 
     PLADE_REQUIRE(n >= 1, PLADE_EINVAL, "subsample_spacing: the cloud is empty (n = 0)");
     PLADE_REQUIRE(n < 0x80000000u, PLADE_EINVAL, "subsample_spacing: more than 2^31 - 1 points");   // (round << 1 | kept in 32 bits)
     PLADE_REQUIRE(stride >= 3, PLADE_EINVAL, "subsample_spacing: stride must be >= 3 floats");
-    const float r = (float)p.spacing;
-    PLADE_REQUIRE(std::isfinite(p.spacing) && std::isfinite(r) && r > 0.f && std::isfinite(r * r) && r * r >= FLT_MIN, PLADE_EINVAL,
+    PLADE_REQUIRE(radius_ok(p.spacing, true), PLADE_EINVAL,
                   "subsample_spacing: spacing must be finite and > 0, its fp32 square finite and not below FLT_MIN");
 }
 
 // The subsample of a device cloud of `stride` floats per point with a known bounding box.  Leaves keep, round and the kept list in
 // W, gathers the kept rows into dst(kept), waits, fills the summary and the stats.  Returns the number of kept points (>= 1).
 uint32_t subsample_dev(plade_ctx *ctx, SubsampleWork &W, const float *d_rows, uint32_t n, uint32_t stride, const float bbmin[3],
-                       const float bbmax[3], const plade_subsample_params &p, const std::function<float *(uint32_t)> &dst,
+                       const float bbmax[3], const plade_subsample_params &p, const KeepRows &dst,
                        plade_subsample_summary *summary) {
     W.spans.mark(ctx, 0);
     TargetGrid &G = W.grid;
@@ -157,13 +150,11 @@ uint32_t subsample_dev(plade_ctx *ctx, SubsampleWork &W, const float *d_rows, ui
     W.spans.mark(ctx, 2);
 
     uint8_t *d_keep = W.keep.ensure((size_t)n + 4);
-    uint32_t *d_flags = W.flags.ensure((size_t)n + 1), *d_round = W.round.ensure(n);
-    ctx->fill_async(d_flags + n, 0, 4);    // compact_flags scans n + 1 entries
+    uint32_t *d_round = W.round.ensure(n), *d_flags = keep_flags(ctx, W, n);
     hipLaunchKernelGGL(k_sub_scatter, dim3(cdiv(n, ROW_TPB)), dim3(ROW_TPB), 0, ctx->stream, a.g.sorted, a.state, n, d_keep, d_flags, d_round);
     HIP_TRY(hipGetLastError());
-    const uint32_t total = compact_flags(ctx, d_flags, n, W.pos, W.kept);   // (waits for the count)
+    const uint32_t total = keep_compact_gather(ctx, W, d_rows, n, stride, dst);
     PLADE_REQUIRE(total >= 1, PLADE_EFAIL, "subsample_spacing: no point was kept");   // (cannot happen: the smallest key is kept)
-    gather_rows(ctx, d_rows, stride, W.kept.p, total, dst(total));
     W.spans.mark(ctx, 3);
     ctx->sync();
     if (summary) {
@@ -180,11 +171,6 @@ uint32_t subsample_dev(plade_ctx *ctx, SubsampleWork &W, const float *d_rows, ui
     ctx->stats.add("subsample_kept", total);
     grid_stats(ctx, "subsample", W.grid);
     return total;
-}
-
-SubsampleWork &work_of(plade_ctx *ctx) {
-    if (!ctx->subsample_work) ctx->subsample_work = subsample_work_create();
-    return *ctx->subsample_work;
 }
 
 }  // namespace
@@ -205,17 +191,13 @@ extern "C" int plade_subsample_spacing(plade_ctx *ctx, const float *rows, uint32
                                        plade_subsample_summary *summary) {
     return guarded(ctx, [&]() -> int {
         PLADE_REQUIRE(rows, PLADE_EINVAL, "plade_subsample_spacing: NULL cloud");
-        plade_subsample_params p;
-        if (params) p = *params; else plade_subsample_default_params(&p);
+        const plade_subsample_params p = params_or_default(params, plade_subsample_default_params);
         check_params(n, stride, p);
-        SubsampleWork &W = work_of(ctx);
+        SubsampleWork &W = work_in<SubsampleWork>(ctx->subsample_work);
         float mn[3], mx[3];
         upload_rows(ctx, W.in, rows, n, stride, mn, mx);
-        const uint32_t total = subsample_dev(ctx, W, W.in.p, n, stride, mn, mx, p,
-                                             [&](uint32_t kept) { return W.out.ensure((size_t)kept * stride + 4); }, summary);
-        if (keep_out) HIP_TRY(hipMemcpyAsync(keep_out, W.keep.p, n, hipMemcpyDeviceToHost, ctx->stream));
-        if (kept_index_out) HIP_TRY(hipMemcpyAsync(kept_index_out, W.kept.p, (size_t)total * 4, hipMemcpyDeviceToHost, ctx->stream));
-        if (rows_out) HIP_TRY(hipMemcpyAsync(rows_out, W.out.p, (size_t)total * stride * 4, hipMemcpyDeviceToHost, ctx->stream));
+        const uint32_t total = subsample_dev(ctx, W, W.in.p, n, stride, mn, mx, p, keep_rows_host(W, stride), summary);
+        keep_copy_out(ctx, W, n, total, stride, keep_out, kept_index_out, rows_out);
         if (round_out) HIP_TRY(hipMemcpyAsync(round_out, W.round.p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
         ctx->sync();
         return PLADE_OK;
@@ -227,21 +209,15 @@ extern "C" int plade_cloud_subsample_dev(plade_ctx *ctx, plade_cloud *cloud, con
     return guarded(ctx, [&]() -> int {
         PLADE_REQUIRE(cloud && out, PLADE_EINVAL, "plade_cloud_subsample_dev: NULL cloud");
         *out = nullptr;
-        plade_subsample_params p;
-        if (params) p = *params; else plade_subsample_default_params(&p);
+        const plade_subsample_params p = params_or_default(params, plade_subsample_default_params);
         const CloudDev &in = cloud->dev;
         check_params(in.n, 6, p);
-        SubsampleWork &W = work_of(ctx);
-        plade_cloud *c = new plade_cloud;
-        try {
-            const uint32_t total = subsample_dev(ctx, W, in.aos.p, in.n, 6, in.bbmin, in.bbmax, p,
-                                                 [&](uint32_t kept) { cloud_shape(c->dev, kept); return c->dev.aos.p; }, summary);
-            if (keep_out) HIP_TRY(hipMemcpyAsync(keep_out, W.keep.p, in.n, hipMemcpyDeviceToHost, ctx->stream));
-            if (kept_index_out) HIP_TRY(hipMemcpyAsync(kept_index_out, W.kept.p, (size_t)total * 4, hipMemcpyDeviceToHost, ctx->stream));
+        SubsampleWork &W = work_in<SubsampleWork>(ctx->subsample_work);
+        resident_result(ctx, out, [&](CloudDev &c) {
+            const uint32_t total = subsample_dev(ctx, W, in.aos.p, in.n, 6, in.bbmin, in.bbmax, p, keep_rows_cloud(c), summary);
+            keep_copy_out(ctx, W, in.n, total, 6, keep_out, kept_index_out, nullptr);
             ctx->sync();
-            cloud_finish_device(ctx, c->dev);   // SoA planes + bounding box of the resident cloud, as plade_cloud_upload
-        } catch (...) { delete c; throw; }
-        *out = c;
+        });
         return PLADE_OK;
     });
 }

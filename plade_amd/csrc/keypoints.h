@@ -32,10 +32,6 @@
 
 namespace plade {
 
-struct IssWork;
-IssWork *iss_work_create();
-void iss_work_destroy(IssWork *w);
-
 // The steps plade_register_keypoints chains (k_corr_pose.hip), device to device.
 // The detector on n device rows (`stride` floats apart, x y z first) with a known bounding box: returns the device list of the
 // keypoints' original indices, ascending (valid until the context's next detection), its length in *n_keypoints, fills the summary

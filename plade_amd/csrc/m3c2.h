@@ -34,8 +34,4 @@ namespace plade {
 
 constexpr int M3C2_MIN_POINTS = 2;
 
-struct M3c2Work;
-M3c2Work *m3c2_work_create();
-void m3c2_work_destroy(M3c2Work *w);
-
 }  // namespace plade

@@ -29,8 +29,6 @@ namespace plade {
 constexpr int MERGE_MAX_CLOUDS = 16;
 
 struct MergeWork;
-MergeWork *merge_work_create();
-void merge_work_destroy(MergeWork *w);
 
 // The voxel fuse of ONE device cloud (n x 6 rows) under the identity at leaf > 0 -- plade_merge_clouds_dev of one cloud -- for the
 // stages that sample a cloud with its normals (gicp.h): returns the number of fused rows and leaves them, n_out x 6, behind *d_out in

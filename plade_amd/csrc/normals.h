@@ -19,8 +19,6 @@ namespace plade {
 constexpr int NORMALS_K_MIN = 3, NORMALS_K_MAX = 64;
 
 struct NormalsWork;
-NormalsWork *normals_work_create();
-void normals_work_destroy(NormalsWork *w);
 
 // d_xyz: n points of `stride` floats on the device, finite (bbmin / bbmax: their bounding box, bbox_host).  Writes n x 6 floats
 // (x y z nx ny nz, the input coordinates copied bit for bit) to d_out; d_curv (n floats) and d_nbr (n x k int32, -1 behind the

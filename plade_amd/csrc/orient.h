@@ -39,11 +39,3 @@
 // the order of the active lists, or whether the input is a host array or a resident cloud.
 #pragma once
 #include "ctx.h"
-
-namespace plade {
-
-struct OrientWork;
-OrientWork *orient_work_create();
-void orient_work_destroy(OrientWork *w);
-
-}  // namespace plade

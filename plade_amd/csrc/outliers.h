@@ -28,8 +28,4 @@ namespace plade {
 
 constexpr int OUTLIERS_K_MIN = 1, OUTLIERS_K_MAX = 64;
 
-struct OutlierWork;
-OutlierWork *outlier_work_create();
-void outlier_work_destroy(OutlierWork *w);
-
 }  // namespace plade

@@ -32,8 +32,4 @@ namespace plade {
 
 constexpr int SMOOTH_MIN_NEIGHBOURS = 3;
 
-struct SmoothWork;
-SmoothWork *smooth_work_create();
-void smooth_work_destroy(SmoothWork *w);
-
 }  // namespace plade

@@ -26,11 +26,3 @@
 // the order of the active lists, or whether the input is a host array or a resident cloud.
 #pragma once
 #include "ctx.h"
-
-namespace plade {
-
-struct SubsampleWork;
-SubsampleWork *subsample_work_create();
-void subsample_work_destroy(SubsampleWork *w);
-
-}  // namespace plade

@@ -1,9 +1,10 @@
 """Print the cloud tools' bits from one build of the library, to compare two builds (not part of bench.py).
 
-Normals, the outlier filter (both modes), the components (with and without keep_largest), the smoothing, the distances, M3C2,
-FPFH and its match, the merge (fused and concatenated) and the two ICP linearisations, each on tests/golden/g9_room.npz and on a
-seeded synthetic sheet: one line per call with a sha1 of every returned array and every summary field (floats in hex).  One
-process per library:
+Normals, the outlier filter (both modes), the components (with and without keep_largest), the subsample, the consistent
+orientation (both modes), the smoothing, the distances, M3C2, FPFH and its match, the ISS keypoints, the merge (fused and
+concatenated), the two ICP linearisations and the resident forms that return a cloud (each downloaded), each on
+tests/golden/g9_room.npz and on a seeded synthetic sheet: one line per call with a sha1 of every returned array and every summary
+field (floats in hex).  One process per library:
 
     python tools/cloud_tools_bits.py path/to/parent/libplade_hip.so > old.txt
     python tools/cloud_tools_bits.py plade_amd/libplade_hip.so      > new.txt
@@ -57,6 +58,9 @@ def run(ctx, name, tgt, src, T, r):
     line("outliers_radius", ctx.remove_outliers(tgt, mode="radius", radius=r, min_neighbours=6))
     line("components", ctx.connected_components(tgt, 0.5 * r, min_size=3))
     line("components_largest", ctx.connected_components(tgt, 0.5 * r, min_size=3, keep_largest=2))
+    line("subsample", ctx.subsample(tgt, 0.7 * r, seed=5))
+    line("orient_vote", ctx.orient_consistent(tgt, r, mode=plade_amd.ORIENT_VOTE, viewpoint=(0.0, 0.0, 10.0)))
+    line("orient_extreme", ctx.orient_consistent(tgt, r, mode=plade_amd.ORIENT_EXTREME, direction=(0.0, 0.0, 1.0), inward=1))
     line("smooth", ctx.smooth_cloud(tgt, r, moments=True))
     line("distances", ctx.cloud_distances(tgt, src, 2.0 * r, T=T))
     line("m3c2", ctx.m3c2(tgt[::3], tgt, src, r, 4.0 * r, T=T, moments=True))
@@ -66,11 +70,33 @@ def run(ctx, name, tgt, src, T, r):
     line("fpfh_src", (ds, is_))
     line("match", ctx.match_features(ds, dt, mutual=True, max_ratio=0.9))
     line("match_plain", ctx.match_features(ds, dt, mutual=False))
+    line("iss", ctx.iss_keypoints(tgt, 2.0 * r, seams=True))
     line("merge_fused", ctx.merge_clouds([tgt, src], [None, T], leaf=r))
     line("merge_cat", ctx.merge_clouds([tgt, src], [None, T], leaf=0.0))
     for c in (None, (3.0, -2.0, 0.5)):
         line("icp_linearize", ctx.icp_linearize(tgt, np.ascontiguousarray(src[:, :3]), T, 2.0 * r, center=c))
         line("gicp_linearize", ctx.gicp_linearize(tgt, src, T, 2.0 * r, center=c))
+
+    # the resident forms that return a cloud: the call's own outputs, then the cloud's rows
+    def resident(tag, res):
+        cloud, rest = (res[0], res[1:]) if isinstance(res, tuple) else (res, ())
+        line(tag, (rest, cloud.download()))
+        cloud.free()
+
+    ct, cs = ctx.upload(tgt), ctx.upload(src)
+    resident("outliers_stat_dev", ctx.remove_outliers_dev(ct, mode="statistical", k=16, alpha=1.0, info=True))
+    resident("outliers_radius_dev", ctx.remove_outliers_dev(ct, mode="radius", radius=r, min_neighbours=6, info=True))
+    resident("components_dev", ctx.filter_components_dev(ct, 0.5 * r, min_size=3, keep_largest=2, info=True))
+    resident("subsample_dev", ctx.subsample_dev(ct, 0.7 * r, seed=5, info=True))
+    resident("orient_vote_dev", ctx.orient_consistent_dev(ct, r, mode=plade_amd.ORIENT_VOTE, viewpoint=(0.0, 0.0, 10.0), info=True))
+    resident("orient_extreme_dev", ctx.orient_consistent_dev(ct, r, mode=plade_amd.ORIENT_EXTREME, inward=1, info=True))
+    resident("smooth_dev", ctx.smooth_cloud_dev(ct, r, info=True))
+    resident("smooth_keep_normals_dev", ctx.smooth_cloud_dev(ct, r, fit_normals=False, info=True))
+    resident("upload_xyz", ctx.upload_xyz(xyz, k=16))
+    resident("merge_fused_dev", ctx.merge_clouds_dev([ct, cs], [None, T], leaf=r, info=True))
+    resident("merge_cat_dev", ctx.merge_clouds_dev([ct, cs], [None, T], leaf=0.0, info=True))
+    ct.free()
+    cs.free()
     return out
 
 

@@ -14,9 +14,9 @@
 //           ends when the k-th key is closer than the outside of the block or the block covers the grid.  Sparse regions and
 //           isolated outliers come out exact.
 //   PCA     in the same kernels, by the one function pca_store (identical fp64 arithmetic on both paths): two passes over the
-//           neighbour list (staged in LDS) in its order, then pca_eig (pca_eig.h, shared with k_smooth.hip): closed-form eigenvalues
-//           of the 3 x 3 symmetric covariance, the eigenvector of the smallest from the cross products of the rows of C - l0 I;
-//           orientation toward the viewpoint.
+//           neighbour list (staged in LDS) in its order, then pca_eig (pca_eig.h, shared with k_smooth.hip): the closed-form
+//           eigen-solve of the 3 x 3 symmetric covariance, the eigenvector of the smallest eigenvalue as well as its conditioning
+//           allows (the contract stands there); orientation toward the viewpoint.
 #include "normals.h"
 #include "cloud_tool.h"
 #include "grid_walk.h"

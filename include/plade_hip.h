@@ -763,6 +763,66 @@ int plade_smooth_cloud(plade_ctx *ctx, const float *rows, uint32_t n, uint32_t s
 int plade_cloud_smooth_dev(plade_ctx *ctx, plade_cloud *cloud, const plade_smooth_params *params, int32_t use_fit_normals,
                            plade_cloud **out, plade_smooth_summary *summary);
 
+/* ---- multi-scale normals and dimensionality features: the normal-scale step of M3C2 (Lague, Brodu, Leroux 2013; no reference
+ * counterpart) ------------------------------------------------------------------------------------------------------------------------
+ * Semantics (plade_amd/csrc/scales.h).  Input: n >= 1 points, rows of `stride` >= 3 floats, x y z first, all
+ * coordinates finite.  The queries are all n points (query_index NULL; k is ignored) or query_index: k >= 1 strictly ascending indices
+ * < n, e.g. the kept_index of plade_subsample_spacing; every output is by query, in the order of that list.  params->scales = S radii,
+ * 1 <= S <= 8, whose fp32 squares r2_s = (float)r_s * (float)r_s are strictly ascending.  One grid and one walk serve all scales.
+ *   neighbours   N(i, s) = the j with d(i, j) < r2_s (the fp32 squared distance and the strict `<` of plade_smooth_cloud); the point
+ *                itself is one of them.  c(i, s) = |N(i, s)|.
+ *   moments      unweighted, fp64, q_j = double(p_j) - double(p_i): per scale the sums of q (3) and of q_a q_b (xx xy xz yy yz zz).
+ *                Each scale adds the terms of the neighbours that pass its own test, in the order of the walk over the grid of the
+ *                largest radius (no atomics): a scale's moments do not depend on which smaller scales were asked for.
+ *   fit          mu = sum q / c, C = M / c - mu mu^T; l1 >= l2 >= l3 = the eigenvalues of C by the closed form, each clamped to
+ *                >= 0; n = the unit eigenvector of the smallest one (the solve of plade_estimate_normals).  A scale is fitted iff
+ *                c >= min_neighbours, C is not exactly zero and l1 > 0; the normal of an unfitted scale is NaN.
+ *   features     fp64: linearity (l1 - l2) / l1, planarity (l2 - l3) / l1, sphericity l3 / l1, variation l3 / ((l1 + l2) + l3).
+ *   choice       over the fitted scales in ascending s: mode 0 keeps the largest planarity (M3C2's rule), mode 1 the smallest
+ *                variation; only a strict improvement replaces a scale (ties keep the smaller radius); -1: no scale is fitted.
+ *   orientation  of every scale's normal.  orient = 0: flipped when (viewpoint - p_i) . n < 0.  orient = 1 (stride >= 6): words
+ *                3..5 of the row are a normal g; t = (g_x n_x + g_y n_y) + g_z n_z in fp64; flipped when t < 0; when t is 0 or not
+ *                finite the viewpoint test decides.
+ *   output       every array may be NULL.  chosen_out: k int32; normal_out: k x 3 floats, the chosen scale's (NaN when -1);
+ *                features_out: k x 4 floats in the order above, the chosen scale's (NaN when -1); per scale count_out: k x S uint32;
+ *                fitted_out: k x S bytes 0 / 1; eigenvalues_out: k x S x 3 doubles l1 l2 l3; normals_out: k x S x 3 floats;
+ *                moments_out: k x S x 9 doubles -- a test seam; summary: queries, fitted (chosen >= 0), the histogram of the chosen
+ *                scale and the largest count (integers, a fixed-order reduction).
+ * The same input gives the same bits on every run, on every context and from plade_cloud_scale_normals_dev.  Counts, fitted flags
+ * and -- away from ties -- chosen depend on the point set and the radii only; the fp64 sums follow the grid's order.
+ * Errors: PLADE_EINVAL for n = 0, stride < 3 (< 6 with orient = 1), a NULL cloud, a non-finite coordinate or viewpoint, scales outside
+ * 1..8, a radius <= 0 or not finite (or its fp32 square not finite or below FLT_MIN), squares not strictly ascending, min_neighbours
+ * < 3, mode or orient not 0 / 1, k = 0 with a list, a query index >= n or a list not strictly ascending; the context stays usable.
+ * plade_stats_get then reports scales_grid_s, scales_walk_s (the walk and the fits), scales_reduce_s (HIP events on the context's
+ * stream) and scales_fitted. */
+typedef struct plade_scale_params {
+    double radii[8];             /* the first `scales` must be set (> 0), absolute, in the cloud's units */
+    int32_t scales;              /* S, 1 .. 8: there is no automatic value */
+    int32_t min_neighbours;      /* >= 3; a scale with fewer neighbours (the point itself included) is not fitted */
+    int32_t mode;                /* 0: the largest planarity; 1: the smallest surface variation */
+    int32_t orient;              /* 0: toward the viewpoint; 1: along the rows' own normals, the viewpoint where they do not decide */
+    float viewpoint[3];
+    int32_t reserved;            /* 0 */
+} plade_scale_params;
+typedef struct plade_scale_summary {
+    uint64_t queries, fitted;    /* fitted: queries with chosen >= 0 */
+    uint32_t chosen_hist[8];     /* queries per chosen scale */
+    uint32_t max_count;          /* the largest c(i, s) */
+    uint32_t reserved;           /* 0 */
+} plade_scale_summary;
+/* The defaults: radii 0 and scales = 0 (unset), min_neighbours = 6, mode = 0, orient = 0, viewpoint = 0 0 0.  Needs no GPU. */
+void plade_scale_default_params(plade_scale_params *p);
+int plade_cloud_scale_features(plade_ctx *ctx, const float *rows, uint32_t n, uint32_t stride, const uint32_t *query_index, uint32_t k,
+                               const plade_scale_params *params, int32_t *chosen_out, float *normal_out, float *features_out,
+                               uint32_t *count_out, uint8_t *fitted_out, double *eigenvalues_out, float *normals_out,
+                               double *moments_out, plade_scale_summary *summary);
+/* The same on a resident cloud (plade_cloud_upload / plade_cloud_upload_xyz; rows x y z nx ny nz, so orient = 1 reads the cloud's
+ * normals) into a NEW resident cloud of the k queries: x y z bit for bit, columns 3..5 the chosen normal (NaN where no scale is
+ * fitted, which plade_cloud_m3c2_dev reports as "no axis").  The rows and the summary are the bits of plade_cloud_scale_features on
+ * the cloud's rows.  *out is NULL after every refusal.  Free both clouds with plade_cloud_free. */
+int plade_cloud_scale_normals_dev(plade_ctx *ctx, plade_cloud *cloud, const uint32_t *query_index, uint32_t k,
+                                  const plade_scale_params *params, plade_cloud **out, plade_scale_summary *summary);
+
 /* ---- change detection between two registered clouds: M3C2 distances (Lague, Brodu, Leroux 2013; no reference counterpart) -------
  * Semantics (plade_amd/csrc/m3c2.h).  Per core point a cylinder of radius R and half-length L along the core
  * point's normal; the mean position of each cloud inside it, measured along the normal; the difference of the two means and its
@@ -1110,7 +1170,7 @@ int plade_dump_get(plade_ctx *ctx, const char *name, const void **ptr, int64_t *
  * names is a ';'-separated list, values has one double per name.
  * The cloud tools that search a point grid also report the grid of their last call: <tool>_grid_dx, _grid_dy, _grid_dz (cells per
  * axis) and <tool>_grid_cell (the cell size, which is larger than the one the tool asked for when the cap on the grid's size
- * applied), <tool> = normals, outliers, distances, smooth, components, fpfh, iss, m3c2_a and m3c2_b (the grids over the reference and
+ * applied), <tool> = normals, outliers, distances, smooth, scales, components, fpfh, iss, m3c2_a and m3c2_b (the grids over the reference and
  * the compared cloud), icp and gicp (the first, widest stage; the linearize seams: their one stage). */
 int plade_stats_get(plade_ctx *ctx, const char **names, const double **values, int32_t *count);
 /* ---- diagnostic: the device-wide stable radix sort every grid of the path is built with ----------------

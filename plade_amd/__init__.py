@@ -35,6 +35,7 @@ ABI_SYMBOLS = [
     "plade_subsample_default_params", "plade_subsample_spacing", "plade_cloud_subsample_dev",
     "plade_orient_default_params", "plade_orient_normals", "plade_cloud_orient_normals_dev",
     "plade_smooth_default_params", "plade_smooth_cloud", "plade_cloud_smooth_dev",
+    "plade_scale_default_params", "plade_cloud_scale_features", "plade_cloud_scale_normals_dev",
     "plade_gicp_default_params", "plade_refine_gicp", "plade_refine_gicp_dev", "plade_gicp_linearize",
     "plade_m3c2_default_params", "plade_cloud_m3c2", "plade_cloud_m3c2_dev",
     "plade_fpfh_default_params", "plade_cloud_fpfh", "plade_cloud_fpfh_dev", "plade_features_free",
@@ -164,6 +165,21 @@ class SmoothParams(C.Structure):
 class SmoothSummary(C.Structure):
     """plade_smooth_summary: n, fitted, rms and max of |displacement| over the fitted points, max_count (the largest neighbourhood)."""
     _fields_ = [("n", C.c_uint64), ("fitted", C.c_uint64), ("rms", C.c_double), ("max", C.c_double), ("max_count", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class ScaleParams(C.Structure):
+    """plade_scale_params: the radii (the first `scales` of eight, absolute, fp32 squares strictly ascending), min_neighbours of a
+    fitted scale (the point itself included), mode (0 the largest planarity, 1 the smallest surface variation), orient (0 toward the
+    viewpoint, 1 along the rows' own normals) and the viewpoint."""
+    _fields_ = [("radii", C.c_double * 8), ("scales", C.c_int32), ("min_neighbours", C.c_int32), ("mode", C.c_int32),
+                ("orient", C.c_int32), ("viewpoint", C.c_float * 3), ("reserved", C.c_int32)]
+
+
+class ScaleSummary(C.Structure):
+    """plade_scale_summary: queries, fitted (queries with a chosen scale), chosen_hist (queries per chosen scale), max_count (the
+    largest neighbourhood)."""
+    _fields_ = [("queries", C.c_uint64), ("fitted", C.c_uint64), ("chosen_hist", C.c_uint32 * 8), ("max_count", C.c_uint32),
                 ("reserved", C.c_uint32)]
 
 
@@ -326,6 +342,10 @@ def load_library(path=LIB_PATH):
     sig("plade_smooth_default_params", argtypes=[C.POINTER(SmoothParams)], restype=None)
     sig("plade_smooth_cloud", argtypes=[p, p, u32, u32, C.POINTER(SmoothParams), p, p, p, p, p, p, p, C.POINTER(SmoothSummary)])
     sig("plade_cloud_smooth_dev", argtypes=[p, p, C.POINTER(SmoothParams), i32, C.POINTER(p), C.POINTER(SmoothSummary)])
+    sig("plade_scale_default_params", argtypes=[C.POINTER(ScaleParams)], restype=None)
+    sig("plade_cloud_scale_features", argtypes=[p, p, u32, u32, p, u32, C.POINTER(ScaleParams), p, p, p, p, p, p, p, p,
+                                                C.POINTER(ScaleSummary)])
+    sig("plade_cloud_scale_normals_dev", argtypes=[p, p, p, u32, C.POINTER(ScaleParams), C.POINTER(p), C.POINTER(ScaleSummary)])
     sig("plade_m3c2_default_params", argtypes=[C.POINTER(M3c2Params)], restype=None)
     sig("plade_cloud_m3c2", argtypes=[p, p, u32, p, u32, u32, p, u32, u32, p, C.POINTER(M3c2Params), p, p, p, p, p, p,
                                       C.POINTER(M3c2Summary)])
@@ -435,6 +455,7 @@ _DEFAULTS = {Params: "plade_default_params",
              SubsampleParams: "plade_subsample_default_params",
              OrientParams: "plade_orient_default_params",
              SmoothParams: "plade_smooth_default_params",
+             ScaleParams: "plade_scale_default_params",
              M3c2Params: "plade_m3c2_default_params",
              FpfhParams: "plade_fpfh_default_params",
              FeatureMatchParams: "plade_feature_match_default_params",
@@ -575,6 +596,37 @@ def _smooth_params(radius, min_neighbours, viewpoint):
 
 def _smooth_info(summ):
     return {k: getattr(summ, k) for k, _ in SmoothSummary._fields_ if k != "reserved"}
+
+
+def scale_default_params():
+    """plade_scale_default_params (pure: needs no GPU) as a dict of the plade_scale_params fields."""
+    return _defaults_dict(ScaleParams)
+
+
+def _scale_params(radii, mode, min_neighbours, viewpoint, orient):
+    prm = _defaults(ScaleParams)
+    r = [float(x) for x in np.asarray(radii, np.float64).reshape(-1)]
+    prm.scales = len(r)              # (the library refuses a number outside 1 .. 8)
+    prm.radii[:] = (r + [0.0] * 8)[:8]
+    prm.mode, prm.orient = int(mode), int(orient)
+    if min_neighbours is not None:
+        prm.min_neighbours = int(min_neighbours)
+    prm.viewpoint[:] = [float(x) for x in _viewpoint(viewpoint)]
+    return prm
+
+
+def _scale_queries(query_index):
+    """(the list as a C-contiguous uint32 array or None, its length)"""
+    if query_index is None:
+        return None, 0
+    q = np.ascontiguousarray(query_index, dtype=np.uint32).reshape(-1)
+    return q, len(q)
+
+
+def _scale_info(summ, scales):
+    info = {k: getattr(summ, k) for k, _ in ScaleSummary._fields_ if k not in ("reserved", "chosen_hist")}
+    info["chosen_hist"] = tuple(summ.chosen_hist)[:max(0, min(scales, 8))]
+    return info
 
 
 def m3c2_default_params():
@@ -1476,6 +1528,55 @@ class Context:
         self._check(self.L.plade_cloud_smooth_dev(self.h, cloud.h, C.byref(prm), 1 if fit_normals else 0, C.byref(h), C.byref(summ)))
         out = Cloud(self, None, handle=(int(summ.n), h))
         return (out, _smooth_info(summ)) if info else out
+
+    # ---- multi-scale normals and dimensionality features ------------------------------------------------
+    def scale_features(self, points, radii, mode=0, min_neighbours=None, viewpoint=(0.0, 0.0, 0.0), orient=0, query_index=None,
+                       per_scale=True, moments=False):
+        """plade_cloud_scale_features: normals and dimensionality features of an (N, >= 3) float32 array (x y z first) at the S =
+        len(radii) <= 8 ascending `radii` in one walk, and per query the scale that is most planar (mode 0, M3C2's rule) or has the
+        smallest surface variation (mode 1).  The queries are all points, or `query_index` (strictly ascending indices; K = their
+        number).  orient 0: normals toward `viewpoint`; 1: along columns 3..5 of `points`, the viewpoint where those do not
+        decide.  Returns (normals, info): normals (K, 3) float32, the chosen scale's (NaN where no scale is fitted); info: a dict
+        with queries, fitted, chosen_hist (S numbers), max_count, chosen (K int32, -1: none), features (K, 4 float32: linearity,
+        planarity, sphericity, variation of the chosen scale) and -- with per_scale -- count (K, S uint32), fitted_mask (K, S
+        bools), eigenvalues (K, S, 3 float64: l1 >= l2 >= l3) and normals (K, S, 3 float32), with moments the (K, S, 9) float64
+        sums of q and q q^T."""
+        a, n, stride = _xyz_view(points)
+        prm = _scale_params(radii, mode, min_neighbours, viewpoint, orient)
+        q, k = _scale_queries(query_index)
+        K, S = (n if q is None else k), max(0, min(int(prm.scales), 8))
+        chosen = np.empty(K, np.int32)
+        nrm = np.empty((K, 3), np.float32)
+        feat = np.empty((K, 4), np.float32)
+        count = np.empty((K, S), np.uint32) if per_scale else None
+        fitted = np.zeros((K, S), np.uint8) if per_scale else None
+        eig = np.empty((K, S, 3), np.float64) if per_scale else None
+        nrms = np.empty((K, S, 3), np.float32) if per_scale else None
+        mom = np.empty((K, S, 9), np.float64) if moments else None
+        summ = ScaleSummary()
+        self._check(self.L.plade_cloud_scale_features(self.h, _ptr(a), n, stride, _ptr(q), k, C.byref(prm), _ptr(chosen), _ptr(nrm),
+                                                      _ptr(feat), _ptr(count), _ptr(fitted), _ptr(eig), _ptr(nrms), _ptr(mom),
+                                                      C.byref(summ)))
+        info = _scale_info(summ, S)
+        info.update(chosen=chosen, features=feat)
+        if per_scale:
+            info.update(count=count, fitted_mask=fitted.view(np.bool_), eigenvalues=eig, normals=nrms)
+        if moments:
+            info["moments"] = mom
+        return nrm, info
+
+    def scale_normals_dev(self, cloud, radii, mode=0, min_neighbours=None, viewpoint=(0.0, 0.0, 0.0), orient=0, query_index=None,
+                          info=False):
+        """plade_cloud_scale_normals_dev: scale_features on a resident cloud (upload, upload_xyz; orient 1 reads its normals) into
+        a new resident Cloud of the queries: x y z bit for bit and the chosen normal (NaN where no scale is fitted) -- the core
+        points m3c2_dev takes.  The rows are the bits of scale_features.  With info also the summary dict."""
+        prm = _scale_params(radii, mode, min_neighbours, viewpoint, orient)
+        q, k = _scale_queries(query_index)
+        summ = ScaleSummary()
+        h = C.c_void_p()
+        self._check(self.L.plade_cloud_scale_normals_dev(self.h, cloud.h, _ptr(q), k, C.byref(prm), C.byref(h), C.byref(summ)))
+        out = Cloud(self, None, handle=(int(summ.queries), h))
+        return (out, _scale_info(summ, int(prm.scales))) if info else out
 
     # ---- change detection: M3C2 distances -------------------------------------------------------------
     def _m3c2(self, call, m, radius, depth, T, min_points, reg_error, per_point, moments):

@@ -211,6 +211,32 @@ inline Parsed<SubsampleSwitch> parse_m3c2_core(const char *text) {
     return parse_spacing_seed(spec, text);
 }
 
+// <r_min>,<r_max>[,<scales>[,<mode>]] of PLADE_M3C2_NORMALS: S radii r_min + (r_max - r_min) * s / (S - 1) in fp64, which
+// plade_cloud_scale_features accepts only with strictly ascending fp32 squares; a value whose radii are not is rejected like one
+// that does not parse
+struct ScaleSwitch { bool on = false; int scales = 4, mode = 0; double radii[8] = {}; };
+inline Parsed<ScaleSwitch> parse_m3c2_normals(const char *text) {
+    static const Field f[] = {real(radius_sq32), real(radius_sq32), integer(2, 8), integer(0, 1)};
+    static const Spec spec = {"PLADE_M3C2_NORMALS", f, 4, 2,
+                              " is not <r_min>,<r_max>[,<scales>[,<mode>]] with 0 < r_min < r_max (the fp32 squares of the radii strictly"
+                              " ascending), scales in [2, 8] and mode 0 or 1; the core points keep their normals"};
+    Parsed<ScaleSwitch> p;
+    Value v[4] = {{}, {}, {0.0, p.value.scales}, {0.0, p.value.mode}};
+    if (!parse(spec, text, v, p.warning)) return p;
+    ScaleSwitch s;
+    s.on = true; s.scales = (int)v[2].i; s.mode = (int)v[3].i;
+    for (int t = 0; t < s.scales; ++t) {
+        s.radii[t] = v[0].r + (v[1].r - v[0].r) * t / (s.scales - 1);
+        const float r = (float)s.radii[t], q = t ? (float)s.radii[t - 1] : 0.f;
+        if (t && !(q * q < r * r)) {
+            p.warning = std::string("warning: ") + spec.name + "=" + text + spec.tail;
+            return p;
+        }
+    }
+    p.value = s;
+    return p;
+}
+
 // <radius>[,<mode>[,<inward>]] of PLADE_CONSISTENT_NORMALS: radius 0 = off; mode 0 = vote against the origin, 1 = extreme point along +z
 struct OrientSwitch { double radius = 0.0; int mode = 0, inward = 0; };
 inline Parsed<OrientSwitch> parse_consistent_normals(const char *text) {

@@ -161,6 +161,24 @@ struct CloudSmoothing {
 bool smooth_cloud(pcl::PointCloud<pcl::PointNormal>::Ptr cloud, pcl::PointCloud<pcl::PointNormal> &smoothed, double radius,
                   int min_neighbours = 6, bool use_fit_normals = false, CloudSmoothing *info = nullptr);
 
+/** Multi-scale normals (no counterpart in the reference): the fields of plade_scale_summary (include/plade_hip.h). */
+struct CloudScales {
+    uint64_t queries = 0, fitted = 0;   // points in, points with a chosen scale
+    uint32_t chosen_hist[8] = {};       // points per chosen scale
+    uint32_t max_count = 0;             // the largest neighbourhood
+};
+/** Normals at the most planar of several scales on the GPU (plade_cloud_scale_features, the normal-scale step of M3C2): every
+ *  point's neighbourhood is fitted at each of the 1 .. 8 ascending `radii` (absolute, in the cloud's units) in one walk, and the
+ *  point takes the normal of the scale with the largest planarity (mode 0) or the smallest surface variation (mode 1) among those
+ *  with at least min_neighbours points (itself included).  `with_normals` receives the points in their original order (it may be
+ *  *cloud) with these normals, NaN where no scale is fitted; they point toward the origin or, with orient_by_cloud_normals, to the
+ *  side of the cloud's own normals (toward the origin where those are zero, orthogonal or not finite).  false: invalid input or no
+ *  GPU; a message is printed and `with_normals` is unchanged.  The CLI gives the core points of PLADE_M3C2 such normals when
+ *  PLADE_M3C2_NORMALS=<r_min>,<r_max>[,<scales>[,<mode>]] is set, and prints one line. */
+bool multiscale_normals(pcl::PointCloud<pcl::PointNormal>::Ptr cloud, pcl::PointCloud<pcl::PointNormal> &with_normals,
+                        const std::vector<double> &radii, int mode = 0, int min_neighbours = 6, bool orient_by_cloud_normals = false,
+                        CloudScales *info = nullptr);
+
 /** Change detection (no counterpart in the reference): the fields of plade_m3c2_summary (include/plade_hip.h). */
 struct CloudComparison {
     uint64_t m = 0, valid = 0, significant = 0;   // core points, those with enough points of both clouds, those beyond the level of detection

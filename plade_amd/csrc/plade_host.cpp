@@ -43,7 +43,7 @@ void trace(const char *what) {
 // parser has to say about a rejected value goes to std::cerr, not to the calling thread's console.
 using cli_switches::GicpSwitch; using cli_switches::M3c2Switch; using cli_switches::FpfhSwitch; using cli_switches::FeatureRegisterSwitch;
 using cli_switches::KeypointSwitch; using cli_switches::OutlierSwitch; using cli_switches::ComponentSwitch; using cli_switches::SmoothSwitch;
-using cli_switches::SubsampleSwitch; using cli_switches::OrientSwitch;
+using cli_switches::SubsampleSwitch; using cli_switches::OrientSwitch; using cli_switches::ScaleSwitch;
 template <class S> S latched(const cli_switches::Parsed<S> &p) {
     if (!p.warning.empty()) std::cerr << p.warning << std::endl;
     return p.value;
@@ -309,14 +309,15 @@ const SubsampleSwitch &subsample_switch() {
     return sw;
 }
 // the rows of an x y z nx ny nz array that the subsample keeps (the normal columns, NaN included, keep their bits): into `out`,
-// which may be `rows` itself
-bool subsample_packed(plade_ctx *ctx, const float *rows, size_t n, double spacing, uint64_t seed, float *out, plade_subsample_summary &s) {
+// which may be `rows` itself; kept_index: their ascending indices (n words) when wanted
+bool subsample_packed(plade_ctx *ctx, const float *rows, size_t n, double spacing, uint64_t seed, float *out, plade_subsample_summary &s,
+                      uint32_t *kept_index = nullptr) {
     plade_subsample_params prm;
     plade_subsample_default_params(&prm);
     prm.spacing = spacing; prm.seed = seed;
     trace("subsample: thinning");
     // (in place: the upload of the rows precedes the read-back of the kept ones on the context's stream)
-    const int rc = plade_subsample_spacing(ctx, rows, (uint32_t)n, 6, &prm, nullptr, nullptr, out, nullptr, &s);
+    const int rc = plade_subsample_spacing(ctx, rows, (uint32_t)n, 6, &prm, nullptr, kept_index, out, nullptr, &s);
     trace("subsample: done");
     if (rc != PLADE_OK) {
         con_err() << "subsampling failed: " << plade_last_error(ctx) << std::endl;
@@ -374,18 +375,68 @@ const SubsampleSwitch &m3c2_core_switch() {
     static const SubsampleSwitch sw = latched(cli_switches::parse_m3c2_core(getenv("PLADE_M3C2_CORE")));
     return sw;
 }
+// PLADE_M3C2_NORMALS=<r_min>,<r_max>[,<scales>[,<mode>]] (opt-in; absolute, in the clouds' units; it acts only together with PLADE_M3C2):
+// the core points of the comparison -- the whole target, or the PLADE_M3C2_CORE subsample -- get their normals from the multi-scale
+// estimate on the target (plade_cloud_scale_features at the core points' indices: `scales` radii from r_min to r_max in equal steps,
+// 2 .. 8, 4 when not given; mode 0 = the most planar scale, M3C2's rule, 1 = the smallest surface variation; orient = 1, so a new
+// normal points to the side of the file's normal), instead of the target file's normals; a core point with no fitted scale carries a
+// NaN normal, which M3C2 reports as "no axis".  One console line before the m3c2 line.  A value that does not parse (a radius not
+// positive and finite or its fp32 square below FLT_MIN, r_min >= r_max or steps so small that the fp32 squares of the radii do not
+// ascend strictly, scales not an integer in [2, 8], mode not 0 or 1, anything behind them) prints one warning and the core points
+// keep their normals; unset, nothing changes.
+const ScaleSwitch &m3c2_normals_switch() {
+    static const ScaleSwitch sw = latched(cli_switches::parse_m3c2_normals(getenv("PLADE_M3C2_NORMALS")));
+    return sw;
+}
+// the multi-scale normals of the packed rows at `query` (k ascending indices; nullptr: all n points) into nrm (3 floats per query);
+// orient_by_rows: a normal keeps the side of its row's own.  false: a message has been printed
+bool scale_normals_packed(plade_ctx *ctx, const float *rows, size_t n, const uint32_t *query, size_t k, const double *radii, int scales,
+                          int mode, int min_neighbours, bool orient_by_rows, float *nrm, plade_scale_summary &s) {
+    plade_scale_params prm;
+    plade_scale_default_params(&prm);
+    prm.scales = scales;
+    for (int t = 0; t < scales && t < 8; ++t) prm.radii[t] = radii[t];
+    prm.mode = mode; prm.min_neighbours = min_neighbours; prm.orient = orient_by_rows ? 1 : 0;
+    trace("scales: fitting");
+    const int rc = plade_cloud_scale_features(ctx, rows, (uint32_t)n, 6, query, (uint32_t)k, &prm, nullptr, nrm, nullptr, nullptr, nullptr,
+                                              nullptr, nullptr, nullptr, &s);
+    trace("scales: done");
+    if (rc != PLADE_OK) {
+        con_err() << "multi-scale normals failed: " << plade_last_error(ctx) << std::endl;
+        return false;
+    }
+    return true;
+}
 void m3c2_line(plade_ctx *ctx, const float *T16, const float *tg, size_t n_t, const float *sr, size_t n_s) {
     const M3c2Switch &sw = m3c2_switch();
     if (!sw.on) return;
     const SubsampleSwitch &cs = m3c2_core_switch();
+    const ScaleSwitch &ns = m3c2_normals_switch();
     std::vector<float> core;
+    std::vector<uint32_t> kept;
     const float *cp = tg;
     size_t m = n_t;
     if (cs.spacing > 0.0 && n_t) {
         core.resize(n_t * 6);
+        if (ns.on) kept.resize(n_t);
         plade_subsample_summary ss;
-        if (!subsample_packed(ctx, tg, n_t, cs.spacing, cs.seed, core.data(), ss)) return;
+        if (!subsample_packed(ctx, tg, n_t, cs.spacing, cs.seed, core.data(), ss, ns.on ? kept.data() : nullptr)) return;
         cp = core.data(); m = ss.kept;
+    }
+    if (ns.on && m) {
+        if (core.empty()) core.assign(tg, tg + n_t * 6);
+        std::vector<float> nrm(m * 3);
+        plade_scale_summary qs;
+        if (!scale_normals_packed(ctx, tg, n_t, kept.empty() ? nullptr : kept.data(), m, ns.radii, ns.scales, ns.mode, 6, true, nrm.data(), qs))
+            return;
+        for (size_t i = 0; i < m; ++i) memcpy(&core[6 * i + 3], &nrm[3 * i], 12);
+        cp = core.data();
+        std::string hist;
+        for (int t = 0; t < ns.scales; ++t) hist += " " + std::to_string(qs.chosen_hist[t]);
+        char b[280];
+        snprintf(b, sizeof(b), "m3c2 normals: %llu of %llu core points fitted (scales%s; largest neighbourhood %u)",
+                 (unsigned long long)qs.fitted, (unsigned long long)qs.queries, hist.c_str(), qs.max_count);
+        con_out() << b << std::endl;
     }
     plade_m3c2_summary s;
     if (!m3c2_packed(ctx, T16, cp, m, tg, n_t, sr, n_s, sw.radius, sw.depth, sw.min_points, sw.reg_error, nullptr, s)) return;
@@ -1175,6 +1226,32 @@ bool smooth_cloud(pcl::PointCloud<pcl::PointNormal>::Ptr cloud, pcl::PointCloud<
         smoothed.at(i) = pcl::PointNormal(p[0], p[1], p[2], q[0], q[1], q[2]);
     }
     if (info) { info->n = s.n; info->fitted = s.fitted; info->rms = s.rms; info->max = s.max; info->max_count = s.max_count; }
+    return true;
+}
+
+// multi-scale normals: see plade.h
+bool multiscale_normals(pcl::PointCloud<pcl::PointNormal>::Ptr cloud, pcl::PointCloud<pcl::PointNormal> &with_normals,
+                        const std::vector<double> &radii, int mode, int min_neighbours, bool orient_by_cloud_normals, CloudScales *info) {
+    plade_ctx *ctx = context();
+    if (!ctx) return false;
+    if (!cloud) { con_err() << "multiscale_normals: null cloud" << std::endl; return false; }
+    const std::vector<float> buf = flatten(*cloud);
+    const size_t n = buf.size() / 6;
+    std::vector<float> nrm(n * 3);
+    plade_scale_summary s;
+    // (more than eight radii: the count goes through as it is and the library refuses it)
+    if (!scale_normals_packed(ctx, buf.data(), n, nullptr, n, radii.data(), (int)std::min<size_t>(radii.size(), 9), mode, min_neighbours,
+                              orient_by_cloud_normals, nrm.data(), s))
+        return false;
+    with_normals.resize(n);
+    for (size_t i = 0; i < n; ++i) {
+        const float *p = &buf[6 * i], *q = &nrm[3 * i];
+        with_normals.at(i) = pcl::PointNormal(p[0], p[1], p[2], q[0], q[1], q[2]);
+    }
+    if (info) {
+        info->queries = s.queries; info->fitted = s.fitted; info->max_count = s.max_count;
+        for (int t = 0; t < 8; ++t) info->chosen_hist[t] = s.chosen_hist[t];
+    }
     return true;
 }
 

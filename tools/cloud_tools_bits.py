@@ -2,13 +2,16 @@
 
 Normals, the outlier filter (both modes), the components (with and without keep_largest), the subsample, the consistent
 orientation (both modes), the smoothing, the distances, M3C2, FPFH and its match, the ISS keypoints, the merge (fused and
-concatenated), the two ICP linearisations and the resident forms that return a cloud (each downloaded), each on
+concatenated), the two ICP linearisations, the resident forms that return a cloud (each downloaded) and the multi-scale normals, each on
 tests/golden/g9_room.npz and on a seeded synthetic sheet: one line per call with a sha1 of every returned array and every summary
 field (floats in hex).  One process per library:
 
     python tools/cloud_tools_bits.py path/to/parent/libplade_hip.so > old.txt
     python tools/cloud_tools_bits.py plade_amd/libplade_hip.so      > new.txt
     cmp old.txt new.txt && sha1sum new.txt
+
+A tool that only the newer build has adds lines (the multi-scale normals: `scales_*`, at the end of each block); run the older build
+from its own checkout and compare the lines both print.
 """
 import hashlib
 import os
@@ -95,6 +98,11 @@ def run(ctx, name, tgt, src, T, r):
     resident("upload_xyz", ctx.upload_xyz(xyz, k=16))
     resident("merge_fused_dev", ctx.merge_clouds_dev([ct, cs], [None, T], leaf=r, info=True))
     resident("merge_cat_dev", ctx.merge_clouds_dev([ct, cs], [None, T], leaf=0.0, info=True))
+    # (the multi-scale normals come last: the lines above keep their place and their sha1 from build to build)
+    rs = (0.7 * r, r, 1.5 * r)
+    line("scales_planarity", ctx.scale_features(tgt, rs, mode=0, moments=True))
+    line("scales_variation_own_normals", ctx.scale_features(tgt, rs, mode=1, orient=1, query_index=np.arange(0, len(tgt), 3), moments=True))
+    resident("scales_dev", ctx.scale_normals_dev(ct, rs, orient=1, info=True))
     ct.free()
     cs.free()
     return out

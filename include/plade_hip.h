@@ -615,6 +615,56 @@ int plade_label_components(plade_ctx *ctx, const float *rows, uint32_t n, uint32
 int plade_cloud_filter_components_dev(plade_ctx *ctx, plade_cloud *cloud, const plade_component_params *params, plade_cloud **out,
                                       int32_t *label_out, uint32_t *kept_index_out, plade_component_summary *summary);
 
+/* ---- DBSCAN: clustering by density, where one thin thread of stray points must not join two objects and isolated points must stay
+ * noise (no reference counterpart; Open3D ships it as cluster_dbscan, scikit-learn as DBSCAN) ---------------------------------------
+ * Semantics (plade_amd/csrc/dbscan.h).  Input: n >= 1 points, rows of `stride` >= 3 floats, x y z first, all
+ * coordinates finite.  d(i, j) = the fp32 FLANN L2 of (p_i, p_j), ((dx*dx + dy*dy) + dz*dz); r2 = (float)radius * (float)radius.
+ *   count        count(i) = |{ j : d(i, j) < r2 }| (strict `<`), the point itself included (Open3D's and scikit-learn's convention);
+ *                i is a core point iff count(i) >= min_points.
+ *   clusters     the connected components of the graph on the core points alone (i ~ j iff both are core and d(i, j) < r2), an
+ *                exact set; ids 0 .. C - 1 in ascending order of the cluster's smallest core index.
+ *   border       a non-core point with at least one core point closer than radius; it takes the label of the core neighbour j with
+ *                the smallest pair (d(i, j), j).  (Textbook DBSCAN leaves that to the visiting order.)  A border point never
+ *                connects two clusters.
+ *   noise        everything else: label -1.
+ *   selection    on the sizes (core and border members) exactly as plade_label_components selects: min_size, max_size,
+ *                keep_largest; noise is never kept.
+ *   output       each array may be NULL.  label_out: n int32; kind_out: n bytes, 0 noise / 1 border / 2 core; size_out: the C sizes
+ *                (room for n); keep_out: n bytes 0 / 1; kept_index_out: the kept original indices, ascending (room for n);
+ *                rows_out: the kept rows in that order, every float copied bit for bit (room for n rows; may be `rows` itself);
+ *                summary: n, clusters = C, core, border, noise, kept_clusters, kept, largest = the largest size.  The result
+ *                depends on the point set and the parameters only, and is the same bits on every run.  With min_points = 1 every
+ *                point is core, and label, size, keep, kept_index and the rows are those of plade_label_components bit for bit.
+ * Errors: PLADE_EINVAL for n = 0, stride < 3, a NULL cloud, a non-finite coordinate, radius <= 0 or not finite (or its fp32 square
+ * not finite or below FLT_MIN: a point must be its own neighbour), min_points < 1, min_size < 1, max_size in (0, min_size),
+ * keep_largest < 0; the outputs are untouched and the context stays usable.  All noise, or a selection that keeps nothing, is
+ * PLADE_OK with kept = 0.  The grid is the components': a radius that is tiny against the cloud's extent is not refused (see there).
+ * plade_stats_get then reports dbscan_grid_s, dbscan_core_s (the counting walk), dbscan_link_s (the union-find over the core-core
+ * edges and the border rule), dbscan_label_s (roots, ids, sizes, selection), dbscan_compact_s (scan, kept list and row gather; HIP
+ * events on the context's stream), dbscan_clusters and dbscan_kept. */
+typedef struct plade_dbscan_params {
+    double radius;               /* must be set (> 0): there is no automatic value */
+    int32_t min_points;          /* >= 1: the neighbours (itself included) that make a point a core point; 4 */
+    int32_t min_size;            /* >= 1 */
+    int32_t max_size;            /* 0: no upper bound, else >= min_size */
+    int32_t keep_largest;        /* 0: every passing cluster, m > 0: the m largest passing ones */
+} plade_dbscan_params;
+typedef struct plade_dbscan_summary {
+    uint64_t n, clusters, core, border, noise, kept_clusters, kept;
+    uint32_t largest;
+    uint32_t reserved;           /* 0 */
+} plade_dbscan_summary;
+/* The defaults: radius = 0 (unset), min_points = 4, min_size = 1, max_size = 0, keep_largest = 0.  Needs no GPU. */
+void plade_dbscan_default_params(plade_dbscan_params *p);
+int plade_cluster_dbscan(plade_ctx *ctx, const float *rows, uint32_t n, uint32_t stride, const plade_dbscan_params *params,
+                         int32_t *label_out, uint8_t *kind_out, uint32_t *size_out, uint8_t *keep_out, uint32_t *kept_index_out,
+                         float *rows_out, plade_dbscan_summary *summary);
+/* The same on a resident cloud (rows x y z nx ny nz) into a NEW resident cloud of the kept points: the point data makes no host round
+ * trip.  The same label, kind, kept_index and summary bits as plade_cluster_dbscan on the cloud's rows.  PLADE_EFAIL (summary
+ * filled, *out NULL) when nothing is kept: a resident cloud has no empty form.  Free both clouds with plade_cloud_free. */
+int plade_cloud_cluster_dbscan_dev(plade_ctx *ctx, plade_cloud *cloud, const plade_dbscan_params *params, plade_cloud **out,
+                                   int32_t *label_out, uint8_t *kind_out, uint32_t *kept_index_out, plade_dbscan_summary *summary);
+
 /* ---- subsampling to a minimum point spacing: a subset of the cloud's OWN points (no reference counterpart; CloudCompare ships it
  * as "Subsample -> Space" and takes M3C2's core points from it) ------------------------------------------------------------------
  * Semantics (plade_amd/csrc/subsample.h).  Input: n >= 1 points, rows of `stride` >= 3 floats, x y z first,
@@ -1170,7 +1220,7 @@ int plade_dump_get(plade_ctx *ctx, const char *name, const void **ptr, int64_t *
  * names is a ';'-separated list, values has one double per name.
  * The cloud tools that search a point grid also report the grid of their last call: <tool>_grid_dx, _grid_dy, _grid_dz (cells per
  * axis) and <tool>_grid_cell (the cell size, which is larger than the one the tool asked for when the cap on the grid's size
- * applied), <tool> = normals, outliers, distances, smooth, scales, components, fpfh, iss, m3c2_a and m3c2_b (the grids over the reference and
+ * applied), <tool> = normals, outliers, distances, smooth, scales, components, dbscan, fpfh, iss, m3c2_a and m3c2_b (the grids over the reference and
  * the compared cloud), icp and gicp (the first, widest stage; the linearize seams: their one stage). */
 int plade_stats_get(plade_ctx *ctx, const char **names, const double **values, int32_t *count);
 /* ---- diagnostic: the device-wide stable radix sort every grid of the path is built with ----------------

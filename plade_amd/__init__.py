@@ -45,6 +45,7 @@ ABI_SYMBOLS = [
     "plade_iss_default_params", "plade_cloud_keypoints_iss", "plade_cloud_keypoints_iss_dev", "plade_features_select",
     "plade_register_keypoints", "plade_register_keypoints_dev",
     "plade_penetration_filter",
+    "plade_dbscan_default_params", "plade_cluster_dbscan", "plade_cloud_cluster_dbscan_dev",
 ]
 
 # plade_pen_item (include/plade_hip.h): one audited item of the penetration filter
@@ -121,6 +122,19 @@ class ComponentParams(C.Structure):
     passing component)."""
     _fields_ = [("radius", C.c_double), ("min_size", C.c_int32), ("max_size", C.c_int32), ("keep_largest", C.c_int32),
                 ("reserved", C.c_int32)]
+
+
+class DbscanParams(C.Structure):
+    """plade_dbscan_params: radius of the neighbourhood, min_points (itself included) of a core point, min_size / max_size (0: no
+    bound) of a passing cluster, keep_largest (0: every passing cluster)."""
+    _fields_ = [("radius", C.c_double), ("min_points", C.c_int32), ("min_size", C.c_int32), ("max_size", C.c_int32),
+                ("keep_largest", C.c_int32)]
+
+
+class DbscanSummary(C.Structure):
+    """plade_dbscan_summary: n, clusters, core, border, noise (points), kept_clusters, kept (points), largest (size)."""
+    _fields_ = [("n", C.c_uint64), ("clusters", C.c_uint64), ("core", C.c_uint64), ("border", C.c_uint64), ("noise", C.c_uint64),
+                ("kept_clusters", C.c_uint64), ("kept", C.c_uint64), ("largest", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class ComponentSummary(C.Structure):
@@ -333,6 +347,9 @@ def load_library(path=LIB_PATH):
     sig("plade_component_default_params", argtypes=[C.POINTER(ComponentParams)], restype=None)
     sig("plade_label_components", argtypes=[p, p, u32, u32, C.POINTER(ComponentParams), p, p, p, p, p, C.POINTER(ComponentSummary)])
     sig("plade_cloud_filter_components_dev", argtypes=[p, p, C.POINTER(ComponentParams), C.POINTER(p), p, p, C.POINTER(ComponentSummary)])
+    sig("plade_dbscan_default_params", argtypes=[C.POINTER(DbscanParams)], restype=None)
+    sig("plade_cluster_dbscan", argtypes=[p, p, u32, u32, C.POINTER(DbscanParams), p, p, p, p, p, p, C.POINTER(DbscanSummary)])
+    sig("plade_cloud_cluster_dbscan_dev", argtypes=[p, p, C.POINTER(DbscanParams), C.POINTER(p), p, p, p, C.POINTER(DbscanSummary)])
     sig("plade_subsample_default_params", argtypes=[C.POINTER(SubsampleParams)], restype=None)
     sig("plade_subsample_spacing", argtypes=[p, p, u32, u32, C.POINTER(SubsampleParams), p, p, p, p, C.POINTER(SubsampleSummary)])
     sig("plade_cloud_subsample_dev", argtypes=[p, p, C.POINTER(SubsampleParams), C.POINTER(p), p, p, C.POINTER(SubsampleSummary)])
@@ -452,6 +469,7 @@ _DEFAULTS = {Params: "plade_default_params",
              IcpParams: "plade_icp_default_params",
              OutlierParams: "plade_outlier_default_params",
              ComponentParams: "plade_component_default_params",
+             DbscanParams: "plade_dbscan_default_params",
              SubsampleParams: "plade_subsample_default_params",
              OrientParams: "plade_orient_default_params",
              SmoothParams: "plade_smooth_default_params",
@@ -531,6 +549,29 @@ def _component_info(summ, label, size, keep):
     info["label"] = label
     if size is not None:
         info["size"] = size[:summ.components].copy()
+    if keep is not None:
+        info["keep"] = keep.view(np.bool_)
+    return info
+
+
+def dbscan_default_params():
+    """plade_dbscan_default_params (pure: needs no GPU) as a dict of the plade_dbscan_params fields."""
+    return _defaults_dict(DbscanParams)
+
+
+def _dbscan_params(radius, min_points, min_size, max_size, keep_largest):
+    prm = _defaults(DbscanParams)
+    prm.radius = float(radius)
+    prm.min_points, prm.min_size, prm.max_size, prm.keep_largest = int(min_points), int(min_size), int(max_size), int(keep_largest)
+    return prm
+
+
+def _dbscan_info(summ, label, kind, size, keep):
+    info = {k: getattr(summ, k) for k, _ in DbscanSummary._fields_ if k != "reserved"}
+    info["label"] = label
+    info["kind"] = kind
+    if size is not None:
+        info["size"] = size[:summ.clusters].copy()
     if keep is not None:
         info["keep"] = keep.view(np.bool_)
     return info
@@ -1416,6 +1457,45 @@ class Context:
                                                              C.byref(summ)))
         out = Cloud(self, None, handle=(int(summ.kept), h))
         return (out, kept[:summ.kept].copy(), _component_info(summ, label, None, None)) if info else out
+
+    # ---- DBSCAN ----------------------------------------------------------------------------------
+    def dbscan(self, points, radius, min_points=4, min_size=1, max_size=0, keep_largest=0):
+        """plade_cluster_dbscan: the DBSCAN clusters of an (N, >= 3) float32 array whose first three columns are x y z.  A point
+        with at least min_points points closer than radius (fp32 squared distance, strict <, itself included) is a core point; the
+        clusters are the connected components of the core points; a non-core point with a core point closer than radius is a
+        border point and joins the cluster of the core neighbour with the smallest (distance, index); the rest is noise.  The
+        clusters are selected by size like connected_components' (min_size, max_size, keep_largest).  Returns (filtered,
+        kept_index, info): the kept rows in their original order with every column copied bit for bit, their original indices
+        (uint32, ascending), and a dict with n, clusters, core, border, noise, kept_clusters, kept, largest, label (N int32: ids in
+        ascending order of a cluster's smallest core index, -1 noise), kind (N uint8: 0 noise, 1 border, 2 core), size (clusters
+        uint32) and keep (N bools)."""
+        a, n, stride = _xyz_view(points)
+        prm = _dbscan_params(radius, min_points, min_size, max_size, keep_largest)
+        label = np.empty(n, np.int32)
+        kind = np.empty(n, np.uint8)
+        size = np.empty(n, np.uint32)
+        keep = np.zeros(n, np.uint8)
+        kept = np.empty(n, np.uint32)
+        rows = np.empty((n, stride), np.float32)
+        summ = DbscanSummary()
+        self._check(self.L.plade_cluster_dbscan(self.h, _ptr(a), n, stride, C.byref(prm), _ptr(label), _ptr(kind), _ptr(size), _ptr(keep),
+                                                _ptr(kept), _ptr(rows), C.byref(summ)))
+        return rows[:summ.kept].copy(), kept[:summ.kept].copy(), _dbscan_info(summ, label, kind, size, keep)
+
+    def dbscan_dev(self, cloud, radius, min_points=4, min_size=1, max_size=0, keep_largest=0, info=False):
+        """plade_cloud_cluster_dbscan_dev: dbscan on a resident cloud (upload, upload_xyz) into a new resident Cloud of the kept
+        points; the point data makes no host round trip.  With info also (kept_index, info dict): the same bits as dbscan gives
+        (label and kind, no size and keep arrays).  Raises PladeError (PLADE_EFAIL) when nothing is kept."""
+        prm = _dbscan_params(radius, min_points, min_size, max_size, keep_largest)
+        label = np.empty(cloud.n, np.int32) if info else None
+        kind = np.empty(cloud.n, np.uint8) if info else None
+        kept = np.empty(cloud.n, np.uint32) if info else None
+        summ = DbscanSummary()
+        h = C.c_void_p()
+        self._check(self.L.plade_cloud_cluster_dbscan_dev(self.h, cloud.h, C.byref(prm), C.byref(h), _ptr(label), _ptr(kind), _ptr(kept),
+                                                          C.byref(summ)))
+        out = Cloud(self, None, handle=(int(summ.kept), h))
+        return (out, kept[:summ.kept].copy(), _dbscan_info(summ, label, kind, None, None)) if info else out
 
     # ---- subsampling to a minimum spacing ---------------------------------------------------------
     def subsample(self, points, spacing, seed=0, per_point=True):

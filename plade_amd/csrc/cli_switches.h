@@ -179,6 +179,35 @@ inline Parsed<ComponentSwitch> parse_keep_components(const char *text) {
     return p;
 }
 
+// <radius>,<min_points>[,<min_size>[,<keep_largest>]] of PLADE_DBSCAN and <radius>[,<min_points>[,<min_size>]] of PLADE_M3C2_CLUSTERS
+struct DbscanSwitch { bool on = false; double radius = 0.0; int min_points = 4, min_size = 1, keep_largest = 0; };
+inline Parsed<DbscanSwitch> parse_dbscan(const char *text) {
+    static const Field f[] = {real(radius_sq32), integer(1), integer(1), integer(0)};
+    static const Spec spec = {"PLADE_DBSCAN", f, 4, 2,
+                              " is not <radius>,<min_points>[,<min_size>[,<keep_largest>]] with radius > 0 (its square not below FLT_MIN),"
+                              " min_points >= 1, min_size >= 1 and keep_largest >= 0; no clustering"};
+    Parsed<DbscanSwitch> p;
+    Value v[4] = {{}, {0.0, p.value.min_points}, {0.0, p.value.min_size}, {0.0, p.value.keep_largest}};
+    if (parse(spec, text, v, p.warning)) {
+        DbscanSwitch &s = p.value;
+        s.on = true; s.radius = v[0].r; s.min_points = (int)v[1].i; s.min_size = (int)v[2].i; s.keep_largest = (int)v[3].i;
+    }
+    return p;
+}
+inline Parsed<DbscanSwitch> parse_m3c2_clusters(const char *text) {
+    static const Field f[] = {real(radius_sq32), integer(1), integer(1)};
+    static const Spec spec = {"PLADE_M3C2_CLUSTERS", f, 3, 1,
+                              " is not <radius>[,<min_points>[,<min_size>]] with radius > 0 (its square not below FLT_MIN), min_points >= 1"
+                              " and min_size >= 1; no clusters of change"};
+    Parsed<DbscanSwitch> p;
+    Value v[3] = {{}, {0.0, p.value.min_points}, {0.0, p.value.min_size}};
+    if (parse(spec, text, v, p.warning)) {
+        DbscanSwitch &s = p.value;
+        s.on = true; s.radius = v[0].r; s.min_points = (int)v[1].i; s.min_size = (int)v[2].i;
+    }
+    return p;
+}
+
 struct SmoothSwitch { double radius = 0.0; int min_neighbours = 6; };
 inline Parsed<SmoothSwitch> parse_smooth(const char *text) {
     static const Field f[] = {real(smooth_radius), integer(3)};

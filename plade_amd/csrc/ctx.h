@@ -103,12 +103,14 @@ struct plade_ctx {
     plade::WorkSlot normals_work, icp_work, dist_work, outlier_work, merge_work, component_work, smooth_work, gicp_work, m3c2_work,
         fpfh_work, corr_pose_work, iss_work, subsample_work, orient_work;
     plade::WorkSlot scales_work;   // k_scales.hip (a statement of its own: the list above is pinned by tests/test_work_slot_host.py)
+    plade::WorkSlot dbscan_work;   // k_dbscan.hip (likewise)
     // the work structs' destructors call HIP (DBuf, EventSpans): plade_ctx_destroy runs this with the device set, before the stream goes
     void reset_tool_work() {
         for (plade::WorkSlot *s : {&normals_work, &icp_work, &dist_work, &outlier_work, &merge_work, &component_work, &smooth_work,
                                    &gicp_work, &m3c2_work, &fpfh_work, &corr_pose_work, &iss_work, &subsample_work, &orient_work})
             s->reset();
         scales_work.reset();   // not in the list above, which a test pins; reset here all the same, so that it goes before the stream
+        dbscan_work.reset();
     }
     plade_ctx *peers[PLADE_GROUP_MAX - 1] = {};   // the contexts of pairs 1.. of a group (plade_registration_pairs): stream, aux, work areas
     hipEvent_t ev_group = nullptr;   // end of a group's joint plane extraction on `stream` (the peers' streams wait for it)

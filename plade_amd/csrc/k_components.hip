@@ -5,19 +5,17 @@
 //            section 10): the 27-cell block around a point holds everything closer than r.
 //   link     k_cc_link: one lane per point in the grid's sorted order walks the nine runs of its block and tests only the
 //            candidates at a smaller sorted position, so every undirected edge is tested once.  An edge unites the two original
-//            indices in parent[] (uint32 by original index, parent[i] = i at the start) by lock-free min-hooking: find both roots,
-//            atomicMin(&parent[hi], lo) at agent scope with hi > lo; a returned value other than hi means somebody hooked hi first,
-//            and the union goes on with (that value, lo).  Parents only ever decrease: every loop ends, no lane waits for another,
-//            and at the end every root is the smallest original index of its component -- whatever the order of the unions.
-//            parent[] is read with relaxed agent-scope atomic loads; a stale value costs a round, never a link, because the
-//            atomicMin's return value decides.
+//            indices in parent[] by the lock-free min-hooking of cluster_tail.h (unite): no lane waits for another, and at the end
+//            every root is the smallest original index of its component -- whatever the order of the unions.
+// The tail (cluster_label_select of cluster_tail.h, which k_dbscan.hip runs too; its kernels are here, once):
 //   flatten  k_cc_flatten (next launch): root[i] by walking up, flags[i] = (root[i] == i).  compact_flags over the flags gives C and,
 //            by its exclusive positions, the id of every root: ascending root = ascending smallest index.
 //   label    k_cc_label_size: label[i] = id[root[i]]; the sizes by integer atomics, one per distinct id of a wavefront.
 //   select   k_cc_pass; with keep_largest the keys ~size << 32 | id (all ones in the high word: does not pass) through the stable
 //            sort_pairs_u64 and k_cc_mark_first; k_cc_summary (largest, kept components); k_cc_keep, compact_flags, gather_rows (prims.h).
+// For DBSCAN a point may have no root (noise: NO_POINT, label -1); the components never meet that case.
 #include "components.h"
-#include "cloud_tool.h"
+#include "cluster_tail.h"
 #include "grid_walk.h"
 #include "voxel.h"
 
@@ -34,23 +32,6 @@ struct LinkArgs {
     float r2;                        // (float)r * (float)r
     uint32_t *parent;                // by original index
 };
-
-__device__ __forceinline__ uint32_t parent_of(const uint32_t *parent, uint32_t x) {
-    return __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// a, b: any two ancestors (or the points themselves) of the two ends
-__device__ __forceinline__ void unite(uint32_t *parent, uint32_t a, uint32_t b) {
-    for (;;) {
-        for (uint32_t p = parent_of(parent, a); p != a; p = parent_of(parent, a)) a = p;
-        for (uint32_t p = parent_of(parent, b); p != b; p = parent_of(parent, b)) b = p;
-        if (a == b) return;
-        const uint32_t hi = max(a, b), lo = min(a, b);
-        const uint32_t old = __hip_atomic_fetch_min(parent + hi, lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (old == hi) return;
-        a = old; b = lo;             // hi had been hooked to `old` already (parent[hi] is now min(old, lo)): old and lo remain to be united
-    }
-}
 
 __global__ __launch_bounds__(ROW_TPB) void k_cc_init(uint32_t *__restrict__ parent, uint32_t n) {
     const uint32_t i = blockIdx.x * ROW_TPB + threadIdx.x;
@@ -78,25 +59,29 @@ __global__ __launch_bounds__(LINK_TPB) void k_cc_link(const LinkArgs a) {
     });
 }
 
-__global__ __launch_bounds__(ROW_TPB) void k_cc_flatten(const uint32_t *__restrict__ parent, uint32_t n, uint32_t *__restrict__ root,
-                                                        uint32_t *__restrict__ flags) {
+// root[i] by walking up from i, or from attach[i] where that is given (NO_POINT: no root); flags[i] = i is a root
+__global__ __launch_bounds__(ROW_TPB) void k_cc_flatten(const uint32_t *__restrict__ parent, const uint32_t *__restrict__ attach, uint32_t n,
+                                                        uint32_t *__restrict__ root, uint32_t *__restrict__ flags) {
     const uint32_t i = blockIdx.x * ROW_TPB + threadIdx.x;
     if (i >= n) return;
-    uint32_t x = i;
-    for (uint32_t p = parent[x]; p != x; p = parent[x]) x = p;
+    uint32_t x = attach ? attach[i] : i;
+    if (x != NO_POINT)
+        for (uint32_t p = parent[x]; p != x; p = parent[x]) x = p;
     root[i] = x;
     flags[i] = x == i ? 1u : 0u;
 }
 
 // label[i] = id[root[i]]; size[id] += 1, one atomic per distinct id of the wavefront (a room-sized component would otherwise put
-// every point's atomic on one address).  Integer sums: the same in any order
+// every point's atomic on one address).  Integer sums: the same in any order.  A point without a root: label -1, in no size
 __global__ __launch_bounds__(ROW_TPB) void k_cc_label_size(const uint32_t *__restrict__ root, const uint32_t *__restrict__ id, uint32_t n,
                                                            int32_t *__restrict__ label, uint32_t *__restrict__ size) {
     const uint32_t i = blockIdx.x * ROW_TPB + threadIdx.x, lane = threadIdx.x & 63u;
-    const bool valid = i < n;
+    bool valid = i < n;
     uint32_t c = 0;
     if (valid) {
-        c = id[root[i]];
+        const uint32_t r = root[i];
+        valid = r != NO_POINT;
+        c = valid ? id[r] : NO_POINT;
         label[i] = (int32_t)c;
     }
     u64 todo = __ballot(valid);
@@ -150,23 +135,55 @@ __global__ __launch_bounds__(ROW_TPB) void k_cc_keep(const int32_t *__restrict__
                                                      uint8_t *__restrict__ keep, uint32_t *__restrict__ flags) {
     const uint32_t i = blockIdx.x * ROW_TPB + threadIdx.x;
     if (i >= n) return;
-    const uint32_t k = kept[label[i]] ? 1u : 0u;
+    const int32_t c = label[i];
+    const uint32_t k = c >= 0 && kept[c] ? 1u : 0u;
     keep[i] = (uint8_t)k;
     flags[i] = k;
 }
 
 }  // namespace
 
-struct ComponentWork : KeepWork {
+struct ComponentWork : ClusterWork {
     TargetGrid grid;
-    DBuf<uint32_t> parent, root, root_pos, root_list, size, count, sort_val, sort_val2;
-    DBuf<unsigned long long> sort_key, sort_key2;
-    DBuf<int32_t> label;
-    DBuf<uint8_t> comp_kept;
+    DBuf<uint32_t> parent;
     EventSpans<5> spans;             // grid, link, label, compact
-    uint32_t h_count[2] = {0, 0};    // the largest size, the kept components
-    uint32_t components = 0;
 };
+
+void cluster_init_parents(plade_ctx *ctx, uint32_t *d_parent, uint32_t n) {
+    hipLaunchKernelGGL(k_cc_init, dim3(cdiv(n, ROW_TPB)), dim3(ROW_TPB), 0, ctx->stream, d_parent, n);
+}
+
+void cluster_label_select(plade_ctx *ctx, ClusterWork &W, uint32_t n, const uint32_t *d_parent, const uint32_t *d_attach, uint32_t min_size,
+                          uint32_t max_size, uint32_t keep_largest) {
+    uint32_t *d_root = W.root.ensure(n), *d_size = W.size.ensure(n), *d_cnt = W.count.ensure(4);
+    int32_t *d_label = W.label.ensure(n);
+    uint8_t *d_keep = W.keep.ensure((size_t)n + 4), *d_ckept = W.cluster_kept.ensure((size_t)n + 4);
+    uint32_t *d_flags = keep_flags(ctx, W, n);   // first the roots' flags, then the kept points'
+    ctx->fill_async(d_size, 0, (size_t)n * 4);
+    ctx->fill_async(d_cnt, 0, 16);
+    hipLaunchKernelGGL(k_cc_flatten, dim3(cdiv(n, ROW_TPB)), dim3(ROW_TPB), 0, ctx->stream, d_parent, d_attach, n, d_root, d_flags);
+    HIP_TRY(hipGetLastError());
+    const uint32_t C = compact_flags(ctx, d_flags, n, W.root_pos, W.root_list);   // (waits for the count)
+    W.clusters = C;
+    hipLaunchKernelGGL(k_cc_label_size, dim3(cdiv(n, ROW_TPB)), dim3(ROW_TPB), 0, ctx->stream, d_root, W.root_pos.p, n, d_label, d_size);
+    const dim3 cgrid(cdiv(C, ROW_TPB));
+    if (C == 0) {
+        // (DBSCAN with every point noise: nothing to select, d_cnt stays 0)
+    } else if (keep_largest > 0) {
+        unsigned long long *d_key = W.sort_key.ensure(C), *d_key2 = W.sort_key2.ensure(C);
+        uint32_t *d_val = W.sort_val.ensure(C), *d_val2 = W.sort_val2.ensure(C);
+        hipLaunchKernelGGL(k_cc_pass, cgrid, dim3(ROW_TPB), 0, ctx->stream, d_size, C, min_size, max_size, d_ckept, d_key, d_val);
+        HIP_TRY(hipGetLastError());
+        sort_pairs_u64(ctx, reinterpret_cast<const uint64_t *>(d_key), reinterpret_cast<uint64_t *>(d_key2), d_val, d_val2, C, 64);
+        hipLaunchKernelGGL(k_cc_mark_first, cgrid, dim3(ROW_TPB), 0, ctx->stream, d_key2, d_val2, C, keep_largest, d_ckept);
+    } else
+        hipLaunchKernelGGL(k_cc_pass, cgrid, dim3(ROW_TPB), 0, ctx->stream, d_size, C, min_size, max_size, d_ckept, (u64 *)nullptr,
+                           (uint32_t *)nullptr);
+    if (C) hipLaunchKernelGGL(k_cc_summary, cgrid, dim3(ROW_TPB), 0, ctx->stream, d_size, d_ckept, C, d_cnt);
+    hipLaunchKernelGGL(k_cc_keep, dim3(cdiv(n, ROW_TPB)), dim3(ROW_TPB), 0, ctx->stream, d_label, d_ckept, n, d_keep, d_flags);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(W.h_count, d_cnt, 8, hipMemcpyDeviceToHost, ctx->stream));
+}
 
 namespace {
 
@@ -196,38 +213,13 @@ uint32_t components_dev(plade_ctx *ctx, ComponentWork &W, const float *d_rows, u
     a.g = view_of(G, "label_components");
     a.n = n; a.r2 = r * r;
     a.parent = W.parent.ensure(n);
-    hipLaunchKernelGGL(k_cc_init, dim3(cdiv(n, ROW_TPB)), dim3(ROW_TPB), 0, ctx->stream, a.parent, n);
+    cluster_init_parents(ctx, a.parent, n);
     hipLaunchKernelGGL(k_cc_link, dim3(cdiv(n, LINK_TPB)), dim3(LINK_TPB), 0, ctx->stream, a);
     HIP_TRY(hipGetLastError());
     W.spans.mark(ctx, 2);
 
-    uint32_t *d_root = W.root.ensure(n), *d_size = W.size.ensure(n), *d_cnt = W.count.ensure(4);
-    int32_t *d_label = W.label.ensure(n);
-    uint8_t *d_keep = W.keep.ensure((size_t)n + 4), *d_ckept = W.comp_kept.ensure((size_t)n + 4);
-    uint32_t *d_flags = keep_flags(ctx, W, n);   // first the roots' flags, then the kept points'
-    ctx->fill_async(d_size, 0, (size_t)n * 4);
-    ctx->fill_async(d_cnt, 0, 16);
-    hipLaunchKernelGGL(k_cc_flatten, dim3(cdiv(n, ROW_TPB)), dim3(ROW_TPB), 0, ctx->stream, a.parent, n, d_root, d_flags);
-    HIP_TRY(hipGetLastError());
-    const uint32_t C = compact_flags(ctx, d_flags, n, W.root_pos, W.root_list);   // (waits for the count)
-    W.components = C;
-    hipLaunchKernelGGL(k_cc_label_size, dim3(cdiv(n, ROW_TPB)), dim3(ROW_TPB), 0, ctx->stream, d_root, W.root_pos.p, n, d_label, d_size);
-    const dim3 cgrid(cdiv(C, ROW_TPB));
-    if (p.keep_largest > 0) {
-        unsigned long long *d_key = W.sort_key.ensure(C), *d_key2 = W.sort_key2.ensure(C);
-        uint32_t *d_val = W.sort_val.ensure(C), *d_val2 = W.sort_val2.ensure(C);
-        hipLaunchKernelGGL(k_cc_pass, cgrid, dim3(ROW_TPB), 0, ctx->stream, d_size, C, (uint32_t)p.min_size, (uint32_t)p.max_size, d_ckept,
-                           d_key, d_val);
-        HIP_TRY(hipGetLastError());
-        sort_pairs_u64(ctx, reinterpret_cast<const uint64_t *>(d_key), reinterpret_cast<uint64_t *>(d_key2), d_val, d_val2, C, 64);
-        hipLaunchKernelGGL(k_cc_mark_first, cgrid, dim3(ROW_TPB), 0, ctx->stream, d_key2, d_val2, C, (uint32_t)p.keep_largest, d_ckept);
-    } else
-        hipLaunchKernelGGL(k_cc_pass, cgrid, dim3(ROW_TPB), 0, ctx->stream, d_size, C, (uint32_t)p.min_size, (uint32_t)p.max_size, d_ckept,
-                           (u64 *)nullptr, (uint32_t *)nullptr);
-    hipLaunchKernelGGL(k_cc_summary, cgrid, dim3(ROW_TPB), 0, ctx->stream, d_size, d_ckept, C, d_cnt);
-    hipLaunchKernelGGL(k_cc_keep, dim3(cdiv(n, ROW_TPB)), dim3(ROW_TPB), 0, ctx->stream, d_label, d_ckept, n, d_keep, d_flags);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(W.h_count, d_cnt, 8, hipMemcpyDeviceToHost, ctx->stream));
+    cluster_label_select(ctx, W, n, a.parent, nullptr, (uint32_t)p.min_size, (uint32_t)p.max_size, (uint32_t)p.keep_largest);
+    const uint32_t C = W.clusters;
     W.spans.mark(ctx, 3);
 
     const uint32_t total = keep_compact_gather(ctx, W, d_rows, n, stride, dst);
@@ -280,7 +272,7 @@ extern "C" int plade_label_components(plade_ctx *ctx, const float *rows, uint32_
         upload_rows(ctx, W.in, rows, n, stride, mn, mx);
         const uint32_t total = components_dev(ctx, W, W.in.p, n, stride, mn, mx, p, keep_rows_host(W, stride), summary);
         if (label_out) HIP_TRY(hipMemcpyAsync(label_out, W.label.p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-        if (size_out) HIP_TRY(hipMemcpyAsync(size_out, W.size.p, (size_t)W.components * 4, hipMemcpyDeviceToHost, ctx->stream));
+        if (size_out) HIP_TRY(hipMemcpyAsync(size_out, W.size.p, (size_t)W.clusters * 4, hipMemcpyDeviceToHost, ctx->stream));
         keep_copy_out(ctx, W, n, total, stride, keep_out, kept_index_out, rows_out);
         ctx->sync();
         return PLADE_OK;

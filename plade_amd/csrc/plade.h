@@ -110,6 +110,26 @@ struct ComponentFilter {
 bool keep_components(pcl::PointCloud<pcl::PointNormal>::Ptr cloud, pcl::PointCloud<pcl::PointNormal> &filtered, double radius,
                      int min_size = 1, int max_size = 0, int keep_largest = 0, ComponentFilter *info = nullptr);
 
+/** DBSCAN (no counterpart in the reference): the fields of plade_dbscan_summary (include/plade_hip.h). */
+struct CloudClusters {
+    uint64_t n = 0, clusters = 0, core = 0, border = 0, noise = 0;   // points in, clusters found, points of each kind
+    uint64_t kept_clusters = 0, kept = 0;                            // clusters and points kept
+    uint32_t largest = 0;                                            // the size of the largest cluster
+};
+/** Clusters a cloud by density on the GPU (plade_cluster_dbscan; radius absolute, in the cloud's units; fp32 squared distance, strict
+ *  <): a point with at least min_points points closer than radius, itself included, is a core point; the clusters are the connected
+ *  components of the core points; a non-core point with a core point closer than radius joins the cluster of the nearest one (ties:
+ *  the smaller index); the rest is noise.  Unlike keep_components, one thin thread of stray points joins no two objects.  `labels`
+ *  receives one id per point of *cloud (ascending in the order of a cluster's smallest core index, -1 = noise); `filtered` the points
+ *  of the clusters that hold at least min_size points -- with keep_largest = m > 0 only of the m largest -- in their original order,
+ *  coordinates and normals copied bit for bit (it may be *cloud).  false: invalid input or no GPU; a message is printed and
+ *  `filtered` and `labels` are unchanged.  The CLI and the file overload of registration() filter both clouds of a pair after
+ *  PLADE_KEEP_COMPONENTS and before PLADE_SMOOTH when PLADE_DBSCAN=<radius>,<min_points>[,<min_size>[,<keep_largest>]] is set, and
+ *  print one line per cloud; PLADE_M3C2_CLUSTERS=<radius>[,<min_points>[,<min_size>]] groups the significant core points of
+ *  PLADE_M3C2 into objects of change. */
+bool cluster_cloud(pcl::PointCloud<pcl::PointNormal>::Ptr cloud, pcl::PointCloud<pcl::PointNormal> &filtered, std::vector<int32_t> &labels,
+                   double radius, int min_points = 4, int min_size = 1, int keep_largest = 0, CloudClusters *info = nullptr);
+
 /** Subsampling (no counterpart in the reference): the fields of plade_subsample_summary (include/plade_hip.h). */
 struct CloudSubsample {
     uint32_t n = 0, kept = 0, rounds = 0;   // points in, points kept, synchronous rounds until every point was decided

@@ -43,7 +43,7 @@ void trace(const char *what) {
 // parser has to say about a rejected value goes to std::cerr, not to the calling thread's console.
 using cli_switches::GicpSwitch; using cli_switches::M3c2Switch; using cli_switches::FpfhSwitch; using cli_switches::FeatureRegisterSwitch;
 using cli_switches::KeypointSwitch; using cli_switches::OutlierSwitch; using cli_switches::ComponentSwitch; using cli_switches::SmoothSwitch;
-using cli_switches::SubsampleSwitch; using cli_switches::OrientSwitch; using cli_switches::ScaleSwitch;
+using cli_switches::SubsampleSwitch; using cli_switches::OrientSwitch; using cli_switches::ScaleSwitch; using cli_switches::DbscanSwitch;
 template <class S> S latched(const cli_switches::Parsed<S> &p) {
     if (!p.warning.empty()) std::cerr << p.warning << std::endl;
     return p.value;
@@ -339,6 +339,51 @@ bool subsample_in_place(std::vector<float> &buf) {
     return true;
 }
 
+// PLADE_DBSCAN=<radius>,<min_points>[,<min_size>[,<keep_largest>]] (opt-in, unset = off; the radius absolute, in the clouds' units): both
+// clouds of a pair keep only the points of their DBSCAN clusters (plade_cluster_dbscan: a core point has at least min_points points
+// closer than radius, itself included; border points join the cluster of their nearest core point; noise goes) with at least
+// min_size points (1 when not given), with keep_largest = m > 0 only the m largest of them, after PLADE_KEEP_COMPONENTS and before
+// PLADE_SMOOTH; one console line per cloud.  A value that does not parse (radius not positive and finite or so small that its fp32
+// square is below FLT_MIN, min_points or min_size not an integer >= 1, keep_largest not an integer >= 0, anything behind them) prints
+// one warning and filters nothing; unset, nothing changes.
+const DbscanSwitch &dbscan_switch() {
+    static const DbscanSwitch sw = latched(cli_switches::parse_dbscan(getenv("PLADE_DBSCAN")));
+    return sw;
+}
+// the rows (`stride` floats each) that DBSCAN keeps, into `out`, which may be `rows` itself (every float keeps its bits); label: one
+// int32 per input point when wanted.  false: a message has been printed
+bool dbscan_packed(plade_ctx *ctx, const float *rows, size_t n, uint32_t stride, double radius, int min_points, int min_size, int keep_largest,
+                   int32_t *label, float *out, plade_dbscan_summary &s) {
+    plade_dbscan_params prm;
+    plade_dbscan_default_params(&prm);
+    prm.radius = radius; prm.min_points = min_points; prm.min_size = min_size; prm.keep_largest = keep_largest;
+    trace("dbscan: clustering");
+    // (in place: the upload of the rows precedes the read-back of the kept ones on the context's stream)
+    const int rc = plade_cluster_dbscan(ctx, rows, (uint32_t)n, stride, &prm, label, nullptr, nullptr, nullptr, nullptr, out, &s);
+    trace("dbscan: done");
+    if (rc != PLADE_OK) {
+        con_err() << "clustering failed: " << plade_last_error(ctx) << std::endl;
+        return false;
+    }
+    return true;
+}
+bool dbscan_in_place(std::vector<float> &buf) {
+    const DbscanSwitch &sw = dbscan_switch();
+    if (!sw.on || buf.empty()) return true;
+    plade_ctx *ctx = context();
+    if (!ctx) return false;
+    plade_dbscan_summary s;
+    if (!dbscan_packed(ctx, buf.data(), buf.size() / 6, 6, sw.radius, sw.min_points, sw.min_size, sw.keep_largest, nullptr, buf.data(), s))
+        return false;
+    buf.resize((size_t)s.kept * 6);
+    char b[280];
+    snprintf(b, sizeof(b), "dbscan: kept %llu of %llu points in %llu of %llu clusters (largest %u; %llu core, %llu border, %llu noise)",
+             (unsigned long long)s.kept, (unsigned long long)s.n, (unsigned long long)s.kept_clusters, (unsigned long long)s.clusters, s.largest,
+             (unsigned long long)s.core, (unsigned long long)s.border, (unsigned long long)s.noise);
+    con_out() << b << std::endl;
+    return true;
+}
+
 // PLADE_M3C2=<radius>,<depth>[,<min_points>[,<reg_error>]] (opt-in, absolute, in the clouds' units): every pair that registered -- after
 // the ICP / GICP refinement when that is on -- is compared by M3C2 distances on the GPU (plade_cloud_m3c2: core points = reference
 // = the target with its normals, compared = the source under the final transformation; min_points 4 and reg_error 0 when not
@@ -350,14 +395,15 @@ const M3c2Switch &m3c2_switch() {
     return sw;
 }
 // M3C2 of the packed source under T16 against the packed reference at the given core points (all x y z nx ny nz rows); dist: one
-// double per core point when wanted.  false: a message has been printed
+// double per core point when wanted; significant: one byte 0 / 1 per core point when wanted.  false: a message has been printed
 bool m3c2_packed(plade_ctx *ctx, const float *T16, const float *core, size_t m, const float *ref, size_t n_a, const float *cmp, size_t n_b,
-                 double radius, double depth, int min_points, double reg_error, double *dist, plade_m3c2_summary &s) {
+                 double radius, double depth, int min_points, double reg_error, double *dist, plade_m3c2_summary &s,
+                 uint8_t *significant = nullptr) {
     plade_m3c2_params prm;
     plade_m3c2_default_params(&prm);
     prm.radius = radius; prm.depth = depth; prm.min_points = min_points; prm.reg_error = reg_error;
     trace("m3c2: comparing");
-    const int rc = plade_cloud_m3c2(ctx, core, (uint32_t)m, ref, (uint32_t)n_a, 6, cmp, (uint32_t)n_b, 6, T16, &prm, dist, nullptr, nullptr,
+    const int rc = plade_cloud_m3c2(ctx, core, (uint32_t)m, ref, (uint32_t)n_a, 6, cmp, (uint32_t)n_b, 6, T16, &prm, dist, nullptr, significant,
                                     nullptr, nullptr, nullptr, &s);
     trace("m3c2: done");
     if (rc != PLADE_OK) {
@@ -386,6 +432,17 @@ const SubsampleSwitch &m3c2_core_switch() {
 // keep their normals; unset, nothing changes.
 const ScaleSwitch &m3c2_normals_switch() {
     static const ScaleSwitch sw = latched(cli_switches::parse_m3c2_normals(getenv("PLADE_M3C2_NORMALS")));
+    return sw;
+}
+// PLADE_M3C2_CLUSTERS=<radius>[,<min_points>[,<min_size>]] (opt-in; absolute, in the clouds' units; it acts only together with PLADE_M3C2):
+// the significant core points of the comparison are grouped into objects of change by DBSCAN on their positions
+// (plade_cluster_dbscan; min_points 4 and min_size 1 when not given), and one console line after the m3c2 line reports the clusters
+// that hold at least min_size points, the significant core points, the largest cluster and the points left as noise; with no
+// significant core point the line carries zeros and the library is not called.  A value that does not parse (radius not positive
+// and finite or so small that its fp32 square is below FLT_MIN, min_points or min_size not an integer >= 1, anything behind them)
+// prints one warning and clusters nothing; unset, nothing changes.
+const DbscanSwitch &m3c2_clusters_switch() {
+    static const DbscanSwitch sw = latched(cli_switches::parse_m3c2_clusters(getenv("PLADE_M3C2_CLUSTERS")));
     return sw;
 }
 // the multi-scale normals of the packed rows at `query` (k ascending indices; nullptr: all n points) into nrm (3 floats per query);
@@ -438,11 +495,25 @@ void m3c2_line(plade_ctx *ctx, const float *T16, const float *tg, size_t n_t, co
                  (unsigned long long)qs.fitted, (unsigned long long)qs.queries, hist.c_str(), qs.max_count);
         con_out() << b << std::endl;
     }
+    const DbscanSwitch &cl = m3c2_clusters_switch();
+    std::vector<uint8_t> sig(cl.on ? m : 0);
     plade_m3c2_summary s;
-    if (!m3c2_packed(ctx, T16, cp, m, tg, n_t, sr, n_s, sw.radius, sw.depth, sw.min_points, sw.reg_error, nullptr, s)) return;
+    if (!m3c2_packed(ctx, T16, cp, m, tg, n_t, sr, n_s, sw.radius, sw.depth, sw.min_points, sw.reg_error, nullptr, s, cl.on ? sig.data() : nullptr))
+        return;
     char b[280];
     snprintf(b, sizeof(b), "m3c2: %llu of %llu core points valid, %llu significant (mean %.6g, rms %.6g, max %.6g)", (unsigned long long)s.valid,
              (unsigned long long)s.m, (unsigned long long)s.significant, s.mean, s.rms, s.max);
+    con_out() << b << std::endl;
+    if (!cl.on) return;
+    std::vector<float> change;                   // the positions of the significant core points, in core order
+    for (size_t i = 0; i < m; ++i)
+        if (sig[i]) change.insert(change.end(), cp + 6 * i, cp + 6 * i + 3);
+    plade_dbscan_summary d;
+    memset(&d, 0, sizeof(d));
+    if (!change.empty() && !dbscan_packed(ctx, change.data(), change.size() / 3, 3, cl.radius, cl.min_points, cl.min_size, 0, nullptr, nullptr, d))
+        return;
+    snprintf(b, sizeof(b), "m3c2 clusters: %llu clusters of %llu significant core points (largest %u, noise %llu)",
+             (unsigned long long)d.kept_clusters, (unsigned long long)(change.size() / 3), d.largest, (unsigned long long)d.noise);
     con_out() << b << std::endl;
 }
 
@@ -940,7 +1011,7 @@ bool register_packed(Eigen::Matrix<float, 4, 4> &transformation, const float *tg
 // file that had none (estimate), then the consistent orientation and the subsample when they are switched on.  false: a message has
 // been printed
 bool prepare_loaded(const std::string &file_name, std::vector<float> &buf, bool estimate) {
-    if (!remove_outliers_in_place(buf) || !keep_components_in_place(buf) || !smooth_in_place(buf)) return false;
+    if (!remove_outliers_in_place(buf) || !keep_components_in_place(buf) || !dbscan_in_place(buf) || !smooth_in_place(buf)) return false;
     if (estimate && !buf.empty() && !estimate_in_place(file_name, buf)) return false;
     return orient_in_place(buf) && subsample_in_place(buf);
 }
@@ -1177,6 +1248,24 @@ bool keep_components(pcl::PointCloud<pcl::PointNormal>::Ptr cloud, pcl::PointClo
     if (!components_packed(ctx, buf, radius, min_size, max_size, keep_largest, s)) return false;
     unflatten(buf.data(), (size_t)s.kept, filtered);
     if (info) { info->n = s.n; info->components = s.components; info->kept_components = s.kept_components; info->kept = s.kept; info->largest = s.largest; }
+    return true;
+}
+
+// DBSCAN: see plade.h
+bool cluster_cloud(pcl::PointCloud<pcl::PointNormal>::Ptr cloud, pcl::PointCloud<pcl::PointNormal> &filtered, std::vector<int32_t> &labels,
+                   double radius, int min_points, int min_size, int keep_largest, CloudClusters *info) {
+    plade_ctx *ctx = context();
+    if (!ctx) return false;
+    std::vector<float> buf = flatten(*cloud);
+    std::vector<int32_t> lab(cloud->size());
+    plade_dbscan_summary s;
+    if (!dbscan_packed(ctx, buf.data(), cloud->size(), 6, radius, min_points, min_size, keep_largest, lab.data(), buf.data(), s)) return false;
+    unflatten(buf.data(), (size_t)s.kept, filtered);
+    labels.swap(lab);
+    if (info) {
+        info->n = s.n; info->clusters = s.clusters; info->core = s.core; info->border = s.border; info->noise = s.noise;
+        info->kept_clusters = s.kept_clusters; info->kept = s.kept; info->largest = s.largest;
+    }
     return true;
 }
 

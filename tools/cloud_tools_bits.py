@@ -10,8 +10,8 @@ field (floats in hex).  One process per library:
     python tools/cloud_tools_bits.py plade_amd/libplade_hip.so      > new.txt
     cmp old.txt new.txt && sha1sum new.txt
 
-A tool that only the newer build has adds lines (the multi-scale normals: `scales_*`, at the end of each block); run the older build
-from its own checkout and compare the lines both print.
+A tool that only the newer build has adds lines (the multi-scale normals: `scales_*`, then DBSCAN: `dbscan*`, at the end of each
+block); run the older build from its own checkout and compare the lines both print.
 """
 import hashlib
 import os
@@ -103,6 +103,9 @@ def run(ctx, name, tgt, src, T, r):
     line("scales_planarity", ctx.scale_features(tgt, rs, mode=0, moments=True))
     line("scales_variation_own_normals", ctx.scale_features(tgt, rs, mode=1, orient=1, query_index=np.arange(0, len(tgt), 3), moments=True))
     resident("scales_dev", ctx.scale_normals_dev(ct, rs, orient=1, info=True))
+    # (DBSCAN, added after them, the same way)
+    line("dbscan", ctx.dbscan(tgt, 0.5 * r, min_points=4, min_size=3, keep_largest=2))
+    resident("dbscan_dev", ctx.dbscan_dev(ct, 0.5 * r, min_points=4, min_size=3, keep_largest=2, info=True))
     ct.free()
     cs.free()
     return out
